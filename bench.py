@@ -99,7 +99,12 @@ def parse():
                    help="A/B runs: a diagnostic knob of the library (mg_debug_set; include/metalign_hip.h), recorded in config.knobs")
     p.add_argument("--dry_run", action="store_true",
                    help="plumbing check only: rendezvous + the known-answer collectives, one JSON line, no GPU work")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write what the last timed step computed to DIR/<name>.npy (float64; the inputs are seeded, so two builds "
+                        "compare output for output)")
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
     return a
 
 
@@ -402,6 +407,30 @@ def committed_run(name, cfg):
     return best
 
 
+DUMP_BYTES = 60 * 10**6  # the arrays' bytes: with the .npy headers the files stay under 64 MB
+
+
+def step_outputs(out):
+    """What a caller of the timed path receives from one step (ShardJob.run's result), as float64 copies: every count is an
+    integer below 2^53 and exact in float64 (first_seen of a taxon no read reached is UINT64_MAX, which becomes 2^64)."""
+    arrays = {name: np.array(out[name], dtype=np.float64)
+              for name in ("hits_k", "sizes_k", "containment_k", "count", "bases", "first_seen", "sketch_sizes")}
+    arrays["tot_rds_n_ambig"] = np.array([out["tot_rds"], out["n_ambig"]], dtype=np.float64)
+    return arrays
+
+
+def dump_outputs(arrays, dirpath):
+    """DIR/<name>.npy per array; over DUMP_BYTES in all, every array is cut to the same fraction of its elements, chosen
+    with a fixed seed (the same positions for the same shapes)."""
+    os.makedirs(dirpath, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            keep = max(1, a.size * DUMP_BYTES // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+
+
 def secondary_config1(hip, args):
     """configs[1] (1M reads, 1k genomes, k = 21) in the same process: reads/s of the pipelined passes."""
     cfg = dict(PRESETS[1], config=1, match=_match_for(args, PRESETS[1]["ks"]) if args.definition == "reference_pipeline" else None)
@@ -647,6 +676,8 @@ def main():
     out = job.run(args.steps)  # K passes, software-pipelined (stage A of pass i+1 is queued before pass i is finished)
     sync()
     dt = time.perf_counter() - t0
+    # copied before the untimed steps below, which may reuse the host buffers the results were read into
+    outputs = step_outputs(out) if args.dump_outputs and rank == 0 else None
     nk1, k1_ms = hip.prof_get(k1_name)
     # per-kernel table from a few extra, untimed steps on ONE stream (nothing overlaps: clean per-family times)
     kernels_ms = {}
@@ -672,6 +703,8 @@ def main():
         dt = float(tmax.item())
 
     if rank == 0:
+        if outputs is not None:
+            dump_outputs(outputs, args.dump_outputs)
         ms = 1e3 * dt / args.steps
         k1_per_pass_ms = k1_ms / max(args.steps, 1)  # all k of one pass (one fused launch, or one launch per k)
         launches_per_pass = nk1 / max(args.steps, 1)

@@ -44,6 +44,32 @@ def test_a_failing_rank_fails_the_command():
     assert not [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
 
 
+def test_dump_outputs_are_float64_copies_and_a_seeded_sample_over_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: every array a step returns as float64, exact; over the byte cap the same positions every time."""
+    import numpy as np
+
+    import bench
+    step = {"hits_k": np.arange(12, dtype=np.uint32).reshape(3, 4), "sizes_k": np.full((3, 4), 9, dtype=np.uint32),
+            "containment_k": np.arange(12).reshape(3, 4) / 9.0, "count": np.array([3, 0], dtype=np.uint64),
+            "bases": np.array([450, 0], dtype=np.uint64), "first_seen": np.array([5, 2**64 - 1], dtype=np.uint64),
+            "sketch_sizes": [77], "tot_rds": 3, "n_ambig": 1}
+    arrays = bench.step_outputs(step)
+    bench.dump_outputs(arrays, str(tmp_path / "all"))
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "all" / (name + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, a), name
+    assert np.array_equal(np.load(tmp_path / "all" / "hits_k.npy"), step["hits_k"])
+    assert np.load(tmp_path / "all" / "tot_rds_n_ambig.npy").tolist() == [3.0, 1.0]
+    monkeypatch.setattr(bench, "DUMP_BYTES", 480)
+    big = {"x": np.arange(100, dtype=np.float64), "y": -np.arange(50, dtype=np.float64)}
+    for d in ("s1", "s2"):
+        bench.dump_outputs(big, str(tmp_path / d))
+    for name in big:
+        a1, a2 = np.load(tmp_path / "s1" / (name + ".npy")), np.load(tmp_path / "s2" / (name + ".npy"))
+        assert np.array_equal(a1, a2) and 0 < a1.size < big[name].size and np.isin(a1, big[name]).all()
+    assert sum(np.load(tmp_path / "s1" / (n + ".npy")).nbytes for n in big) <= 480
+
+
 def test_selfcheck_catches_misdelivered_data():
     """The known-answer check itself: a transport that swaps two ranks' all-gather contributions must be caught."""
     import numpy as np

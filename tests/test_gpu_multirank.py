@@ -119,9 +119,6 @@ def _oracle_sketch_threads(oracle_lib, rb, ro, k, hmax, table_hashes, nthreads):
     return uh, uc
 
 
-@pytest.mark.skipif(os.environ.get("MG_TEST_CONFIG3_HASH") != "1",
-                    reason="the hash-range path of rounds 2-5 at configs[3] size (68 s): on request, MG_TEST_CONFIG3_HASH=1; since round 6 "
-                           "bench.py --gpus N runs stage A by k-mer identity (test_config3_default_path_at_full_size_with_every_collective)")
 def test_config3_one_rank_share_full_size(hip, oracle_lib):
     """BASELINE.json configs[3] as ONE of its 8 ranks sees it: 12.5M reads (100M / 8) and a 1/8 hash-range slice of the
     200k-genome table, K = {21,31,51}; 5 kb genomes put the table's largest hash at a fifth of the hash range — the
