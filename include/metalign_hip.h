@@ -79,7 +79,10 @@ int mg_device_count(void);
  * the host inflater, whose memory is bounded by its pieces; the device inflater holds the whole compressed file), shares_threads (mg_multimapped_shares: 1 = the serial loop, 2 / 4 / 8 host threads; 0 = by the list's length),
  * kc_wg_per_cu, kc_ablate (k_count_kmers: workgroups per CU; measurements only — 1: the minimizer runs are dropped, 2: ... after the
  *   gate, 3: no entry is matched, 5: nothing is counted, 6: the tiles are staged and nothing else, 7: ... staged from 8 KB that
- *   stay in the caches, the runs dropped); kc_gate_extra (mg_refdb_index_kmers: the gate has 2^this bits per k-mer; default 6).
+ *   stay in the caches, the runs dropped); kc_gate_extra (mg_refdb_index_kmers: the gate has 2^this bits per k-mer; default 6);
+ * kc_grid, k1_grid, kb_grid (test hooks, k3_grid's meaning for stages A and B: a value > 0 below the computed grid becomes the
+ *   grid of k_count_kmers, of k_sketch_reads / k_sketch_reads_multi[_resident], of k_contain_pairs / k_match_pairs /
+ *   k_refpipe_count — few workgroups, so that each loops over many tiles).
  * Needs no device and no mg_init.  MG_ERR_ARG for a key that does not exist. */
 int mg_debug_set(const char* key, int64_t value);
 int64_t mg_debug_get(const char* key);

@@ -706,9 +706,9 @@ static int containment_launch(int nk, const mg_sketch* const* qs, const mg_db* c
   ProfScope ps("containment");
   if (tiles) {
     if (rp)
-      hipLaunchKernelGGL(k_contain_pairs<true>, dim3(grid_for(tiles, 1, (unsigned)c.num_cus * 6)), dim3(kCT), 0, st, a);
+      hipLaunchKernelGGL(k_contain_pairs<true>, dim3(grid_cap(grid_for(tiles, 1, (unsigned)c.num_cus * 6), "kb_grid")), dim3(kCT), 0, st, a);
     else
-      hipLaunchKernelGGL(k_contain_pairs<false>, dim3(grid_for(tiles, 1, (unsigned)c.num_cus * 6)), dim3(kCT), 0, st, a);
+      hipLaunchKernelGGL(k_contain_pairs<false>, dim3(grid_cap(grid_for(tiles, 1, (unsigned)c.num_cus * 6), "kb_grid")), dim3(kCT), 0, st, a);
   }
   hipLaunchKernelGGL(k_contain_reduce, dim3(grid_for(reduce_work, 256, (unsigned)c.num_cus * 4)), dim3(256), 0, st, a);
   MG_HIP(hipGetLastError());
@@ -762,7 +762,7 @@ static int match_launch(const uint32_t* d_counts, const mg_refdb* rp, uint32_t c
   ProfScope ps("containment");
   const uint64_t work = a.nzero > a.nzero2 ? a.nzero : a.nzero2;
   hipLaunchKernelGGL(k_build_index, dim3(grid_for(work ? work : 1, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, a);  // (zeroes; no index here)
-  if (a.ntiles) hipLaunchKernelGGL(k_match_pairs<true>, dim3(grid_for(a.ntiles, 1, (unsigned)c.num_cus * 8)), dim3(kCT), 0, st, a);
+  if (a.ntiles) hipLaunchKernelGGL(k_match_pairs<true>, dim3(grid_cap(grid_for(a.ntiles, 1, (unsigned)c.num_cus * 8), "kb_grid")), dim3(kCT), 0, st, a);
   hipLaunchKernelGGL(k_contain_reduce, dim3(grid_for(db->ngenomes, 256, (unsigned)c.num_cus * 4)), dim3(256), 0, st, a);
   MG_HIP(hipGetLastError());
   return MG_OK;
@@ -808,7 +808,7 @@ static int refpipe_count_launch(const mg_refdb* rp, const uint32_t* const* d_mar
   if (!prezeroed)
     hipLaunchKernelGGL(k_zero_u32, dim3(grid_for((uint64_t)m * copies * G, 256, (unsigned)c.num_cus * 8)), dim3(256), 0, st, d_part,
                        (uint64_t)m * copies * G);
-  if (tiles) hipLaunchKernelGGL(k_refpipe_count, dim3(grid_for(tiles, 1, (unsigned)c.num_cus * 8)), dim3(kCT), 0, st, a);
+  if (tiles) hipLaunchKernelGGL(k_refpipe_count, dim3(grid_cap(grid_for(tiles, 1, (unsigned)c.num_cus * 8), "kb_grid")), dim3(kCT), 0, st, a);
   hipLaunchKernelGGL(k_refpipe_reduce, dim3(grid_for(G, 256, (unsigned)c.num_cus * 4)), dim3(256), 0, st, a);
   MG_HIP(hipGetLastError());
   return MG_OK;

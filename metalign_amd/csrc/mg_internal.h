@@ -192,6 +192,12 @@ inline unsigned grid_for(uint64_t items, unsigned per_block, unsigned max_blocks
   if (b > max_blocks) b = max_blocks;
   return (unsigned)b;
 }
+// test hooks (kc_grid, k1_grid, kb_grid): a persistent kernel on fewer workgroups than it would take, so that each of them
+// loops over many tiles — the knob's value when it is > 0 and below `grid`, else `grid`
+inline unsigned grid_cap(unsigned grid, const char* key) {
+  const int64_t v = dbg(key);
+  return v > 0 && (uint64_t)v < grid ? (unsigned)v : grid;
+}
 
 // ---- internal services implemented in mg_sort.hip (rocPRIM-backed plain library ops) ----
 // Sorts n u64 keys ascending using bits [0,end_bit). out may not alias in.

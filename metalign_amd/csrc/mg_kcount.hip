@@ -970,7 +970,7 @@ int mg_count_kmers_dev(const uint8_t* d_bases, const uint64_t* d_offsets, uint64
   if (dbg("kc_wg_per_cu") > 0) per_cu = (unsigned)dbg("kc_wg_per_cu");
   if (c.a_side && c.a_side_wg_per_cu && per_cu > c.a_side_wg_per_cu) per_cu = c.a_side_wg_per_cu;
   const uint64_t ntiles = (nreads + 63) / 64;
-  const unsigned grid = grid_for(ntiles, kKcWaves, (unsigned)c.num_cus * per_cu);
+  const unsigned grid = grid_cap(grid_for(ntiles, kKcWaves, (unsigned)c.num_cus * per_cu), "kc_grid");
   KcArgs a{d_bases, d_offsets, nreads, kc->live.as<uint32_t>(), ix.shared.as<uint32_t>(), ix.prim.as<KcEntry>(), ix.ovf.as<KcEntry>(), kc->counts.as<uint32_t>(),
            kc->sat.as<uint32_t>(), kc->stats.as<unsigned long long>(), (32u - ix.gbits) | (kc->epoch << 8), ix.bmask, (uint32_t)sd, c.count_sat, (uint32_t)dbg("kc_ablate"), (uint32_t)dbg("kc_stagger")};
   {

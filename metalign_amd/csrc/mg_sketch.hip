@@ -501,7 +501,7 @@ static int launch_sketch_reads(const uint8_t* d_bases, const uint64_t* d_offsets
   // trips beside this kernel (the multi-GPU exchange) wants them to get issue slots — two per CU cost this kernel
   // ~12 % and took the exchange pass from 0.99 to 0.73 ms; a single-shard job leaves it at the LDS limit.
   if (c.a_side && c.is_stage_a(c.stream) && c.a_side_wg_per_cu && per_cu > c.a_side_wg_per_cu) per_cu = c.a_side_wg_per_cu;
-  unsigned grid = grid_for(ntiles, kWavesPerBlock, (unsigned)c.num_cus * per_cu);
+  const unsigned grid = grid_cap(grid_for(ntiles, kWavesPerBlock, (unsigned)c.num_cus * per_cu), "k1_grid");
   ProfScope ps("sketch_reads");
   // (epoch != 0: d_tab is a resident index — the kernel takes "no filter words, a mask" as that and the mask as the epoch)
   const uint32_t* fb = filter && !epoch ? filter->bits.as<uint32_t>() : (const uint32_t*)nullptr;

@@ -417,7 +417,7 @@ static int launch_multi(const uint8_t* d_bases, const uint64_t* d_offsets, uint6
   if (per_cu < 1) per_cu = 1;
   if (per_cu > 8) per_cu = 8;
   if (c.a_side && c.is_stage_a(c.stream) && c.a_side_wg_per_cu && per_cu > c.a_side_wg_per_cu) per_cu = c.a_side_wg_per_cu;
-  const unsigned grid = grid_for(ntiles, kWavesPerBlock, (unsigned)c.num_cus * per_cu);
+  const unsigned grid = grid_cap(grid_for(ntiles, kWavesPerBlock, (unsigned)c.num_cus * per_cu), "k1_grid");
   ProfScope ps("sketch_reads");
   if (a.epoch && c.hash_mode == kHashCmash)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sketch_reads_multi_resident<KL, kHashCmash>), dim3(grid), dim3(kBlock), lds, c.stream, d_bases,

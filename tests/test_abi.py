@@ -47,3 +47,23 @@ def test_product_never_imports_oracle():
                 src = open(os.path.join(dirpath, f)).read()
                 assert not re.search(r"^\s*(import|from)\s+oracle\b", src, flags=re.M), f
                 assert "libmg_oracle" not in src, f
+
+
+def test_stage_a_and_b_grid_knobs():
+    """kc_grid, k1_grid, kb_grid (test hooks: the grids of stages A and B cut to a few workgroups) are knobs of mg_debug_set: they
+    read back, debug_set(None) clears them, a key that does not exist still fails.  Needs no device."""
+    import pytest
+    keys = ("kc_grid", "k1_grid", "kb_grid")
+    try:
+        for i, key in enumerate(keys):
+            assert _hip.debug_get(key) == 0
+            _hip.debug_set(key, i + 1)
+        assert [_hip.debug_get(key) for key in keys] == [1, 2, 3]
+        assert _hip.debug_get("k3_grid") == 0
+        _hip.debug_set(None)
+        assert [_hip.debug_get(key) for key in keys] == [0, 0, 0]
+        for bad in ("kc_grids", "k2_grid", "kb"):
+            with pytest.raises(_hip.HipError):
+                _hip.debug_set(bad, 1)
+    finally:
+        _hip.debug_set(None)

@@ -878,3 +878,119 @@ def test_dropping_a_resident_index_leaves_the_bit_filter(hip, oracle_lib):
     sk.free()
     filt.drop_resident()  # (nothing to drop: fine)
     filt.free()
+
+
+# ---- many tiles per wavefront: the stage-A sketch kernels are persistent; their candidate buffer (CandSink / MultiSink) carries
+# across tiles, is flushed when nearly full and once more at the kernel's end, and the per-lane totals are added at the end only.
+# k1_grid (a test hook) cuts the grid to 1 or 3 workgroups: 78 or 26 tiles of every kind util.tile_sample makes to a wavefront.
+def _tiled_reads(seed, k, ntiles=313, last=37):
+    rng = np.random.default_rng(seed)
+    gb, go = util.tile_genomes(rng)
+    kinds = util.tile_kinds(rng, ntiles)
+    bases, offsets = util.tile_sample(rng, gb, go, kinds, k, last=last)
+    for grid in (1, 3):
+        missing = util.TILE_TRANSITIONS - util.tile_transitions(kinds, grid)
+        assert not missing, (grid, missing)
+    return rng, gb, go, bases, offsets
+
+
+@pytest.mark.parametrize("k", [21, 32, 33, 60])
+def test_sketch_reads_tile_by_tile_with_many_tiles_per_wavefront(hip, oracle_lib, knobs, k):
+    """k_sketch_reads on k1_grid 1, 3 and the launcher's grid: every k-mer a candidate and a bottom-s cut (the buffer flushed many
+    times a tile), and a small threshold (few candidates, a flush every few tiles): hashes, counts, truncation and k-mers seen."""
+    _, _, _, bases, offsets = _tiled_reads(7100 + k, k)
+    for hmax, s in ((U64_MAX, 5000), (int(0.002 * 2 ** 64), 0)):
+        oh, oc, otr, oseen = oracle_lib.sketch_reads(bases, offsets, k, hmax=hmax, s=s)
+        assert otr == (s > 0)
+        for grid in (1, 3, 0):
+            knobs("k1_grid", grid)
+            h, c, trunc, seen = hip.sketch_reads(bases, offsets, k, hmax=hmax, s=s)
+            case = "k=%d hmax=%#x s=%d k1_grid=%d" % (k, hmax, s, grid)
+            assert (trunc, seen) == (otr, oseen), case
+            assert np.array_equal(h, oh) and np.array_equal(c, oc), case
+
+
+@pytest.mark.parametrize("ks", [(21, 31, 51), (30, 40, 50, 60)])
+def test_multi_k_sketch_tile_by_tile_with_many_tiles_per_wavefront(hip, oracle_lib, knobs, ks):
+    """The fused kernel (k_sketch_reads_multi) on k1_grid 1, 3 and the launcher's grid, with the tables' filters and without (then
+    every k-mer is a candidate: a threshold that leaves few would take one launch per k, the list path): every k's sketch equals
+    the oracle's."""
+    _, gb, go, bases, offsets = _tiled_reads(7200 + sum(ks), ks[0])
+    nreads = len(offsets) - 1
+    d_b, d_o = hip.array(bases), hip.array(offsets)
+    tables = [oracle_lib.sketch_genomes(gb, go, k, 1500)[0] for k in ks]
+    for filtered in (False, True):
+        hmaxs = [int(t.max()) for t in tables] if filtered else [U64_MAX] * len(ks)
+        filts = [hip.filter_build(t) for t in tables] if filtered else None
+        want = [oracle_lib.sketch_reads_filtered(bases, offsets, k, tables[i], hmax=hmaxs[i]) if filtered
+                else oracle_lib.sketch_reads(bases, offsets, k, hmax=hmaxs[i]) for i, k in enumerate(ks)]
+        for grid in (1, 3, 0):
+            knobs("k1_grid", grid)
+            sks = hip.sketch_reads_multi_dev_async(d_b.ptr, d_o.ptr, nreads, list(ks), hmaxs, 0, filts)
+            for i, k in enumerate(ks):
+                h, c = sks[i].download()
+                oh, oc, _, oseen = want[i]
+                case = "ks=%s k=%d filtered=%s k1_grid=%d" % (ks, k, filtered, grid)
+                assert np.array_equal(h, oh) and np.array_equal(c, oc), case
+                assert sks[i].kmers_seen == oseen, case
+            for x in sks:
+                x.free()
+        for f in filts or []:
+            f.free()
+    d_b.free()
+    d_o.free()
+
+
+def test_resident_index_sketch_tile_by_tile_with_many_tiles_per_wavefront(hip, oracle_lib, knobs):
+    """k_sketch_reads_multi_resident and the one-k kernel against resident indexes on k1_grid 1, 3 and the launcher's grid: the
+    exact intersection of the reads' k-mers with the table's hashes."""
+    ks = (21, 31, 51)
+    _, gb, go, bases, offsets = _tiled_reads(7300, ks[0])
+    nreads = len(offsets) - 1
+    d_b, d_o = hip.array(bases), hip.array(offsets)
+    tabs = [oracle_lib.sketch_genomes(gb, go, k, 1500)[0] for k in ks]
+    hmaxs = [int(t.max()) for t in tabs]
+    filts = [hip.filter_build(t) for t in tabs]
+    for f, t, hm in zip(filts, tabs, hmaxs):
+        assert f.make_resident(t, hm, 0)
+    want = [_exact_sketch(oracle_lib, bases, offsets, k, tabs[i], hmaxs[i]) for i, k in enumerate(ks)]
+    for grid in (1, 3, 0):
+        knobs("k1_grid", grid)
+        sks = hip.sketch_reads_multi_dev_async(d_b.ptr, d_o.ptr, nreads, list(ks), hmaxs, 0, filts)
+        for i, k in enumerate(ks):
+            eh, ec, seen = want[i]
+            case = "k=%d k1_grid=%d" % (k, grid)
+            h, c = sks[i].download()
+            assert np.array_equal(h, eh) and np.array_equal(c, ec) and sks[i].kmers_seen == seen, ("fused", case)
+            one = hip.sketch_reads_dev(d_b.ptr, d_o.ptr, nreads, k, hmaxs[i], 0, filt=filts[i])
+            h1, c1 = one.download()
+            assert np.array_equal(h1, eh) and np.array_equal(c1, ec) and one.kmers_seen == seen, ("one k", case)
+            one.free()
+        for x in sks:
+            x.free()
+    for f in filts:
+        f.free()
+    d_b.free()
+    d_o.free()
+
+
+def test_cmash_sketch_tile_by_tile_with_many_tiles_per_wavefront(hip, oracle_lib, knobs, cmash_mode):
+    """Hash definition 1: the one-k kernel and the fused one on k1_grid 1, 3 and the launcher's grid equal the oracle."""
+    ks = (21, 31, 51)
+    _, _, _, bases, offsets = _tiled_reads(7400, ks[0])
+    nreads = len(offsets) - 1
+    hmax = int(0.2 * oracle_lib.CMASH_PRIME)
+    want = [oracle_lib.sketch_reads(bases, offsets, k, hmax=hmax) for k in ks]
+    d_b, d_o = hip.array(bases), hip.array(offsets)
+    for grid in (1, 3, 0):
+        knobs("k1_grid", grid)
+        h, c, trunc, seen = hip.sketch_reads(bases, offsets, ks[0], hmax=hmax)
+        assert np.array_equal(h, want[0][0]) and np.array_equal(c, want[0][1]) and seen == want[0][3], ("one k", grid)
+        sks = hip.sketch_reads_multi_dev_async(d_b.ptr, d_o.ptr, nreads, list(ks), [hmax] * len(ks), 0, None)
+        for i, k in enumerate(ks):
+            h, c = sks[i].download()
+            oh, oc, _, oseen = want[i]
+            assert np.array_equal(h, oh) and np.array_equal(c, oc) and sks[i].kmers_seen == oseen, ("fused", k, grid)
+            sks[i].free()
+    d_b.free()
+    d_o.free()

@@ -99,3 +99,125 @@ def refpipe_case(rng, ngenomes=5, glen=(1200, 2000), nreads=60, strains=True):
             reads += [r, r]
     reads += rand(40, 60, 150, p_n=0.01, p_lower=0.1) + [b"", b"ACG"]
     return genomes, reads
+
+
+# ---- reads built tile by tile: the persistent stage-A kernels take 64 reads to a wavefront and loop over tiles, so what one tile
+# leaves behind (staged bases, not-a-base bits, walk mode, run lists, candidate buffer, totals) meets the next tile of a DIFFERENT kind
+TILE = 64
+TILE_KINDS = ("clean", "ragged", "bad", "long", "span", "short", "foreign", "repeat")
+_TILE_WEIGHTS = (0.3, 0.1, 0.12, 0.06, 0.06, 0.1, 0.1, 0.12)
+# what the tests want some wavefront to walk one right after the other: a clean tile behind every kind that leaves state behind
+# (not-a-base bits, a chunked walk, a skipped tile, full run lists, a gate that rejected everything), and every other walk behind a clean one
+TILE_TRANSITIONS = ({(a, "clean") for a in ("bad", "long", "span", "short", "foreign", "repeat", "ragged")}
+                    | {("clean", b) for b in ("bad", "long", "span", "short", "ragged")})
+_IUPAC = np.frombuffer(b"RYKMSWBDHVN", dtype=np.uint8)
+
+
+def tile_genomes(rng, ngenomes=12, length=20000):
+    """Genomes for tile_sample: random bases; genome 0 carries a homopolymer and tandem repeats of short units from 1000 on.
+    -> (bases u8, offsets u64)"""
+    gb, go = random_genomes(rng, ngenomes, length)
+    rep = b"A" * 300 + b"ACGTTGA" * 40 + b"C" * 200 + b"AC" * 150 + b"GATTACAGATTACAT" * 20
+    gb[1000:1000 + len(rep)] = np.frombuffer(rep, dtype=np.uint8)
+    return gb, go
+
+
+def tile_kinds(rng, ntiles):
+    """A kind of TILE_KINDS for every tile, at random, every kind at least twice."""
+    kinds = list(rng.choice(len(TILE_KINDS), size=ntiles, p=np.array(_TILE_WEIGHTS) / sum(_TILE_WEIGHTS)))
+    for i in range(len(TILE_KINDS)):
+        if kinds.count(i) < 2:
+            kinds[int(rng.integers(0, ntiles))] = i
+            kinds[int(rng.integers(0, ntiles))] = i
+    return [TILE_KINDS[i] for i in kinds]
+
+
+def tile_sample(rng, gbases, goffsets, kinds, k, last=TILE, main=0, present=(0, 1, 2, 3, 4, 5)):
+    """64 reads of kinds[t] for tile t (`last` reads in the final one), both strands, 1 % substitutions:
+      clean    equal 150 bp reads, half of them from genome `main` (high coverage), the rest from `present`
+      ragged   k - 1 .. 250 bp
+      bad      150 bp with N runs, lower case and IUPAC letters
+      long     150 bp and one read of 1100-3000 bp, one of exactly 1023 and one of 1024 (the chunked path of k_count_kmers)
+      span     400-1000 bp: no read above 1023, the tile's span above any stage sized by a batch's average
+      short    0 .. k - 1 bp: no window in the tile
+      foreign  150 bp of random bases (no genome's)
+      repeat   homopolymers, tandem repeats of 1-12 bp units, reads of genome 0's repeats
+    -> (bases u8, offsets u64) of len(kinds) tiles"""
+    alpha = np.frombuffer(b"ACGT", dtype=np.uint8)
+    glen = (goffsets[1:] - goffsets[:-1]).astype(np.int64)
+    present = np.asarray(present)
+
+    def from_genome(n):
+        g = int(main) if rng.random() < 0.5 else int(present[rng.integers(0, len(present))])
+        n = min(n, int(glen[g]))
+        a = int(goffsets[g]) + int(rng.integers(0, int(glen[g]) - n + 1))
+        s = gbases[a:a + n].copy()
+        if rng.random() < 0.5:
+            s = _COMP[s[::-1]]
+        m = rng.random(n) < 0.01
+        s[m] = rng.choice(alpha, size=int(m.sum()))
+        return s
+
+    reads = []
+    for t, kind in enumerate(kinds):
+        nr = last if t == len(kinds) - 1 else TILE
+        if kind == "clean":
+            tile = [from_genome(150) for _ in range(nr)]
+        elif kind == "ragged":
+            tile = [from_genome(int(n)) for n in rng.integers(max(k - 1, 0), 251, size=nr)]
+        elif kind == "bad":
+            tile = []
+            for _ in range(nr):
+                s = from_genome(150)
+                if rng.random() < 0.5:
+                    a = int(rng.integers(0, 150))
+                    s[a:a + int(rng.integers(1, 21))] = ord("N")
+                m = rng.random(150) < 0.005
+                s[m] = rng.choice(_IUPAC, size=int(m.sum()))
+                m = rng.random(150) < 0.1
+                s[m] |= 0x20
+                tile.append(s)
+        elif kind == "long":
+            tile = [from_genome(150) for _ in range(nr)]
+            for i, n in zip(rng.permutation(nr)[:3], (int(rng.integers(1100, 3001)), 1023, 1024)):
+                tile[i] = from_genome(n)
+        elif kind == "span":
+            tile = [from_genome(int(n)) for n in rng.integers(400, 1001, size=nr)]
+        elif kind == "short":
+            tile = [from_genome(int(n)) if n else np.zeros(0, np.uint8) for n in rng.integers(0, max(k, 1), size=nr)]
+        elif kind == "foreign":
+            tile = [rng.choice(alpha, size=150).astype(np.uint8) for _ in range(nr)]
+        elif kind == "repeat":
+            tile = []
+            for _ in range(nr):
+                r = rng.random()
+                if r < 0.3:
+                    s = np.full(150, alpha[int(rng.integers(0, 4))], dtype=np.uint8)
+                elif r < 0.6:
+                    unit = rng.choice(alpha, size=int(rng.integers(1, 13))).astype(np.uint8)
+                    s = np.tile(unit, 150 // len(unit) + 1)[:150]
+                else:
+                    a = 1000 + int(rng.integers(0, 1100))
+                    s = gbases[a:a + 150].copy()
+                tile.append(s)
+        else:
+            raise ValueError(kind)
+        reads += tile
+    offsets = np.zeros(len(reads) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(r) for r in reads])
+    return (np.concatenate(reads).astype(np.uint8) if reads else np.zeros(0, np.uint8)), offsets
+
+
+def wave_tiles(ntiles, grid, waves=4):
+    """The tiles every wavefront of a persistent grid of `grid` workgroups of `waves` wavefronts walks, in its order: wavefront w
+    takes tiles w, w + waves * grid, ... (tile % (waves * grid) == w).  -> [[tile, ...] per wavefront]"""
+    n = waves * grid
+    return [list(range(w, ntiles, n)) for w in range(min(n, ntiles))]
+
+
+def tile_transitions(kinds, grid, waves=4):
+    """{(kind, next kind)}: the pairs of tiles some wavefront walks one right after the other at this grid."""
+    out = set()
+    for seq in wave_tiles(len(kinds), grid, waves):
+        out.update((kinds[a], kinds[b]) for a, b in zip(seq, seq[1:]))
+    return out
