@@ -13,10 +13,10 @@ Stage A/B definition (--definition):
                   smaller k's column from their k-prefixes (the streaming query, :73-76)
     sketch_per_k  rounds 1-3: every k has a genome sketch table of its own and the reads are hashed at every k (one fused launch)
 --hash_mode 0 (default): MurmurHash3 of the lexicographically smaller strand, 64 bits; 1: min over the strands mod 9999999999971
-(CMash as recollected).  The definitions NOT selected are measured in the same process over the same passes and reported beside
-the headline (`definitions`).
-File I/O, PCIe, on-device ingest and the host CAMI tail are NOT in the timed region; `with_ingest` reports the kept
-command line end to end (files on disk -> subset DB / CAMI profile) on the SAME workload as a secondary figure.
+(CMash as recollected).  With --full, the definitions NOT selected are measured in the same process over the same passes and
+reported beside the headline (`definitions`).
+File I/O, PCIe, on-device ingest and the host CAMI tail are NOT in the timed region; with --full, `with_ingest` reports the
+kept command line end to end (files on disk -> subset DB / CAMI profile) on the SAME workload as a secondary figure.
 
 Workloads = BASELINE.json configs:
   --config 1   1M reads vs 1k genomes (50 kb), k = 21                                  (the reference-sized case)
@@ -30,12 +30,16 @@ N > 1 is launched by torch.distributed.run, one rank per GPU (metalign_amd/distr
 contiguously, sketch tables AND sample sketches sharded by hash range; per pass one all-gather of a few words, one
 all-to-all round of sketch slices, one all-reduce(sum, int64) of hits / sizes / per-taxon counts).
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel family (k_sketch_reads*) against HBM with the
-algorithmic bytes of SURVEY.md §8(d) — 158 B per read, ONE pass for all k — and, because that kernel is integer-VALU
-bound, also gives `valu_frac` (VALU issue cycles / all SIMD cycles of the launch); `kernels` does the same for stage B
-and stage C.  `cpu_baseline` is the C oracle (oracle/, a scalar port) on this host's cores over a bounded sample; the
-same sample goes through the GPU path once more, untimed, and `check.oracle_equal` says whether every containment
-count and every per-taxon accumulator came out identical.
+Prints ONE JSON line (rank 0).  A plain run does what the headline needs: it sets up, warms up, times --steps passes,
+writes --dump-outputs and prints the line.  --full adds what takes runs of its own (its --no_* options leave parts out):
+`roofline` prices the dominant kernel family (k_sketch_reads*) against HBM with the algorithmic bytes of SURVEY.md §8(d)
+— 158 B per read, ONE pass for all k — and, because that kernel is integer-VALU bound, also gives `valu_frac` (VALU
+issue cycles / all SIMD cycles of the launch); `kernels` does the same for stage B and stage C, all from a per-kernel
+table of extra one-stream steps.  `cpu_baseline` is the C oracle (oracle/, a scalar port) on this host's cores over a
+bounded sample; the same sample goes through the GPU path once more, untimed, and `check.oracle_equal` says whether
+every containment count and every per-taxon accumulator came out identical.  Then `definitions`, `secondary`
+(configs[1]), `with_ingest`, and at N > 1 `same_workload_n1` measured in the same run (a plain run quotes the committed
+figure).
 """
 import argparse
 import json
@@ -65,7 +69,7 @@ PRESETS = {
             name="configs[4]: configs[3] + alignment replay -> full CAMI profile"),
 }
 # the reference's OWN parameters (scripts/select_db.py:44,50,69-70,75: kmc -k60, StreamingQueryDNADatabase 30-60-10, n = 1000) on
-# configs[2]'s sizes: --preset stock makes it the headline; the default line carries it in `definitions`
+# configs[2]'s sizes: --preset stock makes it the headline; a --full line carries it in `definitions`
 STOCK_KS = [30, 40, 50, 60]
 STOCK_NAME = "stock Metalign parameters (k_max = 60, k range 30-60-10, n = 1000) on configs[2]'s sizes"
 
@@ -88,13 +92,16 @@ def parse():
     p.add_argument("--match", choices=["kmer", "hash"], default="kmer",
                    help="the reference pipeline on one GPU: a read k_max-mer meets a sketched one by what it IS (kmc's way, default) or by "
                         "its MurmurHash3 value (rounds 4-5)")
-    p.add_argument("--no_definitions", action="store_true", help="skip the passes of the definitions that were not selected")
-    p.add_argument("--no_cpu_baseline", action="store_true", help="also skips the oracle check (it shares the sample)")
+    p.add_argument("--full", action="store_true",
+                   help="also what the headline does not need: the rooflines and the per-kernel table, the CPU baseline and the oracle check, the "
+                        "other definitions, configs[1], with_ingest, and at N > 1 this workload on one GPU")
+    p.add_argument("--no_definitions", action="store_true", help="--full: skip the passes of the definitions that were not selected")
+    p.add_argument("--no_cpu_baseline", action="store_true", help="--full: skip the CPU baseline and the oracle check (it shares the sample)")
     p.add_argument("--cpu_seconds", type=float, default=15.0, help="target CPU-baseline duration")
-    p.add_argument("--no_kernel_table", action="store_true", help="skip the extra instrumented steps (clean traces)")
-    p.add_argument("--no_secondary", action="store_true", help="skip the configs[1] secondary line and the with-ingest figure")
+    p.add_argument("--no_kernel_table", action="store_true", help="--full: skip the extra instrumented steps (clean traces)")
+    p.add_argument("--no_secondary", action="store_true", help="--full: skip the definitions, the configs[1] secondary line and the with-ingest figure")
     p.add_argument("--no_same_workload_n1", action="store_true",
-                   help="N > 1: do not measure this workload on one GPU first (rank 0 alone, same collectives in the path)")
+                   help="--full, N > 1: do not measure this workload on one GPU first (rank 0 alone, same collectives in the path)")
     p.add_argument("--knob", action="append", default=[], metavar="KEY=VALUE",
                    help="A/B runs: a diagnostic knob of the library (mg_debug_set; include/metalign_hip.h), recorded in config.knobs")
     p.add_argument("--dry_run", action="store_true",
@@ -105,6 +112,8 @@ def parse():
     a = p.parse_args()
     if a.steps < 1:
         p.error("--steps must be at least 1")
+    if not a.full:
+        a.no_definitions = a.no_cpu_baseline = a.no_kernel_table = a.no_secondary = a.no_same_workload_n1 = True
     return a
 
 
@@ -557,7 +566,7 @@ def same_workload_on_one_gpu(args, cfg):
     env = {k: v for k, v in os.environ.items() if k not in _LAUNCH_ENV}
     env.update(MG_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--config", str(cfg["config"]), "--steps", str(args.steps),
-           "--warmup", str(args.warmup), "--sketch_n", str(args.sketch_n), "--no_cpu_baseline", "--no_secondary", "--no_kernel_table"]
+           "--warmup", str(args.warmup), "--sketch_n", str(args.sketch_n)]  # (a plain run: the headline alone)
     for flag, val in (("--reads", args.reads), ("--genomes", args.genomes), ("--genome_len", args.genome_len), ("--ks", args.ks)):
         if val:
             cmd += [flag, str(val)]
@@ -671,7 +680,7 @@ def main():
     hip.prof_reset()
     hip.prof_enable(True)
     k1_name = "count_kmers" if getattr(job, "match", None) == "kmer" else "sketch_reads"
-    hip.prof_only(k1_name)  # the dominant kernel is timed with HIP events inside the timed region
+    hip.prof_only(k1_name)  # the dominant kernel is timed with HIP events inside the timed region (in a plain run too: the timed passes do not depend on --full)
     t0 = time.perf_counter()
     out = job.run(args.steps)  # K passes, software-pipelined (stage A of pass i+1 is queued before pass i is finished)
     sync()
@@ -706,70 +715,78 @@ def main():
         if outputs is not None:
             dump_outputs(outputs, args.dump_outputs)
         ms = 1e3 * dt / args.steps
-        k1_per_pass_ms = k1_ms / max(args.steps, 1)  # all k of one pass (one fused launch, or one launch per k)
-        launches_per_pass = nk1 / max(args.steps, 1)
-        algo_k1 = ALGO_BYTES_PER_READ_K1 * nreads
-        # the kernel's OWN duration: HIP events around it with nothing else on the device (the extra one-stream steps below the
-        # timed region; rocprofv3's average of the same kernel is in profiles/<round>/config2_kernel_stats.csv).  In the timed
-        # region two launches overlap (stage A of pass i + 1 starts while pass i finishes), so a launch there is STRETCHED
-        # (avg_launch_ms_pipelined) although one starts every period_ms: that is why ms_per_step can be below the kernel alone.
-        k1_alone_ms = kernels_ms.get(k1_name, {}).get("ms_per_pass") or k1_per_pass_ms
-        achieved = algo_k1 / (k1_alone_ms * 1e-3) / 1e9 if k1_alone_ms else 0.0
-        traffic = committed_profile("pmc_traffic.json", cfg)
-        sq = committed_profile("pmc_sq_summary.json", cfg)
         by_kmer = k1_name == "count_kmers"
-        sq_a = (sq.get("stage_a", sq.get("k_sketch_reads")) if sq else None)
-        tr_a = (traffic.get("stage_a", traffic.get("k_sketch_reads")) if traffic else None)
-        valu_insts = sq_a.get("SQ_INSTS_VALU_per_pass") if sq_a else None
-        roof = {"kernel": ("k_count_kmers<%d> (stage A by k-mer identity: %.0f launch(es) per pass)" % (cfg["ks"][-1], launches_per_pass)) if by_kmer
-                else "k_sketch_reads* (stage A, all k of the pass: %.0f launch(es) per pass)" % launches_per_pass,
-                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                "traffic": (tr_a.get("hbm_bytes_per_pass", tr_a.get("hbm_bytes_per_launch")) if tr_a else None),
-                "kernel_ms_alone": k1_alone_ms, "period_ms": ms,
-                "avg_launch_ms_pipelined": k1_ms / max(nk1, 1), "overlap_ms": max(0.0, k1_per_pass_ms - ms),
-                "ms_per_pass_pipelined": k1_per_pass_ms,
-                "rocprofv3": committed_kernel_stats(cfg),
-                "algorithmic_bytes_per_pass": algo_k1,
-                "traffic_correction": (traffic or {}).get("correction"),
-                # VALU roofline (the kernel is integer-VALU bound), calibrated: every opcode of the hot loop priced with its
-                # measured issue cost (tools/ubench_valu.hip -> profiles/<round>/valu_classes.json; tools/valu_roofline.py
-                # -> k1_valu_roofline.json: cycles per VALU instruction of this kernel's mix), times the VALU instructions the
-                # launch executed, over the SIMD cycles the launch had — both from the SAME committed PMC pass
-                # (SQ_INSTS_VALU; GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs), the kernel running alone on one stream
-                **valu_roofline(sq, kernels_ms.get(k1_name, {}).get("ms_per_pass")),
-                "ms_per_pass_alone": kernels_ms.get(k1_name, {}).get("ms_per_pass"),
-                "valu_insts_per_pass": valu_insts,
-                "note": (("stage A by k-mer identity (k_count_kmers): one lane per read slides a 15-mer minimizer over its windows — no k-mer is "
-                          "hashed — and leaves one event per run of windows; per run the 19 bases around the minimizer are hashed and ONE bit "
-                          "of a 2^29-bit gate is probed (6.9 runs per 150 bp read: 6.9 x 10^7 random 64-byte sectors per 10M reads), the 4 % "
-                          "that pass read their bucket's 128-byte line. achieved / frac = 158 B/read x reads / kernel_ms_alone against 8 TB/s; "
-                          "traffic (FETCH_SIZE + WRITE_SIZE of the committed PMC passes) is 4.5 x that: the gate's sectors. The walk alone "
-                          "is 1.3 of the kernel's 2.1-2.2 ms (SQ_INSTS_VALU 33 per wave-step, three wavefronts per SIMD at 168 VGPRs); "
-                          "valu_frac = SQ_INSTS_VALU x 4 cycles (every opcode of the walk's step is full rate: valu_model.source says how that was "
-                          "taken) / the SIMD cycles of the launch (GRBM_GUI_ACTIVE / 8 x 1024), from the committed PMC pass: the kernel is an "
-                          "integer-VALU kernel with a latency tail (profiles/r06/kcount_*_final.txt hold its SQ counters). ") if by_kmer else
-                         ("integer-VALU bound (one MurmurHash3 per k-mer per k): valu_frac = SQ_INSTS_VALU x the measured issue "
-                          "cycles per VALU instruction of this kernel's opcode mix / the SIMD cycles of the launch (GRBM_GUI_ACTIVE "
-                          "/ 8 x 1024), all from the committed PMC pass of this workload, is the figure that describes it; achieved "
-                          "/ frac = 158 B/read x reads / kernel_ms_alone (the kernel's own duration, HIP events, nothing else on the "
-                          "device) against 8 TB/s; ")) +
-                        "in the timed region a launch starts every period_ms and overlaps its predecessor by overlap_ms "
-                        "(avg_launch_ms_pipelined is the stretched duration there)"}
-        kern = []
-        if "containment" in kernels_ms:
-            t_b = kernels_ms["containment"]["ms_per_pass"] + kernels_ms.get("contain_index", {}).get("ms_per_pass", 0.0)
-            t_b += kernels_ms.get("refpipe_count", {}).get("ms_per_pass", 0.0)
-            # 8 B per table hash and k; the reference pipeline: the largest k's hashes, and per smaller k one
-            # 8-byte (prefix number, genome) entry per table hash
-            algo = (w["table_hashes"] * (len(cfg["ks"]) if w["definition"] == "reference_pipeline" else 1)) * 8 // max(world, 1)
-            kern.append({"kernel": "k_contain_pairs (+ index, reduce%s), all k" % (", k_refpipe_count" if w["definition"] == "reference_pipeline" else ""),
-                         "algorithmic_bytes_per_pass": algo, "ms_per_pass": t_b,
-                         "achieved_GBs": algo / (t_b * 1e-3) / 1e9, "frac": algo / (t_b * 1e-3) / 1e9 / HBM_PEAK_GBS, "bound": "hbm"})
-        if "profile_pass" in kernels_ms:
-            t_c = kernels_ms["profile_pass"]["ms_per_pass"]
-            algo = ALGO_BYTES_PER_RECORD_K3 * nrecs
-            kern.append({"kernel": "k_profile_pass", "algorithmic_bytes_per_pass": algo, "ms_per_pass": t_c,
-                         "achieved_GBs": algo / (t_c * 1e-3) / 1e9, "frac": algo / (t_c * 1e-3) / 1e9 / HBM_PEAK_GBS, "bound": "hbm"})
+        kernel_figures = {}
+        if args.full:  # the kernel figures: the kernel's time alone is the extra one-stream steps'
+            k1_per_pass_ms = k1_ms / max(args.steps, 1)  # all k of one pass (one fused launch, or one launch per k)
+            launches_per_pass = nk1 / max(args.steps, 1)
+            algo_k1 = ALGO_BYTES_PER_READ_K1 * nreads
+            # the kernel's OWN duration: HIP events around it with nothing else on the device (the extra one-stream steps below the
+            # timed region; rocprofv3's average of the same kernel is in profiles/<round>/config2_kernel_stats.csv).  In the timed
+            # region two launches overlap (stage A of pass i + 1 starts while pass i finishes), so a launch there is STRETCHED
+            # (avg_launch_ms_pipelined) although one starts every period_ms: that is why ms_per_step can be below the kernel alone.
+            k1_alone_ms = kernels_ms.get(k1_name, {}).get("ms_per_pass") or k1_per_pass_ms
+            achieved = algo_k1 / (k1_alone_ms * 1e-3) / 1e9 if k1_alone_ms else 0.0
+            traffic = committed_profile("pmc_traffic.json", cfg)
+            sq = committed_profile("pmc_sq_summary.json", cfg)
+            sq_a = (sq.get("stage_a", sq.get("k_sketch_reads")) if sq else None)
+            tr_a = (traffic.get("stage_a", traffic.get("k_sketch_reads")) if traffic else None)
+            valu_insts = sq_a.get("SQ_INSTS_VALU_per_pass") if sq_a else None
+            roof = {"kernel": ("k_count_kmers<%d> (stage A by k-mer identity: %.0f launch(es) per pass)" % (cfg["ks"][-1], launches_per_pass)) if by_kmer
+                    else "k_sketch_reads* (stage A, all k of the pass: %.0f launch(es) per pass)" % launches_per_pass,
+                    "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                    "traffic": (tr_a.get("hbm_bytes_per_pass", tr_a.get("hbm_bytes_per_launch")) if tr_a else None),
+                    "kernel_ms_alone": k1_alone_ms, "period_ms": ms,
+                    "avg_launch_ms_pipelined": k1_ms / max(nk1, 1), "overlap_ms": max(0.0, k1_per_pass_ms - ms),
+                    "ms_per_pass_pipelined": k1_per_pass_ms,
+                    "rocprofv3": committed_kernel_stats(cfg),
+                    "algorithmic_bytes_per_pass": algo_k1,
+                    "traffic_correction": (traffic or {}).get("correction"),
+                    # VALU roofline (the kernel is integer-VALU bound), calibrated: every opcode of the hot loop priced with its
+                    # measured issue cost (tools/ubench_valu.hip -> profiles/<round>/valu_classes.json; tools/valu_roofline.py
+                    # -> k1_valu_roofline.json: cycles per VALU instruction of this kernel's mix), times the VALU instructions the
+                    # launch executed, over the SIMD cycles the launch had — both from the SAME committed PMC pass
+                    # (SQ_INSTS_VALU; GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs), the kernel running alone on one stream
+                    **valu_roofline(sq, kernels_ms.get(k1_name, {}).get("ms_per_pass")),
+                    "ms_per_pass_alone": kernels_ms.get(k1_name, {}).get("ms_per_pass"),
+                    "valu_insts_per_pass": valu_insts,
+                    "note": (("stage A by k-mer identity (k_count_kmers): one lane per read slides a 15-mer minimizer over its windows — no k-mer is "
+                              "hashed — and leaves one event per run of windows; per run the 19 bases around the minimizer are hashed and ONE bit "
+                              "of a 2^29-bit gate is probed (6.9 runs per 150 bp read: 6.9 x 10^7 random 64-byte sectors per 10M reads), the 4 % "
+                              "that pass read their bucket's 128-byte line. achieved / frac = 158 B/read x reads / kernel_ms_alone against 8 TB/s; "
+                              "traffic (FETCH_SIZE + WRITE_SIZE of the committed PMC passes) is 4.5 x that: the gate's sectors. The walk alone "
+                              "is 1.3 of the kernel's 2.1-2.2 ms (SQ_INSTS_VALU 33 per wave-step, three wavefronts per SIMD at 168 VGPRs); "
+                              "valu_frac = SQ_INSTS_VALU x 4 cycles (every opcode of the walk's step is full rate: valu_model.source says how that was "
+                              "taken) / the SIMD cycles of the launch (GRBM_GUI_ACTIVE / 8 x 1024), from the committed PMC pass: the kernel is an "
+                              "integer-VALU kernel with a latency tail (profiles/r06/kcount_*_final.txt hold its SQ counters). ") if by_kmer else
+                             ("integer-VALU bound (one MurmurHash3 per k-mer per k): valu_frac = SQ_INSTS_VALU x the measured issue "
+                              "cycles per VALU instruction of this kernel's opcode mix / the SIMD cycles of the launch (GRBM_GUI_ACTIVE "
+                              "/ 8 x 1024), all from the committed PMC pass of this workload, is the figure that describes it; achieved "
+                              "/ frac = 158 B/read x reads / kernel_ms_alone (the kernel's own duration, HIP events, nothing else on the "
+                              "device) against 8 TB/s; ")) +
+                            "in the timed region a launch starts every period_ms and overlaps its predecessor by overlap_ms "
+                            "(avg_launch_ms_pipelined is the stretched duration there)"}
+            kern = []
+            if "containment" in kernels_ms:
+                t_b = kernels_ms["containment"]["ms_per_pass"] + kernels_ms.get("contain_index", {}).get("ms_per_pass", 0.0)
+                t_b += kernels_ms.get("refpipe_count", {}).get("ms_per_pass", 0.0)
+                # 8 B per table hash and k; the reference pipeline: the largest k's hashes, and per smaller k one
+                # 8-byte (prefix number, genome) entry per table hash
+                algo = (w["table_hashes"] * (len(cfg["ks"]) if w["definition"] == "reference_pipeline" else 1)) * 8 // max(world, 1)
+                kern.append({"kernel": "k_contain_pairs (+ index, reduce%s), all k" % (", k_refpipe_count" if w["definition"] == "reference_pipeline" else ""),
+                             "algorithmic_bytes_per_pass": algo, "ms_per_pass": t_b,
+                             "achieved_GBs": algo / (t_b * 1e-3) / 1e9, "frac": algo / (t_b * 1e-3) / 1e9 / HBM_PEAK_GBS, "bound": "hbm"})
+            if "profile_pass" in kernels_ms:
+                t_c = kernels_ms["profile_pass"]["ms_per_pass"]
+                algo = ALGO_BYTES_PER_RECORD_K3 * nrecs
+                kern.append({"kernel": "k_profile_pass", "algorithmic_bytes_per_pass": algo, "ms_per_pass": t_c,
+                             "achieved_GBs": algo / (t_c * 1e-3) / 1e9, "frac": algo / (t_c * 1e-3) / 1e9 / HBM_PEAK_GBS, "bound": "hbm"})
+            kernel_figures = {
+                "roofline": roof,
+                "kernels": kern,
+                "kernel_ms_per_pass": kernels_ms,
+                "kernel_note": "HIP-event time per kernel family from extra untimed steps with everything on ONE stream (nothing "
+                               "overlaps); the timed passes themselves are pipelined over three streams"}
         res = {
             "metric": "150bp reads/s end-to-end (CMash filter + profile)",
             "value": nreads * world / (dt / args.steps),
@@ -794,11 +811,7 @@ def main():
                                        "all-gathered (two bits a pair) and summed, the count lists streamed in shares" % world)
                        if getattr(job, "match", None) == "kmer" else
                        ("reads + alignment records sharded x%d, read sketches and sketch tables sharded by hash range" % world)},
-            "roofline": roof,
-            "kernels": kern,
-            "kernel_ms_per_pass": kernels_ms,
-            "kernel_note": "HIP-event time per kernel family from extra untimed steps with everything on ONE stream (nothing "
-                           "overlaps); the timed passes themselves are pipelined over three streams",
+            **kernel_figures,
             "sanity": {"top_genomes_recovered": out.get("top_ok"), "tot_rds": out.get("tot_rds"),
                        "sketch_sizes": out.get("sketch_sizes")},
         }

@@ -44,6 +44,18 @@ def test_a_failing_rank_fails_the_command():
     assert not [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
 
 
+def test_a_plain_run_leaves_the_extras_to_full(monkeypatch):
+    """Without --full every part beyond the headline is off; --full turns them on, and a --no_* option still drops its part."""
+    import bench
+    extras = ("no_definitions", "no_cpu_baseline", "no_kernel_table", "no_secondary", "no_same_workload_n1")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and all(getattr(a, x) for x in extras)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--full", "--no_secondary"])
+    a = bench.parse()
+    assert a.full and a.no_secondary and not any(getattr(a, x) for x in extras if x != "no_secondary")
+
+
 def test_dump_outputs_are_float64_copies_and_a_seeded_sample_over_the_cap(tmp_path, monkeypatch):
     """--dump-outputs: every array a step returns as float64, exact; over the byte cap the same positions every time."""
     import numpy as np

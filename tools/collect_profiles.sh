@@ -10,8 +10,8 @@ OUT=gpurun_out/prof_$TAG
 export TMPDIR=/tmp
 mkdir -p "$OUT"
 ARGS="--steps 5 --warmup 2 --no_cpu_baseline --no_secondary --no_kernel_table $*"
-timeout -s KILL 600 python3 bench.py --no_secondary "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
-MG_SINGLE_STREAM=1 timeout -s KILL 600 python3 bench.py --no_cpu_baseline --no_secondary "$@" > "$OUT/bench_single_stream.json" 2>> "$OUT/bench.err"
+timeout -s KILL 600 python3 bench.py --full --no_secondary "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+MG_SINGLE_STREAM=1 timeout -s KILL 600 python3 bench.py --full --no_cpu_baseline --no_secondary "$@" > "$OUT/bench_single_stream.json" 2>> "$OUT/bench.err"
 # the DEFAULT schedule (stage A of consecutive passes on two alternating streams, stage C on a third): the trace that
 # evidences the driver-timed step; kernels of different passes overlap here, so averages are NOT a kernel's own time
 timeout -s KILL 900 rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/stats_pipelined" -o run -- python3 bench.py --steps 20 --warmup 3 --no_cpu_baseline --no_secondary --no_kernel_table "$@" > "$OUT/bench_pipelined_under_rocprof.json" 2> "$OUT/stats_pipelined.log"

@@ -6,7 +6,7 @@ OUT=gpurun_out/k1_dense_ablation.txt; : > $OUT
 p=29720
 for knob in "" "--knob resident_ablate=3" "--knob resident_ablate=2" "--knob resident_ablate=1"; do
   p=$((p+1)); export MASTER_PORT=$p
-  timeout 900 python3 bench.py --gpus 1 --config 3 --steps 6 --warmup 2 --no_cpu_baseline --no_secondary --no_definitions $knob > gpurun_out/abl.json 2> gpurun_out/abl.err
+  timeout 900 python3 bench.py --gpus 1 --config 3 --steps 6 --warmup 2 --full --no_cpu_baseline --no_secondary --no_definitions $knob > "${OUT%/*}/abl.json" 2> "${OUT%/*}/abl.err"
   python3 - "$knob" >> $OUT <<'PY'
 import json, sys
 d = json.loads(open("gpurun_out/abl.json").read().strip().splitlines()[-1])
