@@ -753,6 +753,22 @@ int mg_paf_tokenize(const uint8_t* text, uint64_t nbytes, const mg_acc_index* ix
  * scripts/map_and_profile.py:201-217.  err_line is relative to the piece the line fell into. */
 int mg_sam_stream_file(const char* path, int paf, const mg_acc_index* ix, uint64_t offset, uint64_t length,
                        uint64_t chunk_bytes, int nthreads, mg_sam_batch** out, int* err_kind, uint64_t* err_line);
+/* A BAM FILE (BGZF, or uncompressed) -> the records its SAM rendering (`samtools view -h`) gives through mg_sam_tokenize_dev,
+ * through the same pipeline and inflaters as a `.sam.gz`: the header (magic, text, references) is read on the host with zlib
+ * and each header name mapped through ix; every piece of the record stream is cut after its last complete record (BAM records
+ * are a chain of length-prefixed blocks: found in parallel by speculative entry and stitching, metalign_amd/csrc/mg_bam.hip).
+ * err_kind: 1..5 as above (a record's SAM rendering raises that); 6: the device does not decide the record's rendering (a QNAME
+ * or reference name that is not one SAM field, a QUAL byte above '~', a float first tag) — the caller takes the host definition;
+ * 7: not a BAM record (a corrupt block_size, a truncated file, a CIGAR op above 8) or a CIGAR kept in a CG tag (not supported).
+ * err_rec: the record's number within its piece (kind 7 of the chain itself: the byte offset in the piece). */
+int mg_bam_stream_file(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,
+                       int* err_kind, uint64_t* err_rec);
+/* The same for BAM record bytes already in HBM (what follows the header; d_bytes starts at a record).  refmap[i] = the row in
+ * ix of reference i's name (-1: no accession of that name; -2: a name that is not one SAM field), nref of them; refID -1 ('*')
+ * is looked up in ix.  final = 0: a PIECE — the complete records are decoded and *consumed = the end of the last of them (the
+ * caller carries the rest); final = 1: the bytes must end on a record's end. */
+int mg_bam_tokenize_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* refmap, uint32_t nref, const mg_acc_index* ix,
+                        const char* prev_qname, int final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec);
 uint64_t mg_sam_batch_count(const mg_sam_batch* b);
 const char* mg_sam_batch_last_qname(const mg_sam_batch* b);
 int mg_sam_batch_device_ptr(const mg_sam_batch* b, const mg_aln_rec** d_recs);

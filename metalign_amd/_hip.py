@@ -37,7 +37,7 @@ EXPORTS = [
     "mg_sketch_stream_begin", "mg_sketch_stream_begin_counts", "mg_sketch_stream_add_dev", "mg_sketch_stream_add_file", "mg_sketch_stream_finish", "mg_sketch_stream_nreads", "mg_sketch_stream_nbases", "mg_sketch_stream_free",
     "mg_reads_parse_dev", "mg_reads_parse_prefix_dev", "mg_reads_parse", "mg_reads_count", "mg_reads_nbases", "mg_reads_device_ptrs",
     "mg_reads_download", "mg_reads_free",
-    "mg_acc_index_build", "mg_acc_index_free", "mg_sam_tokenize_dev", "mg_sam_tokenize", "mg_paf_tokenize_dev", "mg_paf_tokenize", "mg_sam_stream_file", "mg_sam_batch_count",
+    "mg_acc_index_build", "mg_acc_index_free", "mg_sam_tokenize_dev", "mg_sam_tokenize", "mg_paf_tokenize_dev", "mg_paf_tokenize", "mg_sam_stream_file", "mg_bam_stream_file", "mg_bam_tokenize_dev", "mg_sam_batch_count",
     "mg_sam_batch_last_qname", "mg_sam_batch_device_ptr", "mg_sam_batch_download", "mg_sam_batch_free",
     "mg_gunzip_open", "mg_gunzip_read", "mg_gunzip_close", "mg_zcat_files", "mg_stream_thin_file",
     "mg_inflate_dev", "mg_inflated_bytes", "mg_inflated_download", "mg_inflated_free", "mg_inflate_config", "mg_inflate_stats",
@@ -1296,6 +1296,34 @@ class Hip:
             raise SamParseError(kind.value, line.value)
         self._chk(rc)
         return SamBatch(self, h)
+
+    def bam_stream_file(self, path, acc_index, chunk_bytes=0, nthreads=0):
+        """A BAM file -> SamBatch: the records its SAM rendering gives through sam_stream_file (mg_bam_stream_file).  SamParseError
+        for a record whose rendering the reference cannot parse, that the device does not decide (kind 6) or that is not a BAM
+        record the package takes (kind 7); `line` is the record's number within its piece."""
+        h = _vp()
+        kind, rec = ctypes.c_int(0), ctypes.c_uint64(0)
+        rc = self.lib.mg_bam_stream_file(os.fsencode(path), acc_index.handle, ctypes.c_uint64(int(chunk_bytes)), ctypes.c_int(int(nthreads)),
+                                         ctypes.byref(h), ctypes.byref(kind), ctypes.byref(rec))
+        if rc != 0 and kind.value:
+            raise SamParseError(kind.value, rec.value)
+        self._chk(rc)
+        return SamBatch(self, h)
+
+    def bam_tokenize_dev(self, d_bytes, nbytes, refmap, acc_index, prev_qname="", final=True):
+        """BAM record bytes resident in HBM (behind the header) -> (SamBatch, consumed) (mg_bam_tokenize_dev); refmap: the accession row
+        of every header reference (-1: none, -2: not one SAM field).  SamParseError as bam_stream_file."""
+        rm = np.ascontiguousarray(refmap, dtype=np.int32)
+        h = _vp()
+        kind, rec, used = ctypes.c_int(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = self.lib.mg_bam_tokenize_dev(_vp(d_bytes), ctypes.c_uint64(nbytes), _np(rm if rm.size else np.zeros(1, np.int32), ctypes.c_int32),
+                                          ctypes.c_uint32(rm.size), acc_index.handle, ctypes.c_char_p(prev_qname.encode()),
+                                          ctypes.c_int(1 if final else 0), ctypes.byref(used), ctypes.byref(h), ctypes.byref(kind),
+                                          ctypes.byref(rec))
+        if rc != 0 and kind.value:
+            raise SamParseError(kind.value, rec.value)
+        self._chk(rc)
+        return SamBatch(self, h), int(used.value)
 
     def acc_index(self, names):
         blob = "".join(names).encode()

@@ -278,14 +278,6 @@ __device__ __forceinline__ int64_t acc_lookup(const AccTable& t, const uint8_t* 
   }
 }
 
-constexpr uint32_t kQnameInline = 256;  // (SAM: QNAME is at most 254 characters)
-struct LineOut {
-  mg_aln_rec rec;      // ref_new without the new-read bit
-  uint64_t qbeg;       // QNAME span in the text
-  uint32_t qlen;
-  uint32_t retained;
-};
-
 // One thread per line: everything except the new-read bit.  err: [0] = first failing line (atomicMin),
 // kinds[line] holds the failure kind for the host to look up.
 __global__ void k_sam_parse(const uint8_t* __restrict__ text, const uint64_t* __restrict__ line_end, uint64_t nlines,
@@ -787,6 +779,7 @@ int mg_acc_index_build(const char* names, const uint64_t* name_offsets, uint32_t
     sh[p] = h;
     sr[p] = i;
     (void)dup;
+    ix->host_rows[std::string(names + b, e - b)] = i;
   }
   const uint64_t nb = nacc ? name_offsets[nacc] : 0;
   MG_TRY(ix->slot_hash.alloc(slots * sizeof(uint64_t)));
@@ -886,38 +879,48 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
       if (err_line) *err_line = h_err;
       return fail(MG_ERR_ARG, "%s line %llu: parse error kind %u", paf ? "PAF" : "SAM", h_err, kind);
     }
-    MG_TRY(sb->recs.alloc((nret + 1) * sizeof(mg_aln_rec)));
-    if (nret) {
-      uint64_t* d_list = (uint64_t*)scratch("sam_list", nret * sizeof(uint64_t));
-      if (!d_list) return MG_ERR_NOMEM;
-      hipLaunchKernelGGL(k_sam_list, dim3(grid_for(nlines, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_ret, d_rank,
-                         nlines, d_list);
-      hipLaunchKernelGGL(k_sam_emit, dim3(grid_for(nret, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_text, d_lines,
-                         d_list, nret, d_prev, (uint32_t)plen, sb->recs.as<mg_aln_rec>());
-      MG_HIP(hipGetLastError());
-      // QNAME of the last retained line, for the next chunk: its span and its first kQnameInline bytes in ONE round trip
-      // (three dependent ones — line number, span, bytes — were a quarter of a streamed piece's host time)
-      uint8_t* d_q = (uint8_t*)scratch("sam_lastq", 16 + kQnameInline);
-      if (!d_q) return MG_ERR_NOMEM;
-      hipLaunchKernelGGL(k_sam_last_qname, dim3(1), dim3(64), 0, st, d_text, d_lines, d_list, nret, d_q);
-      MG_HIP(hipGetLastError());
-      std::vector<uint8_t> hq(16 + kQnameInline);
-      MG_HIP(hipMemcpyAsync(hq.data(), d_q, hq.size(), hipMemcpyDeviceToHost, st));
-      MG_HIP(hipStreamSynchronize(st));
-      uint64_t qbeg;
-      uint32_t qlen;
-      memcpy(&qbeg, hq.data(), 8);
-      memcpy(&qlen, hq.data() + 8, 4);
-      sb->last_qname.assign(reinterpret_cast<const char*>(hq.data() + 16), qlen < kQnameInline ? qlen : kQnameInline);
-      if (qlen > kQnameInline) {  // (a QNAME longer than the SAM format allows: the rest in a second trip)
-        sb->last_qname.resize(qlen);
-        MG_HIP(hipMemcpyAsync(&sb->last_qname[0], d_text + qbeg, qlen, hipMemcpyDeviceToHost, st));
-        MG_HIP(hipStreamSynchronize(st));
-      }
-    }
+    MG_TRY(aln_emit_retained(d_text, d_lines, d_ret, d_rank, nlines, nret, d_prev, (uint32_t)plen, sb.get()));
   }
   sb->nrecs = nret;
   *out = sb.release();
+  return MG_OK;
+}
+
+// The retained lines (d_ret[l] = 1, d_rank = its exclusive prefix, nret of them) -> sb->recs with the new-read bit, and
+// sb->last_qname.  The SAM / PAF tokeniser above and the BAM decoder (mg_bam.hip) end here.
+int mg::aln_emit_retained(const uint8_t* d_text, const LineOut* d_lines, const uint32_t* d_ret, const uint64_t* d_rank, uint64_t nlines,
+                          uint64_t nret, const uint8_t* d_prev, uint32_t plen, mg_sam_batch* sb) {
+  Context& c = ctx();
+  hipStream_t st = c.stream;
+  MG_TRY(sb->recs.alloc((nret + 1) * sizeof(mg_aln_rec)));
+  if (nret) {
+    uint64_t* d_list = (uint64_t*)scratch("sam_list", nret * sizeof(uint64_t));
+    if (!d_list) return MG_ERR_NOMEM;
+    hipLaunchKernelGGL(k_sam_list, dim3(grid_for(nlines, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_ret, d_rank,
+                       nlines, d_list);
+    hipLaunchKernelGGL(k_sam_emit, dim3(grid_for(nret, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_text, d_lines,
+                       d_list, nret, d_prev, plen, sb->recs.as<mg_aln_rec>());
+    MG_HIP(hipGetLastError());
+    // QNAME of the last retained line, for the next chunk: its span and its first kQnameInline bytes in ONE round trip
+    // (three dependent ones — line number, span, bytes — were a quarter of a streamed piece's host time)
+    uint8_t* d_q = (uint8_t*)scratch("sam_lastq", 16 + kQnameInline);
+    if (!d_q) return MG_ERR_NOMEM;
+    hipLaunchKernelGGL(k_sam_last_qname, dim3(1), dim3(64), 0, st, d_text, d_lines, d_list, nret, d_q);
+    MG_HIP(hipGetLastError());
+    std::vector<uint8_t> hq(16 + kQnameInline);
+    MG_HIP(hipMemcpyAsync(hq.data(), d_q, hq.size(), hipMemcpyDeviceToHost, st));
+    MG_HIP(hipStreamSynchronize(st));
+    uint64_t qbeg;
+    uint32_t qlen;
+    memcpy(&qbeg, hq.data(), 8);
+    memcpy(&qlen, hq.data() + 8, 4);
+    sb->last_qname.assign(reinterpret_cast<const char*>(hq.data() + 16), qlen < kQnameInline ? qlen : kQnameInline);
+    if (qlen > kQnameInline) {  // (a QNAME longer than the SAM format allows: the rest in a second trip)
+      sb->last_qname.resize(qlen);
+      MG_HIP(hipMemcpyAsync(&sb->last_qname[0], d_text + qbeg, qlen, hipMemcpyDeviceToHost, st));
+      MG_HIP(hipStreamSynchronize(st));
+    }
+  }
   return MG_OK;
 }
 

@@ -301,6 +301,7 @@ struct mg_reads {
 
 struct mg_acc_index {
   mg::DevBuf slot_hash, slot_row, names, name_off;
+  std::map<std::string, uint32_t> host_rows;  // (the same names on the host: a BAM header's references are looked up there)
   uint64_t slots = 0;
   uint32_t nacc = 0;
 };
@@ -314,6 +315,27 @@ struct mg_sam_batch {
 };
 
 namespace mg {
+constexpr uint32_t kQnameInline = 256;  // (SAM: QNAME is at most 254 characters)
+// One line of alignment text (or one BAM record, mg_bam.hip) as the tokeniser leaves it
+struct LineOut {
+  mg_aln_rec rec;      // ref_new without the new-read bit
+  uint64_t qbeg;       // QNAME span in the text
+  uint32_t qlen;
+  uint32_t retained;
+};
+int aln_emit_retained(const uint8_t* d_text, const LineOut* d_lines, const uint32_t* d_ret, const uint64_t* d_rank, uint64_t nlines,
+                      uint64_t nret, const uint8_t* d_prev, uint32_t plen, mg_sam_batch* sb);
+// BAM (mg_bam.hip): the header as zlib reads it from the file; a piece of the records behind it -> the batch, as
+// aln_tokenize_prefix_dev for text (d_refmap: int32[1 + n_ref], bam_refmap's); *consumed = the end of its last complete record.
+struct BamHeader {
+  std::string text;                 // the SAM header text
+  std::vector<std::string> names;   // the references, refID order
+  uint64_t bytes = 0;               // of the inflated stream, in front of the first record
+};
+int bam_read_header(const char* path, BamHeader* h);
+std::vector<int32_t> bam_refmap(const std::vector<std::string>& names, const mg_acc_index* ix);
+int bam_tokenize_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* d_refmap, int32_t n_ref, const char* prev_qname,
+                            bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec);
 // thin: the piece comes from the file reader's thinning (mg_stream.hip: a SEQ field is MG_THIN_MARK + its length in decimal).
 int aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg_acc_index* ix, const char* prev_qname, bool paf,
                             bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_line, bool thin = false);

@@ -887,6 +887,28 @@ int mg_sketch_stream_add_file(mg_sketch_stream* ss, const char* path, int format
   return run_pipeline(*src, chunk_bytes, nthreads, consume, nullptr);
 }
 
+// The batches of a file's pieces -> one (a single piece's records are taken over as they are)
+static int concat_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uint64_t total, const std::string& prev, mg_sam_batch** out) {
+  std::unique_ptr<mg_sam_batch> all(new mg_sam_batch());
+  all->last_qname = prev;
+  all->nrecs = total;
+  if (parts.size() == 1) {
+    all->recs = std::move(parts[0]->recs);
+  } else {
+    MG_TRY(all->recs.alloc((total + 1) * sizeof(mg_aln_rec)));
+    uint64_t at = 0;
+    hipStream_t st = ctx().stream;
+    for (auto& p : parts) {
+      if (p->nrecs)
+        MG_HIP(hipMemcpyAsync(all->recs.as<mg_aln_rec>() + at, p->recs.p, p->nrecs * sizeof(mg_aln_rec), hipMemcpyDeviceToDevice, st));
+      at += p->nrecs;
+    }
+    MG_HIP(hipStreamSynchronize(st));
+  }
+  *out = all.release();
+  return MG_OK;
+}
+
 // SAM (paf = 0) or PAF text file -> alignment records on the device, through the same pipeline: every piece is cut at its
 // last newline, tokenised (mg_sam_tokenize_dev's rules; the previous retained QNAME carried from piece to piece so that
 // the new-read bit is the whole file's) and its records appended.  Replaces the per-line Python of map_and_process,
@@ -930,24 +952,63 @@ int mg_sam_stream_file(const char* path, int paf, const mg_acc_index* ix, uint64
   } else {
     MG_TRY(run_pipeline(*src, chunk_bytes, nthreads, consume, nullptr));
   }
-  std::unique_ptr<mg_sam_batch> all(new mg_sam_batch());
-  all->last_qname = prev;
-  all->nrecs = total;
-  if (parts.size() == 1) {
-    all->recs = std::move(parts[0]->recs);
-  } else {
-    MG_TRY(all->recs.alloc((total + 1) * sizeof(mg_aln_rec)));
-    uint64_t at = 0;
-    hipStream_t st = ctx().stream;
-    for (auto& p : parts) {
-      if (p->nrecs)
-        MG_HIP(hipMemcpyAsync(all->recs.as<mg_aln_rec>() + at, p->recs.p, p->nrecs * sizeof(mg_aln_rec), hipMemcpyDeviceToDevice, st));
-      at += p->nrecs;
-    }
-    MG_HIP(hipStreamSynchronize(st));
+  return concat_batches(parts, total, prev, out);
+}
+
+// BAM file (BGZF, or uncompressed) -> alignment records on the device: the SAME pipeline and the same inflaters as a `.sam.gz`
+// (the device's, or the host readers' when mg_inflate_config turned it off or the file does not fit), the header read here
+// with zlib and stepped over in the first piece(s), every piece cut after its last complete record (mg_bam.hip).
+int mg_bam_stream_file(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,
+                       int* err_kind, uint64_t* err_rec) {
+  MG_REQUIRE_READY();
+  if (!path || !ix || !out) return fail(MG_ERR_ARG, "null argument");
+  *out = nullptr;
+  if (err_kind) *err_kind = 0;
+  if (err_rec) *err_rec = 0;
+  BamHeader hdr;
+  MG_TRY(bam_read_header(path, &hdr));
+  const std::vector<int32_t> map = bam_refmap(hdr.names, ix);
+  DevBuf d_map;
+  MG_TRY(d_map.alloc(map.size() * sizeof(int32_t)));
+  MG_TRY(mg_memcpy_h2d(d_map.p, map.data(), map.size() * sizeof(int32_t)));
+  std::unique_ptr<Source> src;
+  bool gz = false;
+  uint64_t gsize = 0;
+  int gfd = open_for_device_inflate(path, 0, 0, &gsize);
+  if (gfd >= 0) {  // (room for the compressed file on the device? as mg_sam_stream_file)
+    DevBuf probe;
+    if (probe.alloc(((gsize + 3) & ~3ull) + 64) != MG_OK) { close(gfd); gfd = -1; }
   }
-  *out = all.release();
-  return MG_OK;
+  if (gfd < 0) MG_TRY(open_source(path, 0, 0, &chunk_bytes, &src, &gz));
+  if (nthreads <= 0) nthreads = default_threads();
+  std::vector<std::unique_ptr<mg_sam_batch>> parts;
+  std::string prev;
+  uint64_t total = 0, skip = hdr.bytes;
+  Consumer consume = [&](const uint8_t* d_text, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
+    const uint64_t off = skip < nbytes ? skip : nbytes;  // the header's bytes
+    skip -= off;
+    if (skip) {
+      *consumed = nbytes;
+      return final ? fail(MG_ERR_ARG, "%s: the BAM header runs past the end of the file", path) : MG_OK;
+    }
+    mg_sam_batch* b = nullptr;
+    uint64_t used = 0;
+    MG_TRY(bam_tokenize_prefix_dev(d_text + off, nbytes - off, d_map.as<int32_t>(), (int32_t)hdr.names.size(), prev.c_str(), final,
+                                   &used, &b, err_kind, err_rec));
+    *consumed = off + used;
+    prev = b->last_qname;
+    total += b->nrecs;
+    parts.emplace_back(b);
+    return MG_OK;
+  };
+  if (gfd >= 0) {
+    const int rc = inflate_file_pipeline(gfd, gsize, consume, nullptr);
+    close(gfd);
+    MG_TRY(rc);
+  } else {
+    MG_TRY(run_pipeline(*src, chunk_bytes, nthreads, consume, nullptr));
+  }
+  return concat_batches(parts, total, prev, out);
 }
 
 // What the file readers hand to the device for a plain FASTQ (kind 0) or SAM (kind 1) file, written to out_path instead: the

@@ -21,6 +21,7 @@ CAMI file is byte-identical.
 There is no CPU fallback: without libmetalign_hip.so / a GPU, map_and_process
 raises (metalign_amd._hip.HipUnavailable).
 """
+import ctypes
 import os
 import subprocess
 import sys
@@ -28,7 +29,7 @@ import time
 
 import numpy as np
 
-from . import _hip, cli
+from . import _hip, bam, cli
 
 start = time.time()
 RANKS = ['superkingdom', 'phylum', 'class', 'order', 'family', 'genus', 'species', 'strain']
@@ -300,6 +301,35 @@ def tokenise_paf_device(instream, acc_index, decode=False):
 _device_tokenise_paf = tokenise_paf_device
 
 
+def tokenise_bam_device(path, acc_index, chunk_bytes=0):
+    """BAM file -> records on the MI355X (mg_bam_stream_file).  A record the device does not decide, or a file it refuses: the
+    file's SAM rendering (bam.sam_lines) through tokenise_sam_device, which raises what the reference raises on that line."""
+    hip = _hip.Hip.get()
+    names = [None] * len(acc_index)
+    for a, i in acc_index.items():
+        names[i] = a
+    index = hip.acc_index(names)
+    batch = None
+    try:
+        try:
+            batch = hip.bam_stream_file(path, index, chunk_bytes=chunk_bytes)
+        except _hip.SamParseError:
+            pass
+        except _hip.HipError as e:
+            if e.code != _hip.ERR_ARG:
+                raise
+        if batch is not None:
+            recs = np.zeros(batch.count, dtype=_hip.REC_DTYPE)
+            if batch.count:
+                hip._chk(hip.lib.mg_sam_batch_download(batch.handle, ctypes.c_void_p(recs.ctypes.data)))
+            return recs
+    finally:
+        index.free()
+        if batch is not None:
+            batch.free()
+    return tokenise_sam_device(bam.sam_lines(path), acc_index)
+
+
 def dense_tables(acc2info, taxid2info):
     """Dense ids for the device: accession row -> taxon row."""
     taxids = list(taxid2info)
@@ -362,11 +392,12 @@ def assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=True):
     return taxids2abs, multimapped, {}
 
 
-def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _resident=False, _paf=False):
+def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _resident=False, _paf=False, _bam=False):
     """map_and_process for a plain SAM FILE, without the text or the records ever being host arrays: the file goes up
     through page-locked chunks (Hip.upload_file), is tokenised where it lands and stage C runs on the records the
     tokeniser left in HBM.  A line the reference cannot parse makes this return None: the caller then takes the
-    streaming path, which reproduces the reference's exception for that line."""
+    streaming path, which reproduces the reference's exception for that line.  _bam: a BAM file (mg_bam_stream_file), None
+    likewise for a record the device does not decide — the caller then streams the file's SAM rendering (bam.sam_lines)."""
     acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
     _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
     hip = _hip.Hip.get()
@@ -384,7 +415,9 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
         if (os.path.getsize(path) // 8 if streamed else 2 * os.path.getsize(path)) > free + pooled:
             return None
         try:
-            if not streamed:  # the whole text up, then one tokeniser call (round 2's path)
+            if _bam:  # (a BAM is always streamed: ~16 B of records per ~60 B of the compressed file stay resident)
+                batch = hip.bam_stream_file(path, index, chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)))
+            elif not streamed:  # the whole text up, then one tokeniser call (round 2's path)
                 d_text, size = hip.upload_file(path)
                 batch = hip.sam_tokenize_dev_batch(d_text.ptr, size, index, '', paf=_paf)
             else:
@@ -795,6 +828,9 @@ def compute_abundances(args, infile, acc2info, tax2info):
     seams_untouched = (_device_tokenise is tokenise_sam_device and _device_tokenise_paf is tokenise_paf_device
                        and _device_assign is _DEVICE_ASSIGN)  # (tests reroute them)
     paf = bool(getattr(args, 'paf_input', False))
+    if args.input_type == 'sam' and not paf and bam.is_bam(infile):  # decided per file: a BAM is never SAM text
+        instream.close()
+        return _compute_abundances_bam(args, infile, acc2info, tax2info, on_device, seams_untouched)
     if args.input_type == 'sam' and seams_untouched and not paf:
         from .select_db import dist_context
         ctx = dist_context()
@@ -815,6 +851,26 @@ def compute_abundances(args, infile, acc2info, tax2info):
     else:
         mapper.stdout.close()
         mapper.wait()
+    return _abundances_tail(args, taxids2abs, mm, tax2info, on_device)
+
+
+def _compute_abundances_bam(args, infile, acc2info, tax2info, on_device, seams_untouched):
+    """A BAM file -> clade abundances: its records decoded on the device (map_and_process_file), or — for a record the device does
+    not decide, or a file it refuses — its SAM rendering through the SAM path, which raises what the reference raises on that line.
+    A multi-GPU launch leaves a BAM to rank 0 (sharing one between the ranks is not done)."""
+    if int(os.environ.get('RANK', '0')) != 0:
+        return None
+    bam.warn_about(infile)
+    done = None
+    if seams_untouched:
+        done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _bam=True)
+    if done is None:
+        done = map_and_process(args, bam.sam_lines(infile), acc2info, tax2info, _want_lists=False, _resident=on_device)
+    taxids2abs, mm, _ = done
+    return _abundances_tail(args, taxids2abs, mm, tax2info, on_device)
+
+
+def _abundances_tail(args, taxids2abs, mm, tax2info, on_device):
     taxids2abs = {k: v for k, v in taxids2abs.items() if v[0] > args.read_cutoff}
     if on_device:
         try:
@@ -878,7 +934,7 @@ def map_main(args=None):
         args = profile_parseargs()
     if args.pct_id > 1.0 or args.pct_id < 0.0:
         sys.exit('Error: --pct_id must be between 0.0 and 1.0, inclusive.')
-    if args.db == 'NONE' and not args.infiles[0].endswith(('sam', 'paf')):
+    if args.db == 'NONE' and not args.infiles[0].endswith(('sam', 'paf', 'bam')):
         sys.exit('Error: --db must be specified unless sam files are provided.')
     args.data = cli.with_slash(args.data)
     if args.dbinfo == 'AUTO':
@@ -889,6 +945,8 @@ def map_main(args=None):
             args.input_type = 'sam'
         elif first.endswith('.paf'):  # build-only: a minimap2 PAF file is replayed like a SAM file
             args.input_type, args.paf_input = 'sam', True
+        elif first.endswith('.bam'):  # BAM alignments: decoded on the device, each file recognised by its content
+            args.input_type, args.bam_input = 'sam', True
         else:
             args.input_type = cli.sniff_reads_type(first)
     if int(os.environ.get('RANK', '0')) != 0 and (args.input_type != 'sam' or getattr(args, 'paf_input', False)):
