@@ -236,7 +236,8 @@ int mg_sketch_reads_multi_dev_async(const uint8_t* d_bases, const uint64_t* d_of
  *            fill page-locked chunks (plain files: positional reads in parallel; gzip: zlib inflate, BGZF blocks in
  *            parallel), one DMA stream uploads chunk i + 1 while chunk i is parsed on the device (mg_reads_parse
  *            rules; record-aligned: the incomplete last record of a chunk is carried to the front of the next ON THE
- *            DEVICE) and hashed into the tables.  format as mg_reads_parse; offset / length: a byte range of the
+ *            DEVICE) and hashed into the tables.  format as mg_reads_parse, or 3: a BAM reads file (see
+ *            mg_reads_parse_bam_prefix_dev); offset / length: a byte range of the
  *            file that begins on a record boundary (a rank's share; length 0 = to the end).  chunk_bytes / nthreads:
  *            0 = defaults (32 MB, up to 8 readers). */
 typedef struct mg_sketch_stream mg_sketch_stream;
@@ -363,6 +364,18 @@ int mg_reads_parse_dev(const uint8_t* d_text, uint64_t nbytes, int format, mg_re
  * the next piece (mg_sketch_stream_add_file does, on the device).  final != 0: mg_reads_parse_dev. */
 int mg_reads_parse_prefix_dev(const uint8_t* d_text, uint64_t nbytes, int format, int final, uint64_t* consumed, mg_reads** out);
 int mg_reads_parse(const uint8_t* text, uint64_t nbytes, int format, mg_reads** out);
+/* BAM record bytes in HBM (what follows the header; d_bytes starts at a record; n_ref = the header's reference count, which the
+ * record checks use) -> the reads `samtools fastq` (-F 0x900) writes for them: every record that is neither secondary (0x100)
+ * nor supplementary (0x800), in file order, its 4-bit SEQ decoded through "=ACMGRSVTWYHKDBN" and reverse-complemented back for
+ * 0x10 (SEQ '*': a read of length 0); QNAME, QUAL, CIGAR and the aux fields are ignored.  final / consumed as
+ * mg_reads_parse_prefix_dev (consumed = the end of the last complete record).  A break in the record chain (a corrupt
+ * block_size; final: a truncated record): MG_ERR_ARG, *err_at = that byte of d_bytes.
+ * mg_sketch_stream_add_file takes a BAM FILE as format 3 (BGZF or uncompressed, offset = length = 0): the header is read on
+ * the host with zlib and stepped over, the records go through the same pipeline and inflaters as mg_bam_stream_file.
+ * mg_reads_from_bam_file: a whole BAM reads file -> one batch (chunk_bytes / nthreads: 0 = defaults). */
+int mg_reads_parse_bam_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, int32_t n_ref, int final, uint64_t* consumed, mg_reads** out,
+                                  uint64_t* err_at);
+int mg_reads_from_bam_file(const char* path, uint64_t chunk_bytes, int nthreads, mg_reads** out);
 uint64_t mg_reads_count(const mg_reads* r);
 uint64_t mg_reads_nbases(const mg_reads* r);
 int mg_reads_device_ptrs(const mg_reads* r, const uint8_t** d_bases, const uint64_t** d_offsets);

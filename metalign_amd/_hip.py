@@ -35,7 +35,7 @@ EXPORTS = [
     "mg_sketch_reads_filtered_dev", "mg_sketch_reads_filtered_dev_async", "mg_sketch_from_pairs_dev", "mg_sketch_merge_dev", "mg_sketch_merge_dev_async", "mg_sketch_split", "mg_sketch_slice_words_dev", "mg_sketch_set_bound", "mg_sketch_size", "mg_sketch_truncated", "mg_sketch_last_hash",
     "mg_sketch_kmers_seen", "mg_sketch_device_ptrs", "mg_sketch_download", "mg_sketch_free", "mg_sketch_reads",
     "mg_sketch_stream_begin", "mg_sketch_stream_begin_counts", "mg_sketch_stream_add_dev", "mg_sketch_stream_add_file", "mg_sketch_stream_finish", "mg_sketch_stream_nreads", "mg_sketch_stream_nbases", "mg_sketch_stream_free",
-    "mg_reads_parse_dev", "mg_reads_parse_prefix_dev", "mg_reads_parse", "mg_reads_count", "mg_reads_nbases", "mg_reads_device_ptrs",
+    "mg_reads_parse_dev", "mg_reads_parse_prefix_dev", "mg_reads_parse", "mg_reads_parse_bam_prefix_dev", "mg_reads_from_bam_file", "mg_reads_count", "mg_reads_nbases", "mg_reads_device_ptrs",
     "mg_reads_download", "mg_reads_free",
     "mg_acc_index_build", "mg_acc_index_free", "mg_sam_tokenize_dev", "mg_sam_tokenize", "mg_paf_tokenize_dev", "mg_paf_tokenize", "mg_sam_stream_file", "mg_bam_stream_file", "mg_bam_tokenize_dev", "mg_sam_batch_count",
     "mg_sam_batch_last_qname", "mg_sam_batch_device_ptr", "mg_sam_batch_download", "mg_sam_batch_free",
@@ -113,7 +113,7 @@ def load_library(path=LIB_PATH):
     return lib
 
 
-_READS_FORMAT = {"fastq": 0, "fasta": 1, "fasta_ml": 2}
+_READS_FORMAT = {"fastq": 0, "fasta": 1, "fasta_ml": 2, "bam": 3}
 
 _host_lib = None
 
@@ -1253,6 +1253,27 @@ class Hip:
         h = _vp()
         self._chk(self.lib.mg_reads_parse_dev(_vp(d_text), ctypes.c_uint64(nbytes),
                                               ctypes.c_int(_READS_FORMAT[fmt]), ctypes.byref(h)))
+        return Reads(self, h)
+
+    def parse_bam_reads_dev(self, d_bytes, nbytes, n_ref, final=True):
+        """BAM record bytes resident in HBM (behind the header) -> (Reads, consumed) (mg_reads_parse_bam_prefix_dev): the reads
+        `samtools fastq` writes for them.  A break in the record chain raises HipError whose `err_at` is its byte."""
+        h = _vp()
+        used, at = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = self.lib.mg_reads_parse_bam_prefix_dev(_vp(d_bytes), ctypes.c_uint64(int(nbytes)), ctypes.c_int32(int(n_ref)),
+                                                    ctypes.c_int(1 if final else 0), ctypes.byref(used), ctypes.byref(h), ctypes.byref(at))
+        try:
+            self._chk(rc)
+        except HipError as e:
+            e.err_at = int(at.value)
+            raise
+        return Reads(self, h), int(used.value)
+
+    def reads_from_bam_file(self, path, chunk_bytes=0, nthreads=0):
+        """A whole BAM reads file -> device-resident Reads (mg_reads_from_bam_file), streamed and unpacked on the device."""
+        h = _vp()
+        self._chk(self.lib.mg_reads_from_bam_file(os.fsencode(path), ctypes.c_uint64(int(chunk_bytes)), ctypes.c_int(int(nthreads)),
+                                                  ctypes.byref(h)))
         return Reads(self, h)
 
     def sam_tokenize_dev(self, d_text, nbytes, acc_index, prev_qname=""):

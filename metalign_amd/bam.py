@@ -1,5 +1,5 @@
-"""BAM files on the host: detection, the header, and the SAM rendering of every record (SAM specification §4.2, as
-`samtools view -h` prints it).
+"""BAM files on the host: detection, the header, the SAM rendering of every record (SAM specification §4.2, as
+`samtools view -h` prints it), and the FASTQ rendering of a BAM READS file (fastq_records, as `samtools fastq` writes it).
 
 The device decodes BAM records itself (metalign_amd/csrc/mg_bam.hip); this module is the DEFINITION it is held to.  A record
 the device does not decide, or a file it refuses, is rendered here line by line and fed to the SAM path (map_and_process),
@@ -170,6 +170,53 @@ def sam_lines(path):
         yield ln.encode("utf-8")
     for body in rd.records():
         yield render(body, rd.names, path)
+
+
+_SEQ_PAIRS = [(SEQ_CODES[b >> 4] + SEQ_CODES[b & 15]).encode() for b in range(256)]
+_SEQ_COMP = bytes.maketrans(b"=ACMGRSVTWYHKDBN", b"=TGKCYSBAWRDMHVN")
+NOT_READ = 0x900  # secondary (0x100) | supplementary (0x800): not a read (`samtools fastq`'s default -F 0x900)
+ABSENT_QUAL = 1   # the quality written for a record without QUAL (0xff)
+
+
+def fastq_records(path):
+    """A BAM READS file -> its FASTQ rendering, one record (bytes, four lines) at a time, as `samtools fastq` with its default filter
+    writes it: every record that is neither secondary (0x100) nor supplementary (0x800), in file order; the name is QNAME; SEQ
+    decoded through "=ACMGRSVTWYHKDBN" and, for 0x10, reverse-complemented back to the read's own orientation (A<->T, C<->G, M<->K,
+    R<->Y, V<->B, H<->D; S, W, N, '=' kept); QUAL + 33, reversed for 0x10.  A record without QUAL (0xff) gets quality 1 ('"') at
+    every base: believed to be `samtools fastq -v 1`'s default, not checked against samtools here.  SEQ '*' is an empty read.
+    The device path (mg_reads_parse_bam_prefix_dev) uses the same rules for the bases; it is held to the FASTQ the reads came from,
+    not to this function.  A truncated or corrupt file raises ValueError naming it."""
+    rd = BamReader(path)
+    for body in rd.records():
+        l_rn, ncig, flag, l_seq = body[8], struct.unpack_from("<H", body, 12)[0], struct.unpack_from("<H", body, 14)[0], \
+            struct.unpack_from("<I", body, 16)[0]
+        if flag & NOT_READ:
+            continue
+        name = body[32:32 + l_rn - 1]
+        p = 32 + l_rn + 4 * ncig
+        packed = body[p:p + (l_seq + 1) // 2]
+        seq = b"".join(_SEQ_PAIRS[b] for b in packed)[:l_seq]
+        qual = body[p + (l_seq + 1) // 2:p + (l_seq + 1) // 2 + l_seq]
+        if l_seq and qual[0] == 0xFF:
+            qual = bytes([ABSENT_QUAL + 33]) * l_seq
+        else:
+            qual = bytes((q + 33) & 0xFF for q in qual)
+        if flag & 0x10:
+            seq = seq.translate(_SEQ_COMP)[::-1]
+            qual = qual[::-1]
+        yield b"@" + name + b"\n" + seq + b"\n+\n" + qual + b"\n"
+
+
+def write_fastq(path, out_path, batch=1 << 12):
+    """fastq_records(path) -> the file out_path."""
+    with open(out_path, "wb") as out:
+        buf = []
+        for rec in fastq_records(path):
+            buf.append(rec)
+            if len(buf) >= batch:
+                out.write(b"".join(buf))
+                buf = []
+        out.write(b"".join(buf))
 
 
 def warn_about(path):

@@ -52,7 +52,8 @@ _READ_TYPES = ['fastq', 'fasta', 'AUTO']
 _TOOLS = {
     'metalign': dict(
         description='Runs full metalign pipeline on input reads file(s).',
-        positionals=[('reads', dict(help='Reads file (FASTA / FASTQ, optionally .gz).')),
+        positionals=[('reads', dict(help='Reads file (FASTA / FASTQ, optionally .gz, or a BAM of reads; a paired BAM is aligned '
+                                          'single-end, as one reads file is).')),
                      ('data', dict(help='data/ directory (db_info.txt, organism_files/, sketch_table/).'))],
         options=['cutoff', 'db_dir', 'dbinfo_in', 'keep_temp_files', ('input_type', _READ_TYPES), 'length_normalize',
                  'low_mem', 'min_abundance', 'no_quantify_unmapped', 'output', 'pct_id', 'precise', 'rank_renormalize',
@@ -60,7 +61,7 @@ _TOOLS = {
                  'sketch_table', 'min_count', 'sketch_size', 'kmer_match', 'device_multimap']),
     'select_db': dict(
         description='Run CMash and select a subset of the whole database to align to.',
-        positionals=[('reads', dict(help='Reads file (FASTA / FASTQ, optionally .gz).')),
+        positionals=[('reads', dict(help='Reads file (FASTA / FASTQ, optionally .gz, or a BAM of reads).')),
                      ('data', dict(help='data/ directory (db_info.txt, organism_files/, sketch_table/).'))],
         options=['cmash_results', 'cutoff', ('db', 'AUTO', 'Subset database FASTA to write (default: temp_dir/cmashed_db.fna).'),
                  'db_dir', 'dbinfo_in', 'dbinfo_out', ('input_type', _READ_TYPES), 'keep_temp_files', 'strain_level',
@@ -97,6 +98,15 @@ def with_slash(path):
 
 
 _EXT = {'fq': 'fastq', 'fastq': 'fastq', 'fa': 'fasta', 'fna': 'fasta', 'fasta': 'fasta'}
+
+
+def reads_kind(path, input_type):
+    """The kind of a reads file: 'bam' for a BAM file (decided by its content, bam.is_bam, whatever its name or --input_type),
+    else input_type, or the extension's kind when that is 'AUTO'."""
+    from . import bam
+    if bam.is_bam(path):
+        return 'bam'
+    return sniff_reads_type(path) if input_type == 'AUTO' else input_type
 
 
 def sniff_reads_type(path):

@@ -17,6 +17,12 @@
 //   k_bam_decode   one lane per record (mg_bam_core.h: decode) -> LineOut, as k_sam_parse leaves a line;
 //   then the SAM tokeniser's own k_sam_list / k_sam_emit / k_sam_last_qname (aln_emit_retained): the new-read bit and the
 //   QNAME carried to the next piece.
+//
+// A BAM READS file (stages A / B) takes the same chain (bam_chain_dev), then:
+//   k_bam_seq_len     one lane per record: its kept length (mg_bam_core.h: kept_len) and whether it is a read; two scans give
+//                     every read's rank and its first base's place;
+//   k_bam_seq_unpack  one wavefront per record: the 4-bit SEQ -> ASCII bases (reverse-complemented for 0x10) in a `bases +
+//                     offsets` batch laid out like mg_reads_parse's, which the stage-A kernels take as they are.
 #include <zlib.h>
 
 #include <cstring>
@@ -163,24 +169,15 @@ __global__ __launch_bounds__(256) void k_bam_decode(const uint8_t* __restrict__ 
   }
 }
 
-int bam_tokenize_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* d_refmap, int32_t n_ref, const char* prev_qname,
-                            bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec) {
-  MG_REQUIRE_READY();
-  if (!out || !d_refmap) return fail(MG_ERR_ARG, "null argument");
-  *out = nullptr;
-  if (err_kind) *err_kind = 0;
-  if (err_rec) *err_rec = 0;
-  if (consumed) *consumed = 0;
-  if (nbytes && !d_bytes) return fail(MG_ERR_ARG, "null device bytes");
+// The chain step shared by the SAM-record decoder and the reads path: walk -> stitch -> scan -> compact.  nbytes > 0.
+// -> *d_rec_off (scratch: the record offsets, dense and in file order), *nrec, *consumed = the end of the last complete record.
+// A non-record on the true chain, or (final) bytes after the last complete record: MG_ERR_ARG, *err_at = that byte of the piece.
+static int bam_chain_dev(const uint8_t* d_bytes, uint64_t nbytes, int32_t n_ref, bool final, uint64_t* consumed, uint64_t** d_rec_off,
+                         uint64_t* nrec_out, uint64_t* err_at) {
   Context& c = ctx();
   hipStream_t st = c.stream;
-  std::unique_ptr<mg_sam_batch> sb(new mg_sam_batch());
-  if (prev_qname) sb->last_qname = prev_qname;
-  if (nbytes == 0) {
-    MG_TRY(sb->recs.alloc(16));
-    *out = sb.release();
-    return MG_OK;
-  }
+  *d_rec_off = nullptr;
+  *nrec_out = 0;
   const uint64_t nchunks = (nbytes + kBamChunk - 1) / kBamChunk;
   uint64_t* d_entry = (uint64_t*)scratch("bam_entry", nchunks * sizeof(uint64_t));
   uint64_t* d_exit = (uint64_t*)scratch("bam_exit", nchunks * sizeof(uint64_t));
@@ -205,32 +202,69 @@ int bam_tokenize_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32
     bad = reinterpret_cast<const volatile uint64_t*>(pin)[41];
   }
   if (bad != kNoEntry) {
-    if (err_kind) *err_kind = (int)mgb::kCorrupt;
-    if (err_rec) *err_rec = bad;
+    *err_at = bad;
     return fail(MG_ERR_ARG, "BAM: no record at byte %llu of the piece (a corrupt block_size?)", (unsigned long long)bad);
   }
   if (final && end != nbytes) {
-    if (err_kind) *err_kind = (int)mgb::kCorrupt;
-    if (err_rec) *err_rec = end;
+    *err_at = end;
     return fail(MG_ERR_ARG, "BAM: truncated record at byte %llu of the last piece", (unsigned long long)end);
   }
   if (consumed) *consumed = end;
+  if (nrec) {
+    uint64_t* d_off = (uint64_t*)scratch("bam_recoff", nrec * sizeof(uint64_t));
+    if (!d_off) return MG_ERR_NOMEM;
+    hipLaunchKernelGGL(k_bam_compact, dim3(grid_for(nchunks, 4, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_count, d_crank, d_offs,
+                       nchunks, d_off);
+    MG_HIP(hipGetLastError());
+    *d_rec_off = d_off;
+  }
+  *nrec_out = nrec;
+  return MG_OK;
+}
+
+int bam_tokenize_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* d_refmap, int32_t n_ref, const char* prev_qname,
+                            bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec) {
+  MG_REQUIRE_READY();
+  if (!out || !d_refmap) return fail(MG_ERR_ARG, "null argument");
+  *out = nullptr;
+  if (err_kind) *err_kind = 0;
+  if (err_rec) *err_rec = 0;
+  if (consumed) *consumed = 0;
+  if (nbytes && !d_bytes) return fail(MG_ERR_ARG, "null device bytes");
+  Context& c = ctx();
+  hipStream_t st = c.stream;
+  std::unique_ptr<mg_sam_batch> sb(new mg_sam_batch());
+  if (prev_qname) sb->last_qname = prev_qname;
+  if (nbytes == 0) {
+    MG_TRY(sb->recs.alloc(16));
+    *out = sb.release();
+    return MG_OK;
+  }
+  uint64_t* d_off = nullptr;
+  uint64_t nrec = 0, at = 0;
+  {
+    const int rc = bam_chain_dev(d_bytes, nbytes, n_ref, final, consumed, &d_off, &nrec, &at);
+    if (rc == MG_ERR_ARG) {
+      if (err_kind) *err_kind = (int)mgb::kCorrupt;
+      if (err_rec) *err_rec = at;
+    }
+    MG_TRY(rc);
+  }
+  unsigned long long* d_res = (unsigned long long*)scratch("bam_res", 4 * sizeof(unsigned long long));
+  uint64_t* pin = host_words();
   const size_t plen = prev_qname ? strlen(prev_qname) : 0;
   uint8_t* d_prev = (uint8_t*)scratch("bam_prev", plen + 16);
-  if (!d_prev) return MG_ERR_NOMEM;
+  if (!d_prev || !d_res) return MG_ERR_NOMEM;
   if (plen) MG_HIP(hipMemcpyAsync(d_prev, prev_qname, plen, hipMemcpyHostToDevice, st));
   uint64_t nret = 0;
   if (nrec) {
     ProfScope ps("bam_decode");
-    uint64_t* d_off = (uint64_t*)scratch("bam_recoff", nrec * sizeof(uint64_t));
     LineOut* d_lines = (LineOut*)scratch("bam_lines", nrec * sizeof(LineOut));
     uint32_t* d_ret = (uint32_t*)scratch("bam_ret", nrec * sizeof(uint32_t));
     uint64_t* d_rank = (uint64_t*)scratch("bam_rank", (nrec + 1) * sizeof(uint64_t));
     uint32_t* d_kind = (uint32_t*)scratch("bam_kind", nrec * sizeof(uint32_t));
-    if (!d_off || !d_lines || !d_ret || !d_rank || !d_kind) return MG_ERR_NOMEM;
+    if (!d_lines || !d_ret || !d_rank || !d_kind) return MG_ERR_NOMEM;
     MG_HIP(hipMemsetAsync(d_res + 2, 0xff, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_bam_compact, dim3(grid_for(nchunks, 4, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_count, d_crank, d_offs,
-                       nchunks, d_off);
     hipLaunchKernelGGL(k_bam_decode, dim3(grid_for(nrec, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_bytes, nbytes, d_off, nrec,
                        d_refmap, n_ref, d_lines, d_ret, d_res + 2, d_kind);
     MG_HIP(hipGetLastError());
@@ -252,6 +286,96 @@ int bam_tokenize_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32
   }
   sb->nrecs = nret;
   *out = sb.release();
+  return MG_OK;
+}
+
+// ---- reads (stages A / B): BAM records -> bases + offsets as mg_reads_parse leaves them (mg_bam_core.h: seq_kept / seq_base) ----
+
+// one lane per record: its kept length, and whether it is a read at all
+__global__ __launch_bounds__(256) void k_bam_seq_len(const uint8_t* __restrict__ b, const uint64_t* __restrict__ rec_off, uint64_t nrec,
+                                                     uint32_t* __restrict__ len, uint32_t* __restrict__ keep) {
+  uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (; r < nrec; r += stride) {
+    uint32_t k = 0;
+    len[r] = mgb::kept_len(b, rec_off[r], &k);
+    keep[r] = k;
+  }
+}
+
+// One wavefront per record: lane i writes bases 2i and 2i + 1 (+ 128 per step) of the read — consecutive output bytes across the
+// wavefront whichever the strand (a reverse record reads its packed bytes backwards); pos[r] may be odd, the stores are bytes.
+// offsets[rank[r]] = pos[r] for a read, and the last record closes the list: offsets[rank[nrec]] = pos[nrec].
+constexpr int kUnpackWaves = 4;
+__global__ __launch_bounds__(64 * kUnpackWaves) void k_bam_seq_unpack(const uint8_t* __restrict__ b, const uint64_t* __restrict__ rec_off,
+                                                                      uint64_t nrec, const uint32_t* __restrict__ keep,
+                                                                      const uint64_t* __restrict__ rank, const uint64_t* __restrict__ pos,
+                                                                      uint8_t* __restrict__ bases, uint64_t* __restrict__ offsets) {
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint64_t r = (uint64_t)blockIdx.x * kUnpackWaves + threadIdx.x / 64; r < nrec; r += (uint64_t)gridDim.x * kUnpackWaves) {
+    if (lane == 0) {
+      if (keep[r]) offsets[rank[r]] = pos[r];
+      if (r == nrec - 1) offsets[rank[nrec]] = pos[nrec];
+    }
+    const uint64_t o = pos[r];
+    const uint32_t len = (uint32_t)(pos[r + 1] - o);  // (0 for a record that is not a read)
+    if (len == 0) continue;
+    uint64_t seq = 0;
+    uint32_t lseq = 0, flag = 0;
+    mgb::seq_span(b, rec_off[r], &seq, &lseq, &flag);
+    const bool rev = (flag & mgb::kFlagReverse) != 0;
+    for (uint32_t j = 2 * lane; j < len; j += 128) {
+      bases[o + j] = mgb::seq_base(b, seq, len, rev, j);
+      if (j + 1 < len) bases[o + j + 1] = mgb::seq_base(b, seq, len, rev, j + 1);
+    }
+  }
+}
+
+int bam_reads_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, int32_t n_ref, bool final, uint64_t* consumed, mg_reads** out,
+                         uint64_t* err_at) {
+  MG_REQUIRE_READY();
+  if (!out) return fail(MG_ERR_ARG, "null out handle");
+  *out = nullptr;
+  if (consumed) *consumed = 0;
+  if (err_at) *err_at = 0;
+  if (nbytes && !d_bytes) return fail(MG_ERR_ARG, "null device bytes");
+  if (n_ref < 0) return fail(MG_ERR_ARG, "n_ref < 0");
+  Context& c = ctx();
+  hipStream_t st = c.stream;
+  std::unique_ptr<mg_reads> rd(new mg_reads());
+  uint64_t* d_off = nullptr;
+  uint64_t nrec = 0, at = 0;
+  if (nbytes) {
+    const int rc = bam_chain_dev(d_bytes, nbytes, n_ref, final, consumed, &d_off, &nrec, &at);
+    if (rc == MG_ERR_ARG && err_at) *err_at = at;
+    MG_TRY(rc);
+  }
+  if (nrec == 0) {
+    MG_TRY(rd->offsets.alloc(2 * sizeof(uint64_t)));
+    MG_TRY(rd->bases.alloc(16));
+    MG_HIP(hipMemsetAsync(rd->offsets.p, 0, 2 * sizeof(uint64_t), st));
+    *out = rd.release();
+    return MG_OK;
+  }
+  uint32_t* d_len = (uint32_t*)scratch("bamr_len", nrec * sizeof(uint32_t));
+  uint32_t* d_keep = (uint32_t*)scratch("bamr_keep", nrec * sizeof(uint32_t));
+  uint64_t* d_rank = (uint64_t*)scratch("bamr_rank", (nrec + 1) * sizeof(uint64_t));
+  uint64_t* d_pos = (uint64_t*)scratch("bamr_pos", (nrec + 1) * sizeof(uint64_t));
+  if (!d_len || !d_keep || !d_rank || !d_pos) return MG_ERR_NOMEM;
+  ProfScope ps("bam_reads");
+  hipLaunchKernelGGL(k_bam_seq_len, dim3(grid_for(nrec, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_bytes, d_off, nrec, d_len,
+                     d_keep);
+  MG_HIP(hipGetLastError());
+  uint64_t nkept = 0;
+  MG_TRY(exclusive_sum_u32_to_u64(d_keep, d_rank, nrec, &nkept));
+  MG_TRY(exclusive_sum_u32_to_u64(d_len, d_pos, nrec, &rd->nbases));
+  rd->nreads = nkept;
+  MG_TRY(rd->offsets.alloc((nkept + 2) * sizeof(uint64_t)));
+  MG_TRY(rd->bases.alloc(rd->nbases + 16));
+  hipLaunchKernelGGL(k_bam_seq_unpack, dim3(grid_for(nrec, kUnpackWaves, (unsigned)c.num_cus * 64)), dim3(64 * kUnpackWaves), 0, st,
+                     d_bytes, d_off, nrec, d_keep, d_rank, d_pos, rd->bases.as<uint8_t>(), rd->offsets.as<uint64_t>());
+  MG_HIP(hipGetLastError());
+  *out = rd.release();
   return MG_OK;
 }
 
@@ -329,6 +453,12 @@ int mg_bam_tokenize_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* 
                                          err_kind, err_rec);
   (void)hipStreamSynchronize(ctx().stream);  // (d_map is released here)
   return rc;
+}
+
+int mg_reads_parse_bam_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, int32_t n_ref, int final, uint64_t* consumed, mg_reads** out,
+                                  uint64_t* err_at) {
+  if (!consumed) return fail(MG_ERR_ARG, "null consumed");
+  return bam_reads_prefix_dev(d_bytes, nbytes, n_ref, final != 0, consumed, out, err_at);
 }
 
 }  // extern "C"

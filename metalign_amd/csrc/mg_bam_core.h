@@ -11,6 +11,13 @@
 //   walk()    the block_size chain from an entry over the records that START before a stop offset (one chunk of a piece).
 //   decode()  one record -> mg_aln_rec (without the new-read bit), its QNAME span, retained or not, or an error kind.
 //
+// A BAM READS file (stages A / B) is defined through `samtools fastq` with its default filter (-F 0x900):
+//   seq_kept()   a record is a read unless it is secondary (0x100) or supplementary (0x800);
+//   kept_len()   its length: l_seq (0 for SEQ '*'), 0 for a record that is not kept;
+//   seq_base()   base j of the read, in the read's own orientation: the 4-bit code through "=ACMGRSVTWYHKDBN", a record with 0x10
+//                set read backwards through the complement of each code (the code's four bits reversed: A<->T, C<->G, M<->K,
+//                R<->Y, V<->B, H<->D; S, W, N and '=' stay).
+//
 // Memory is reached through an accessor (`m[i]` = byte i of the range), so that the host test can run the same code on a
 // plain array.
 #pragma once
@@ -240,6 +247,40 @@ MGB_HD void decode(const M& m, uint64_t n, uint64_t p, const int32_t* refmap, in
   o->rec.flag_len = (flag & MG_REC_FLAG_MASK) | (lseq << MG_REC_LEN_SHIFT);
   o->qbeg = qn;
   o->qlen = qlen;
+}
+
+// ---- reads (stages A / B) ----
+constexpr uint32_t kFlagReverse = 0x10, kFlagNotRead = 0x900;  // (0x100 secondary | 0x800 supplementary)
+
+MGB_HD bool seq_kept(uint32_t flag) { return (flag & kFlagNotRead) == 0; }
+
+// code -> ASCII, and code -> the ASCII of its complement
+MGB_HD uint8_t seq_ascii(uint32_t code) { return (uint8_t)"=ACMGRSVTWYHKDBN"[code & 15u]; }
+MGB_HD uint8_t seq_ascii_comp(uint32_t code) { return (uint8_t)"=TGKCYSBAWRDMHVN"[code & 15u]; }
+
+// Where the SEQ of the complete record at p (check() said kOk) lies: *seq = its first packed byte, *lseq, *flag.
+template <class M>
+MGB_HD void seq_span(const M& m, uint64_t p, uint64_t* seq, uint32_t* lseq, uint32_t* flag) {
+  const uint32_t lrn = m[p + 12], ncig = ld16(m, p + 16);
+  *flag = ld16(m, p + 18);
+  *lseq = ld32(m, p + 20);
+  *seq = p + 4 + kFixed + lrn + 4ull * ncig;
+}
+
+// The record's kept length (0 when it is not a read; *kept tells the two zeros apart).
+template <class M>
+MGB_HD uint32_t kept_len(const M& m, uint64_t p, uint32_t* kept) {
+  const uint32_t flag = ld16(m, p + 18);
+  *kept = seq_kept(flag) ? 1u : 0u;
+  return *kept ? ld32(m, p + 20) : 0u;
+}
+
+// Base j (< lseq) of the read whose packed SEQ starts at seq: reverse = flag & 0x10.  One load, inside [seq, seq + (lseq + 1) / 2).
+template <class M>
+MGB_HD uint8_t seq_base(const M& m, uint64_t seq, uint32_t lseq, bool reverse, uint32_t j) {
+  const uint32_t i = reverse ? lseq - 1u - j : j;
+  const uint32_t code = (m[seq + (i >> 1)] >> ((i & 1u) ? 0 : 4)) & 15u;
+  return reverse ? seq_ascii_comp(code) : seq_ascii(code);
 }
 
 }  // namespace mgb

@@ -336,6 +336,10 @@ int bam_read_header(const char* path, BamHeader* h);
 std::vector<int32_t> bam_refmap(const std::vector<std::string>& names, const mg_acc_index* ix);
 int bam_tokenize_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* d_refmap, int32_t n_ref, const char* prev_qname,
                             bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec);
+// The reads of a piece of BAM records (`samtools fastq -F 0x900`, mg_bam_core.h) -> *out, as mg_reads_parse_prefix_dev for text;
+// a break in the chain: MG_ERR_ARG, *err_at = its byte in the piece.
+int bam_reads_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, int32_t n_ref, bool final, uint64_t* consumed, mg_reads** out,
+                         uint64_t* err_at);
 // thin: the piece comes from the file reader's thinning (mg_stream.hip: a SEQ field is MG_THIN_MARK + its length in decimal).
 int aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg_acc_index* ix, const char* prev_qname, bool paf,
                             bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_line, bool thin = false);

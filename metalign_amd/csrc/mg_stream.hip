@@ -830,6 +830,69 @@ static int open_for_device_inflate(const char* path, uint64_t offset, uint64_t l
   return fd;
 }
 
+// A BAM READS file (BGZF, or uncompressed) -> its reads, piece by piece: the header read here with zlib and stepped over, every
+// piece through the device inflater or the host readers exactly as mg_bam_stream_file, cut after its last complete record, its
+// records unpacked on the device (mg_bam.hip: bam_reads_prefix_dev).  sink(reads) owns each batch.  A break in the record chain:
+// MG_ERR_ARG naming the file and the byte of the inflated stream.
+static int bam_reads_file(const char* path, uint64_t chunk_bytes, int nthreads, const std::function<int(mg_reads*)>& sink) {
+  BamHeader hdr;
+  MG_TRY(bam_read_header(path, &hdr));
+  const int32_t n_ref = (int32_t)hdr.names.size();
+  std::unique_ptr<Source> src;
+  bool gz = false;
+  uint64_t gsize = 0;
+  int gfd = open_for_device_inflate(path, 0, 0, &gsize);
+  if (gfd >= 0) {  // (room for the compressed file on the device? as mg_bam_stream_file)
+    DevBuf probe;
+    if (probe.alloc(((gsize + 3) & ~3ull) + 64) != MG_OK) { close(gfd); gfd = -1; }
+  }
+  if (gfd < 0) MG_TRY(open_source(path, 0, 0, &chunk_bytes, &src, &gz));
+  const bool auto_threads = nthreads <= 0;
+  if (nthreads <= 0) nthreads = default_threads();
+  if (gz && src->parallel() && auto_threads) {  // BGZF: inflating is the work (as mg_sketch_stream_add_file)
+    const unsigned hw = std::thread::hardware_concurrency();
+    if (dbg("stream_threads") <= 0 && hw > (unsigned)nthreads) nthreads = (int)(hw > 32 ? 32 : hw);
+  }
+  uint64_t skip = hdr.bytes, done = hdr.bytes;  // done: the stream's bytes in front of this piece's records
+  Consumer consume = [&](const uint8_t* d_text, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
+    const uint64_t off = skip < nbytes ? skip : nbytes;  // the header's bytes
+    skip -= off;
+    if (skip) {
+      *consumed = nbytes;
+      return final ? fail(MG_ERR_ARG, "%s: the BAM header runs past the end of the file", path) : MG_OK;
+    }
+    mg_reads* rd = nullptr;
+    uint64_t used = 0, at = 0;
+    const int rc = bam_reads_prefix_dev(d_text + off, nbytes - off, n_ref, final, &used, &rd, &at);
+    if (rc == MG_ERR_ARG) {
+      const std::string why = mg_last_error();
+      return fail(MG_ERR_ARG, "%s: corrupt or truncated BAM at byte %llu of the inflated stream (%s)", path,
+                  (unsigned long long)(done + at), why.c_str());
+    }
+    MG_TRY(rc);
+    *consumed = off + used;
+    done += used;
+    return sink(rd);
+  };
+  int rc = MG_OK;
+  if (gfd >= 0) {
+    rc = inflate_file_pipeline(gfd, gsize, consume, nullptr);
+    close(gfd);
+  } else {
+    rc = run_pipeline(*src, chunk_bytes, nthreads, consume, nullptr);
+  }
+  if (rc == MG_ERR_CAPACITY) {  // (a record longer than a piece's headroom — or a corrupt block_size that claims one)
+    const std::string why = mg_last_error();
+    return fail(MG_ERR_CAPACITY, "%s: %s", path, why.c_str());
+  }
+  return rc;
+}
+
+__global__ __launch_bounds__(256) void k_shift_offsets(const uint64_t* __restrict__ in, uint64_t n, uint64_t add, uint64_t* __restrict__ out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = in[i] + add;
+}
+
 }  // namespace mg
 
 using namespace mg;
@@ -840,7 +903,18 @@ int mg_sketch_stream_add_file(mg_sketch_stream* ss, const char* path, int format
                               uint64_t chunk_bytes, int nthreads) {
   MG_REQUIRE_READY();
   if (!ss || !path) return fail(MG_ERR_ARG, "null argument");
-  if (format < 0 || format > 2) return fail(MG_ERR_ARG, "format must be 0 (fastq), 1 (single-line fasta) or 2 (fasta)");
+  if (format < 0 || format > 3) return fail(MG_ERR_ARG, "format must be 0 (fastq), 1 (single-line fasta), 2 (fasta) or 3 (bam)");
+  if (format == 3) {
+    if (offset || length) return fail(MG_ERR_ARG, "a byte range of a BAM file cannot be streamed");
+    return bam_reads_file(path, chunk_bytes, nthreads, [&](mg_reads* rd) -> int {
+      const uint8_t* d_b = nullptr;
+      const uint64_t* d_o = nullptr;
+      int rc = mg_reads_device_ptrs(rd, &d_b, &d_o);
+      if (rc == MG_OK) rc = mg_sketch_stream_add_dev(ss, d_b, d_o, mg_reads_count(rd), mg_reads_nbases(rd));
+      mg_reads_free(rd);  // (stream-ordered, as for text)
+      return rc;
+    });
+  }
   {
     uint64_t fsize = 0;
     const int gfd = open_for_device_inflate(path, offset, length, &fsize);
@@ -885,6 +959,46 @@ int mg_sketch_stream_add_file(mg_sketch_stream* ss, const char* path, int format
     return rc;
   };
   return run_pipeline(*src, chunk_bytes, nthreads, consume, nullptr);
+}
+
+// A whole BAM reads file -> one batch (the multi-rank path: rank 0 decodes, then shares the reads out)
+int mg_reads_from_bam_file(const char* path, uint64_t chunk_bytes, int nthreads, mg_reads** out) {
+  MG_REQUIRE_READY();
+  if (!path || !out) return fail(MG_ERR_ARG, "null argument");
+  *out = nullptr;
+  std::vector<std::unique_ptr<mg_reads>> parts;
+  uint64_t nreads = 0, nbases = 0;
+  MG_TRY(bam_reads_file(path, chunk_bytes, nthreads, [&](mg_reads* rd) -> int {
+    nreads += rd->nreads;
+    nbases += rd->nbases;
+    parts.emplace_back(rd);
+    return MG_OK;
+  }));
+  if (parts.size() == 1) {
+    *out = parts[0].release();
+    return MG_OK;
+  }
+  std::unique_ptr<mg_reads> all(new mg_reads());
+  all->nreads = nreads;
+  all->nbases = nbases;
+  MG_TRY(all->offsets.alloc((nreads + 2) * sizeof(uint64_t)));
+  MG_TRY(all->bases.alloc(nbases + 16));
+  hipStream_t st = ctx().stream;
+  MG_HIP(hipMemsetAsync(all->offsets.p, 0, sizeof(uint64_t), st));  // (offsets[0]; no parts at all: an empty batch)
+  uint64_t r = 0, b = 0;
+  for (auto& p : parts) {
+    if (p->nbases) MG_HIP(hipMemcpyAsync(all->bases.as<uint8_t>() + b, p->bases.p, p->nbases, hipMemcpyDeviceToDevice, st));
+    // (offsets[1 .. n] of the part, shifted by the bases in front of it: its offsets[0] = 0 is the previous part's last)
+    if (p->nreads)
+      hipLaunchKernelGGL(k_shift_offsets, dim3(grid_for(p->nreads, 256, 1024)), dim3(256), 0, st, p->offsets.as<uint64_t>() + 1,
+                         p->nreads, b, all->offsets.as<uint64_t>() + r + 1);
+    MG_HIP(hipGetLastError());
+    r += p->nreads;
+    b += p->nbases;
+  }
+  MG_HIP(hipStreamSynchronize(st));
+  *out = all.release();
+  return MG_OK;
 }
 
 // The batches of a file's pieces -> one (a single piece's records are taken over as they are)

@@ -37,6 +37,19 @@ def _wire_stages(args):
     args.cmash_results = 'NONE'
 
 
+def _bam_for_the_aligner(args):
+    """Stages A / B took the BAM itself; minimap2 reads FASTA / FASTQ only, so stage C aligns its FASTQ rendering
+    (bam.fastq_records), written to temp_dir (kept with --keep_temp_files, like every other temporary).  A paired BAM becomes
+    one file aligned single-end, as the reference aligns one reads file.  The profile's @SampleID stays the BAM's path."""
+    from . import bam
+    fq = args.temp_dir + 'reads_from_bam.fq'
+    bam.write_fastq(args.reads, fq)
+    if args.sampleID == 'NONE':
+        args.sampleID = args.reads
+    args.infiles = [fq]
+    args.input_type = 'fastq'
+
+
 def main(argv=None):
     args = metalign_parseargs(argv)
     args.data = cli.with_slash(args.data)
@@ -48,8 +61,7 @@ def main(argv=None):
         args.dbinfo_in = args.data + 'db_info.txt'
     if args.db_dir == 'AUTO':
         args.db_dir = args.data + 'organism_files/'
-    if args.input_type == 'AUTO':
-        args.input_type = cli.sniff_reads_type(args.reads)
+    args.input_type = cli.reads_kind(args.reads, args.input_type)  # ('bam': a BAM file, whatever its name or --input_type)
     _apply_modes(args)
     _wire_stages(args)
     select.select_main(args)
@@ -62,6 +74,8 @@ def main(argv=None):
         if own_temp and not args.keep_temp_files:
             shutil.rmtree(args.temp_dir, ignore_errors=True)
         return
+    if args.input_type == 'bam':
+        _bam_for_the_aligner(args)
     mapper.map_main(args)
     if not args.keep_temp_files:
         shutil.rmtree(args.temp_dir, ignore_errors=True)

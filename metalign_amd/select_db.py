@@ -78,6 +78,11 @@ class _HostParsedReads:
         self._o.free()
 
 
+def reads_format(kind):
+    """The library's reads format of a reads kind: 'fastq', 'bam', or any FASTA ('fasta_ml': sequences over any number of lines)."""
+    return kind if kind in ('fastq', 'bam') else 'fasta_ml'
+
+
 def load_reads_device(hip, path, kind):
     """Reads file -> device-resident bases + offsets.  FASTQ and FASTA are parsed on the GPU from the raw
     (decompressed) text (mg_reads_parse_dev); the host parser is only the fallback for text the device rejects."""
@@ -275,6 +280,49 @@ def scatter_text(dist, rank, world, dev, text, kind):
     return t.cpu().numpy().tobytes()
 
 
+def read_share_cuts(offsets, world):
+    """world + 1 read indices: share r = reads [cut[r], cut[r + 1]), cut where the bases split evenly (whole reads only)."""
+    n = len(offsets) - 1
+    total = int(offsets[-1])
+    cuts = [0] + [min(int(np.searchsorted(offsets, total * r // world, side='left')), n) for r in range(1, world)] + [n]
+    for i in range(1, len(cuts)):
+        cuts[i] = max(cuts[i], cuts[i - 1])
+    return cuts
+
+
+def scatter_reads(dist, rank, world, dev, bases, offsets):
+    """Rank 0 holds the reads (bases u8, offsets u64); -> this rank's share of whole reads, its offsets from 0.  Sizes by broadcast,
+    the shares by point-to-point sends, as scatter_text."""
+    import torch
+    if world == 1:
+        return bases, offsets
+    sizes = [None]
+    if rank == 0:
+        cuts = read_share_cuts(offsets, world)
+        sizes = [[(cuts[r + 1] - cuts[r], int(offsets[cuts[r + 1]] - offsets[cuts[r]])) for r in range(world)]]
+    dist.broadcast_object_list(sizes, src=0)
+    nreads, nbases = sizes[0][rank]
+    if rank == 0:
+        reqs = []
+        for q in range(1, world):
+            a, b = cuts[q], cuts[q + 1]
+            offs = (offsets[a:b + 1] - offsets[a]).astype(np.int64)
+            ts = [torch.from_numpy(offs).to(dev)]
+            if sizes[0][q][1]:
+                ts.append(torch.from_numpy(bases[int(offsets[a]):int(offsets[b])].copy()).to(dev))
+            reqs += [(dist.isend(t, dst=q), t) for t in ts]
+        for r, _ in reqs:
+            r.wait()
+        b = cuts[1]
+        return bases[:int(offsets[b])], offsets[:b + 1].copy()
+    t_o = torch.empty(nreads + 1, dtype=torch.int64, device=dev)
+    dist.recv(t_o, src=0)
+    t_b = torch.empty(nbases, dtype=torch.uint8, device=dev)
+    if nbases:
+        dist.recv(t_b, src=0)
+    return t_b.cpu().numpy(), t_o.cpu().numpy().astype(np.uint64)
+
+
 _dist_keep = []  # (the torch stream the library launches on must outlive the job)
 
 
@@ -319,7 +367,16 @@ def run_sketch_steps_dist(args, ctx):
         dist.all_gather(out, t)
         return [int(o.item()) for o in out]
 
-    if formats.is_gzip(args.reads):
+    if args.input_type == 'bam':
+        # rank 0 decodes the BAM ON ITS GPU (the reads stream of mg_reads_from_bam_file) and scatters record-aligned shares of the
+        # reads themselves; cutting BAM shares on every rank is not done
+        rb = ro = None
+        if rank == 0:
+            reads = hip.reads_from_bam_file(args.reads)
+            rb, ro = reads.download()
+            reads.free()
+        rb, ro = scatter_reads(dist, rank, world, dev, rb, ro)
+    elif formats.is_gzip(args.reads):
         # rank 0 inflates the file ON ITS GPU (mg_inflate.hip: compressed bytes up, text down; round 4 did it with every core of
         # the host, mg_pgzip.hip — 0.40 s against 0.07 + 0.06 s for a 10M-read file) and SCATTERS record-aligned shares of the
         # text: every rank parses and sketches its own (rounds 2-3: rank 0 inflated on one core and sketched everything, the
@@ -341,9 +398,10 @@ def run_sketch_steps_dist(args, ctx):
         with open(args.reads, 'rb') as fh:
             fh.seek(start)
             text = fh.read(end - start)
-    reads = hip.parse_reads(text, 'fastq' if args.input_type == 'fastq' else 'fasta_ml')
-    rb, ro = reads.download()
-    reads.free()
+    if args.input_type != 'bam':
+        reads = hip.parse_reads(text, 'fastq' if args.input_type == 'fastq' else 'fasta_ml')
+        rb, ro = reads.download()
+        reads.free()
     if os.environ.get('MG_DIST_REPORT') == '1':  # (tests: what every rank's shard held)
         with open(os.path.join(args.temp_dir, 'shard_rank%d.txt' % rank), 'w') as fh:
             fh.write('%d reads, %d bases\n' % (len(ro) - 1, len(rb)))
@@ -383,6 +441,9 @@ def iter_read_batches(hip, path, kind, batch_bytes):
     larger than the device's free memory is sketched piece by piece and the sketches are merged (run_sketch_steps);
     the reference's kmc spills to disk instead (scripts/select_db.py:50-52)."""
     import gzip
+    if kind == 'bam':
+        yield from _bam_read_batches(hip, path, batch_bytes)
+        return
     gz = path.endswith('.gz')
     if not gz and os.path.getsize(path) <= batch_bytes:
         yield load_reads_device(hip, path, kind)
@@ -404,11 +465,35 @@ def iter_read_batches(hip, path, kind, batch_bytes):
             carry = data[cut:]
 
 
+def _bam_read_batches(hip, path, batch_bytes):
+    """A BAM reads file as device batches: the whole file decoded on the device (mg_reads_from_bam_file); a record larger than a
+    streaming piece's headroom goes through the host rendering (bam.fastq_records) in FASTQ batches of about batch_bytes."""
+    from . import bam
+    try:
+        yield hip.reads_from_bam_file(path)
+        return
+    except _hip.HipError as e:
+        if e.code != _hip.ERR_CAPACITY:
+            raise
+    buf, size = [], 0
+    for rec in bam.fastq_records(path):
+        buf.append(rec)
+        size += len(rec)
+        if size >= batch_bytes:
+            yield hip.parse_reads(b''.join(buf), 'fastq')
+            buf, size = [], 0
+    if buf:
+        yield hip.parse_reads(b''.join(buf), 'fastq')
+
+
 def expected_bases(path, kind):
     """Roughly the bases in a reads file, from its size: sizes the streamed sketch's counting tables (an estimate that
     proves too small is caught — a table overflow — and the file streamed again).  FASTQ: half the bytes are bases;
-    gzip: DNA text deflates about 4 x."""
+    gzip: DNA text deflates about 4 x.  BAM: a record holds half a byte of SEQ and a byte of QUAL per base, plus ~60 bytes
+    of fixed part and name (about 0.55 bases per byte at 150 bp); BGZF: about 2.5 x, qualities deflate poorly."""
     size = os.path.getsize(path)
+    if kind == 'bam':
+        return int(size * (2.5 if formats.is_gzip(path) else 1.0) * 0.55) + 1
     if path.endswith('.gz'):
         guess = size * 4
         try:  # a gzip member ends with the length of its text (mod 2^32): the whole text for a file of one member below 4 GB
@@ -431,7 +516,7 @@ def stream_reads_file(hip, path, kind, ks, hmaxs, s, filts, offset=0, length=0):
     scripts/select_db.py:45-52 (`.gz` expected: :146-148).
     None when the file does not suit the pipeline (a record larger than a chunk's headroom; FASTA text the device parser
     rejects): the caller takes the piece-wise path, whose host parser decides."""
-    fmt = 'fastq' if kind == 'fastq' else 'fasta_ml'
+    fmt = reads_format(kind)
     expect = expected_bases(path, kind) if not length else int(length * (0.5 if kind == 'fastq' else 1.0)) + 1
     chunk = int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0))
     for attempt in range(2):
@@ -443,7 +528,7 @@ def stream_reads_file(hip, path, kind, ks, hmaxs, s, filts, offset=0, length=0):
             except _hip.HipError as e:
                 # a record longer than a piece's headroom (capacity), or FASTA text the device parser refuses: not for
                 # this pipeline; a malformed FASTQ record is the caller's error, as on the whole-file path
-                if e.code == _hip.ERR_CAPACITY or (e.code == _hip.ERR_ARG and kind != 'fastq'):
+                if e.code == _hip.ERR_CAPACITY or (e.code == _hip.ERR_ARG and kind not in ('fastq', 'bam')):
                     return None
                 raise
             sks = stream.finish()
@@ -618,12 +703,12 @@ def _run_count_steps(args, hip, table, arrays, t_start):
     if os.environ.get('MG_NO_STREAM') != '1':
         stream = hip.count_stream(counts)
         try:
-            stream.add_file(args.reads, 'fastq' if kind == 'fastq' else 'fasta_ml', chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)))
+            stream.add_file(args.reads, reads_format(kind), chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)))
             done = True
         except _hip.HipError as e:
             # a record longer than a piece's headroom (capacity), or FASTA text the device parser refuses: the piece-wise path's
-            # host parser decides; a malformed FASTQ record is the caller's error, as on the whole-file path
-            if not (e.code == _hip.ERR_CAPACITY or (e.code == _hip.ERR_ARG and kind != 'fastq')):
+            # host parser decides; a malformed FASTQ record or a corrupt BAM is the caller's error, as on the whole-file path
+            if not (e.code == _hip.ERR_CAPACITY or (e.code == _hip.ERR_ARG and kind not in ('fastq', 'bam'))):
                 raise
             counts.reset()
         finally:
@@ -717,8 +802,7 @@ def select_main(args=None):
                           ('db', args.temp_dir + 'cmashed_db.fna')):
         if getattr(args, attr) == 'AUTO':
             setattr(args, attr, default)
-    if args.input_type == 'AUTO':
-        args.input_type = cli.sniff_reads_type(args.reads)
+    args.input_type = cli.reads_kind(args.reads, args.input_type)  # ('bam': a BAM file, whatever its name or --input_type)
 
     # db_info is parsed by a second thread while the reads stream through the device (the library calls release the
     # interpreter lock): 0.011 s of a 0.16 s select_main at 10M reads.  The file is opened here, so that a missing one still
