@@ -89,9 +89,16 @@ def pack_table(table, k):
     return hi, lo
 
 
-@pytest.mark.parametrize("k", [15, 16, 17, 21, 31, 32, 33, 47, 51, 60, 63, 64])
-@pytest.mark.parametrize("kind,cap,lead,cs,bb", [("equal", 12, 0, 0, 0), ("ragged", 12, 5, 2, 0), ("ragged", 3, 0, 0, 0), ("long", 12, 3, 3, 0),
-                                                 ("equal", 3, 9, 1, 0), ("ragged", 12, 2, 2, 4)])
+# every k the host checker (and mg_kcount.hip) is built for: twelve of them with every case, the other 38 with a restart case and the
+# chunked one (the flank steps at k = 19, 23, 53, 55, ..., every candidate count W = k - 14 - 2 e)
+K_ALL = range(15, 65)
+K_EVERY_CASE = (15, 16, 17, 21, 31, 32, 33, 47, 51, 60, 63, 64)
+CASES = [("equal", 12, 0, 0, 0), ("ragged", 12, 5, 2, 0), ("ragged", 3, 0, 0, 0), ("long", 12, 3, 3, 0), ("equal", 3, 9, 1, 0), ("ragged", 12, 2, 2, 4)]
+CASES_EVERY_K = (("ragged", 3, 0, 0, 0), ("long", 12, 3, 3, 0))
+PARAMS = [c + (k,) for c in CASES for k in K_ALL if k in K_EVERY_CASE or c in CASES_EVERY_K]
+
+
+@pytest.mark.parametrize("kind,cap,lead,cs,bb,k", PARAMS, ids=["-".join(map(str, p)) for p in PARAMS])
 def test_counts_equal_the_oracle(checker, k, kind, cap, lead, cs, bb):
     oracle.build()
     rng = np.random.default_rng(1000 * k + cap + lead)

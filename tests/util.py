@@ -221,3 +221,105 @@ def tile_transitions(kinds, grid, waves=4):
     for seq in wave_tiles(len(kinds), grid, waves):
         out.update((kinds[a], kinds[b]) for a, b in zip(seq, seq[1:]))
     return out
+
+
+# ---- every k: the builders of tests/test_gpu_every_k.py (one small sample per k that reaches what changes with k)
+def revcomp(s):
+    """bytes -> the reverse complement (upper or lower case; N stays N)"""
+    return bytes(_COMP[np.frombuffer(s, dtype=np.uint8)[::-1]])
+
+
+def unpack_kmer(hi, lo, k):
+    """A table's 2-bit packed k-mer (first base most significant) -> bytes"""
+    v = (int(hi) << 64) | int(lo)
+    return bytes(b"ACGT"[(v >> (2 * (k - 1 - i))) & 3] for i in range(k))
+
+
+def pack_kmer(s):
+    """bytes of ACGT -> (hi, lo) as sketch_genomes_kmers packs them"""
+    v = 0
+    for ch in s:
+        v = (v << 2) | b"ACGT".index(ch)
+    return v >> 64, v & 0xFFFFFFFFFFFFFFFF
+
+
+def palindrome(rng, k):
+    """A k-mer that is its own reverse complement (k even)."""
+    half = rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=k // 2).astype(np.uint8).tobytes()
+    return half + revcomp(half)
+
+
+def with_entry(entries, g, kmer, h):
+    """sketch_genomes_kmers' entries with one more in genome g — the k-mer `kmer` matched by hash h — at its place by hash (at the end of
+    a genome whose hashes do not ascend: a forward-selected one), unless the genome holds it already.  -> the same four arrays"""
+    hashes, khi, klo, offs = entries
+    a, b = int(offs[g]), int(offs[g + 1])
+    hi, lo = pack_kmer(kmer)
+    if np.any((khi[a:b] == np.uint64(hi)) & (klo[a:b] == np.uint64(lo))):
+        return entries
+    at = a + int(np.searchsorted(hashes[a:b], np.uint64(h))) if b > a and np.all(hashes[a + 1:b] >= hashes[a:b - 1]) else b
+    ins = lambda arr, v: np.insert(arr, at, np.uint64(v))  # noqa: E731
+    offs = offs.copy()
+    offs[g + 1:] += np.uint64(1)
+    return ins(hashes, h), ins(khi, hi), ins(klo, lo), offs
+
+
+# the order of tiles that walks every pair of TILE_TRANSITIONS: a clean tile around every other kind
+_KIND_CHAIN = ("clean", "bad", "clean", "long", "clean", "span", "clean", "short", "clean", "ragged", "clean", "foreign", "clean", "repeat", "clean")
+
+
+def tile_kinds_walked(rng, ntiles, grid=1, waves=4, seg=5):
+    """tile_kinds, with the first `seg` tiles of the wavefronts of a persistent grid of `grid` workgroups laid out so that together they
+    walk _KIND_CHAIN (each wavefront's piece begins with the kind the last one's ended on): every kind, every pair of TILE_TRANSITIONS.
+    Needs seg tiles on enough wavefronts: ntiles >= 4 * seg at grid 1."""
+    kinds = tile_kinds(rng, ntiles)
+    pos = 0
+    for seq in wave_tiles(ntiles, grid, waves):
+        if pos >= len(_KIND_CHAIN) - 1:
+            break
+        for t, kind in zip(seq, _KIND_CHAIN[pos:pos + seg]):
+            kinds[t] = kind
+        pos += seg - 1
+    return kinds
+
+
+def edge_reads(rng, gbases, goffsets, k, table_kmers, pal=None):
+    """The reads at the edges of k: reads of k - 1, k and k + 1 bases of table k-mers; reads whose first and last windows are table
+    k-mers, in both orientations and twice; reads of 1023, 1024, 1025 and 2600 bases (k_count_kmers takes reads above 1023 in chunks that
+    overlap by k - 1); reads holding `pal` (a reverse-palindromic k-mer) and `pal` alone.  -> [bytes]"""
+    g = bytes(gbases[int(goffsets[1]):int(goffsets[2])])
+    out = []
+    for i in range(3):
+        a, b = table_kmers[(2 * i) % len(table_kmers)], table_kmers[(2 * i + 1) % len(table_kmers)]
+        out += [a[:k - 1], a, a + b"ACGT"[i:i + 1], revcomp(b)]
+        s = int(rng.integers(0, len(g) - 60))
+        r = a + g[s:s + 20 + 13 * i] + b
+        out += [r, revcomp(r)] * 2
+    for n in (1023, 1024, 1025, 2600):
+        s = int(rng.integers(0, len(g) - n + 1))
+        out.append(g[s:s + n] if n != 1024 else revcomp(g[s:s + n]))
+    if pal is not None:
+        for i in range(3):
+            s = int(rng.integers(0, len(g) - 60))
+            out.append(g[s:s + 7 + i] + pal + g[s + 30:s + 60])
+        out.append(pal)
+    return out
+
+
+def edge_sample(rng, gbases, goffsets, kinds, k, edges, last=TILE, main=0, present=(0, 1, 2, 3, 4, 5)):
+    """tile_sample of `kinds`, where a kind "edge" is a tile of the next 64 of `edges` (the last such tile filled up with 150-base reads of
+    genome `main`).  -> (bases u8, offsets u64)"""
+    reads, e = [], list(edges)
+    for t, kind in enumerate(kinds):
+        nr = last if t == len(kinds) - 1 else TILE
+        if kind == "edge":
+            tile, e = e[:nr], e[nr:]
+            while len(tile) < nr:
+                a = int(goffsets[main]) + int(rng.integers(0, int(goffsets[main + 1] - goffsets[main]) - 150))
+                tile.append(bytes(gbases[a:a + 150]))
+            reads += tile
+        else:
+            b, o = tile_sample(rng, gbases, goffsets, [kind], k, last=nr, main=main, present=present)
+            reads += [bytes(b[int(o[i]):int(o[i + 1])]) for i in range(len(o) - 1)]
+    assert not e, "more edge reads than edge tiles"
+    return flat(reads)
