@@ -5,7 +5,8 @@
 #include "mg_internal.h"
 
 namespace mg {
-// .gz inputs of mg_sketch_stream_add_file / mg_sam_stream_file go through the device (mg_inflate_config's `on`)
+// gzip / BGZF inputs of mg_stream.hip's stream_file — reads text, BAM reads, SAM / PAF text, BAM alignments — go through the
+// device (mg_inflate_config's `on`)
 bool inflate_dev_enabled();
 // The file's text, stage by stage: consume(d_text, nbytes, final, &consumed) as in mg_stream.hip's pipeline — [consumed, nbytes) is
 // carried in front of the next stage's text on the device.

@@ -13,6 +13,21 @@
 //                       (mg_sketch_stream_add_dev: ONE set of counting tables for the whole file)
 //
 // Nothing of the text ever exists as a host array beyond the slots; the host never looks at a byte of it.
+//
+// That is the HOST pipeline (run_pipeline).  A gzip or BGZF file has a second one, the DEVICE inflater
+// (mg_inflate.hip: inflate_file_pipeline), which takes the compressed bytes up and hands the same [carry | piece] text to the
+// same consumer.  stream_file chooses, once for all four entry points (reads text, BAM reads, SAM / PAF text, BAM alignments):
+//
+//   the file                                                             goes through
+//   gzip / BGZF, whole, mg_inflate_config on, at most half of the        the device inflater; if that runs out of device
+//     free device memory (and the knob inflate_dev_max_bytes)              memory before its first piece: the host pipeline
+//   gzip / BGZF otherwise                                                the host pipeline: BgzfSource on all readers, or
+//                                                                          ParallelGzipSource / GzipSource feeding one reader
+//   plain, whole, of a kind that thins, knob stream_thin                 the host pipeline, ThinSource (*thinned = true)
+//   plain otherwise (a byte range; an uncompressed BAM)                  the host pipeline, PlainSource
+//
+// and reader_threads says how many readers the host pipeline gets.  What an entry point adds is its StreamPlan (data), its
+// consumer, a BAM file's header (skip_bam_header) and the assembly of its result.
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -795,20 +810,36 @@ static int open_source(const char* path, uint64_t offset, uint64_t length, uint6
   return MG_OK;
 }
 
-// Thinning is host work per byte (a reader does ~4 GB/s of it against ~12 GB/s of plain reads): twice the readers, when the
-// box has them and nobody fixed the number.
-static int thin_threads(int n) {
-  if (dbg("stream_threads") > 0) return n;
-  const unsigned hw = std::thread::hardware_concurrency();
-  const int want = n * 2;
-  return hw >= (unsigned)want * 2 ? want : n;
-}
+// ---------------------------------------------------------------------------------------------------------------------
+// the driver: this file's bytes, as pieces of text on the device, to this consumer (the decision table is at the top of the file)
+// ---------------------------------------------------------------------------------------------------------------------
+// What differs between the entry points — data, not code.
+struct StreamPlan {
+  uint64_t offset = 0, length = 0;  // a byte range of a plain file (0, 0: the whole file)
+  uint64_t chunk_bytes = 0;         // 0: the default of the source's kind (open_source)
+  int nthreads = 0;                 // <= 0: reader_threads decides
+  int thin_kind = -1;               // -1, or the ThinSource::Kind a plain whole file may be thinned as
+  // The host readers of a BGZF file, when the caller named no number: every core (up to 32), because inflating is the work —
+  // or the eight of any other file.  The entry points differ, and every figure was taken with these values:
+  //   mg_sketch_stream_add_file, text   true       bam_reads_file       true
+  //   mg_sam_stream_file                false      mg_bam_stream_file   false
+  bool bgzf_uses_all_cores = false;
+  // ... and also when the caller DID name a number (mg_sketch_stream_add_file's text formats only: the tests and the probes under
+  // tools/ that pass thread counts measure this)
+  bool bgzf_overrides_caller = false;
+};
 
-static int default_threads() {
-  unsigned hw = std::thread::hardware_concurrency();
-  if (hw == 0) hw = 4;
-  if (dbg("stream_threads") > 0) return (int)dbg("stream_threads");
-  return (int)(hw > 8 ? 8 : hw);
+// The reader threads of the host pipeline (run_pipeline itself takes one for a source that is not parallel()).
+static int reader_threads(const StreamPlan& plan, bool bgzf, bool thinned) {
+  const unsigned hw = std::thread::hardware_concurrency();
+  const bool auto_threads = plan.nthreads <= 0;
+  if (dbg("stream_threads") > 0) return auto_threads ? (int)dbg("stream_threads") : plan.nthreads;  // (the knob fixes the number)
+  int n = auto_threads ? (int)(hw == 0 ? 4 : (hw > 8 ? 8 : hw)) : plan.nthreads;
+  if (bgzf && plan.bgzf_uses_all_cores && (auto_threads || plan.bgzf_overrides_caller) && hw > (unsigned)n) n = (int)(hw > 32 ? 32 : hw);
+  // Thinning is host work per byte (a reader does ~4 GB/s of it against ~12 GB/s of plain reads): twice the readers, when the
+  // box has twice as many cores again and nobody fixed the number.
+  if (thinned && auto_threads && hw >= (unsigned)n * 4) n *= 2;
+  return n;
 }
 
 // A `.gz` file (gzip or BGZF) whose compressed bytes go to the device and are inflated there (mg_inflate.hip), unless
@@ -830,61 +861,83 @@ static int open_for_device_inflate(const char* path, uint64_t offset, uint64_t l
   return fd;
 }
 
-// A BAM READS file (BGZF, or uncompressed) -> its reads, piece by piece: the header read here with zlib and stepped over, every
-// piece through the device inflater or the host readers exactly as mg_bam_stream_file, cut after its last complete record, its
-// records unpacked on the device (mg_bam.hip: bam_reads_prefix_dev).  sink(reads) owns each batch.  A break in the record chain:
-// MG_ERR_ARG naming the file and the byte of the inflated stream.
-static int bam_reads_file(const char* path, uint64_t chunk_bytes, int nthreads, const std::function<int(mg_reads*)>& sink) {
-  BamHeader hdr;
-  MG_TRY(bam_read_header(path, &hdr));
-  const int32_t n_ref = (int32_t)hdr.names.size();
+// *thinned (may be null) is set before the first call of `consume`: the consumer may read it through a captured reference.
+// The device inflater running out of memory (MG_ERR_NOMEM) before it handed over its first piece is no error: `consume` has not
+// been called, so whatever state it keeps is untouched, and the host readers take the file from its first byte.  That holds for
+// the compressed file's own buffer and for everything the inflater sets up behind it, for every entry point.
+static int stream_file(const char* path, const StreamPlan& plan, const Consumer& consume, bool* thinned = nullptr) {
+  bool thinned_here = false;
+  if (!thinned) thinned = &thinned_here;
+  *thinned = false;
+  uint64_t fsize = 0;
+  const int gfd = open_for_device_inflate(path, plan.offset, plan.length, &fsize);
+  if (gfd >= 0) {
+    bool started = false;
+    const int rc = inflate_file_pipeline(gfd, fsize, consume, &started);
+    close(gfd);
+    if (!(rc == MG_ERR_NOMEM && !started)) return rc;
+  }
   std::unique_ptr<Source> src;
   bool gz = false;
-  uint64_t gsize = 0;
-  int gfd = open_for_device_inflate(path, 0, 0, &gsize);
-  if (gfd >= 0) {  // (room for the compressed file on the device? as mg_bam_stream_file)
-    DevBuf probe;
-    if (probe.alloc(((gsize + 3) & ~3ull) + 64) != MG_OK) { close(gfd); gfd = -1; }
-  }
-  if (gfd < 0) MG_TRY(open_source(path, 0, 0, &chunk_bytes, &src, &gz));
-  const bool auto_threads = nthreads <= 0;
-  if (nthreads <= 0) nthreads = default_threads();
-  if (gz && src->parallel() && auto_threads) {  // BGZF: inflating is the work (as mg_sketch_stream_add_file)
-    const unsigned hw = std::thread::hardware_concurrency();
-    if (dbg("stream_threads") <= 0 && hw > (unsigned)nthreads) nthreads = (int)(hw > 32 ? 32 : hw);
-  }
-  uint64_t skip = hdr.bytes, done = hdr.bytes;  // done: the stream's bytes in front of this piece's records
-  Consumer consume = [&](const uint8_t* d_text, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
+  uint64_t chunk_bytes = plan.chunk_bytes;
+  MG_TRY(open_source(path, plan.offset, plan.length, &chunk_bytes, &src, &gz, plan.thin_kind, thinned));
+  return run_pipeline(*src, chunk_bytes, reader_threads(plan, gz && src->parallel(), *thinned), consume, nullptr);
+}
+
+// `inner` behind a BAM file's header (read by the caller with zlib: hdr_bytes of the inflated stream): its bytes are eaten from
+// the first piece(s), and inner sees the records only.
+static Consumer skip_bam_header(uint64_t hdr_bytes, const char* path, Consumer inner) {
+  return [skip = hdr_bytes, path, inner = std::move(inner)](const uint8_t* d_text, uint64_t nbytes, bool final, uint64_t* consumed) mutable -> int {
     const uint64_t off = skip < nbytes ? skip : nbytes;  // the header's bytes
     skip -= off;
     if (skip) {
       *consumed = nbytes;
       return final ? fail(MG_ERR_ARG, "%s: the BAM header runs past the end of the file", path) : MG_OK;
     }
+    uint64_t used = 0;
+    MG_TRY(inner(d_text + off, nbytes - off, final, &used));
+    *consumed = off + used;
+    return MG_OK;
+  };
+}
+
+// A BAM READS file (BGZF, or uncompressed) -> its reads, piece by piece: the header read here with zlib and stepped over, every
+// piece cut after its last complete record, its records unpacked on the device (mg_bam.hip: bam_reads_prefix_dev).  sink(reads)
+// owns each batch.  A break in the record chain: MG_ERR_ARG naming the file and the byte of the inflated stream.
+static int bam_reads_file(const char* path, uint64_t chunk_bytes, int nthreads, const std::function<int(mg_reads*)>& sink) {
+  BamHeader hdr;
+  MG_TRY(bam_read_header(path, &hdr));
+  const int32_t n_ref = (int32_t)hdr.names.size();
+  uint64_t done = hdr.bytes;  // the stream's bytes in front of this piece's records
+  // (BGZF on every core, as the reads text — but a caller's own number holds)
+  const StreamPlan plan{.chunk_bytes = chunk_bytes, .nthreads = nthreads, .bgzf_uses_all_cores = true};
+  const int rc = stream_file(path, plan, skip_bam_header(hdr.bytes, path, [&](const uint8_t* d_recs, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
     mg_reads* rd = nullptr;
-    uint64_t used = 0, at = 0;
-    const int rc = bam_reads_prefix_dev(d_text + off, nbytes - off, n_ref, final, &used, &rd, &at);
-    if (rc == MG_ERR_ARG) {
+    uint64_t at = 0;
+    const int prc = bam_reads_prefix_dev(d_recs, nbytes, n_ref, final, consumed, &rd, &at);
+    if (prc == MG_ERR_ARG) {
       const std::string why = mg_last_error();
       return fail(MG_ERR_ARG, "%s: corrupt or truncated BAM at byte %llu of the inflated stream (%s)", path,
                   (unsigned long long)(done + at), why.c_str());
     }
-    MG_TRY(rc);
-    *consumed = off + used;
-    done += used;
+    MG_TRY(prc);
+    done += *consumed;
     return sink(rd);
-  };
-  int rc = MG_OK;
-  if (gfd >= 0) {
-    rc = inflate_file_pipeline(gfd, gsize, consume, nullptr);
-    close(gfd);
-  } else {
-    rc = run_pipeline(*src, chunk_bytes, nthreads, consume, nullptr);
-  }
+  }));
   if (rc == MG_ERR_CAPACITY) {  // (a record longer than a piece's headroom — or a corrupt block_size that claims one)
     const std::string why = mg_last_error();
     return fail(MG_ERR_CAPACITY, "%s: %s", path, why.c_str());
   }
+  return rc;
+}
+
+// A batch of reads into the counting tables of the whole file; the batch is released.
+static int add_reads(mg_sketch_stream* ss, mg_reads* rd) {
+  const uint8_t* d_b = nullptr;
+  const uint64_t* d_o = nullptr;
+  int rc = mg_reads_device_ptrs(rd, &d_b, &d_o);
+  if (rc == MG_OK) rc = mg_sketch_stream_add_dev(ss, d_b, d_o, mg_reads_count(rd), mg_reads_nbases(rd));
+  mg_reads_free(rd);  // (stream-ordered: the hashing kernel queued above still reads it; the pool hands it out behind that)
   return rc;
 }
 
@@ -906,59 +959,18 @@ int mg_sketch_stream_add_file(mg_sketch_stream* ss, const char* path, int format
   if (format < 0 || format > 3) return fail(MG_ERR_ARG, "format must be 0 (fastq), 1 (single-line fasta), 2 (fasta) or 3 (bam)");
   if (format == 3) {
     if (offset || length) return fail(MG_ERR_ARG, "a byte range of a BAM file cannot be streamed");
-    return bam_reads_file(path, chunk_bytes, nthreads, [&](mg_reads* rd) -> int {
-      const uint8_t* d_b = nullptr;
-      const uint64_t* d_o = nullptr;
-      int rc = mg_reads_device_ptrs(rd, &d_b, &d_o);
-      if (rc == MG_OK) rc = mg_sketch_stream_add_dev(ss, d_b, d_o, mg_reads_count(rd), mg_reads_nbases(rd));
-      mg_reads_free(rd);  // (stream-ordered, as for text)
-      return rc;
-    });
+    return bam_reads_file(path, chunk_bytes, nthreads, [&](mg_reads* rd) -> int { return add_reads(ss, rd); });
   }
-  {
-    uint64_t fsize = 0;
-    const int gfd = open_for_device_inflate(path, offset, length, &fsize);
-    if (gfd >= 0) {
-      Consumer consume_gz = [&](const uint8_t* d_text, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
-        mg_reads* rd = nullptr;
-        MG_TRY(mg_reads_parse_prefix_dev(d_text, nbytes, format, final ? 1 : 0, consumed, &rd));
-        const uint8_t* d_b = nullptr;
-        const uint64_t* d_o = nullptr;
-        int rc = mg_reads_device_ptrs(rd, &d_b, &d_o);
-        if (rc == MG_OK) rc = mg_sketch_stream_add_dev(ss, d_b, d_o, mg_reads_count(rd), mg_reads_nbases(rd));
-        mg_reads_free(rd);
-        return rc;
-      };
-      bool started = false;
-      const int rc = inflate_file_pipeline(gfd, fsize, consume_gz, &started);
-      close(gfd);
-      if (!(rc == MG_ERR_NOMEM && !started)) return rc;
-      // (no room on the device for the compressed file after all, and nothing consumed yet: the host inflater takes it)
-    }
-  }
-  std::unique_ptr<Source> src;
-  bool gz = false;
+  // (BGZF: inflating is the work — every core the box has, whatever the caller asked for)
+  const StreamPlan plan{.offset = offset, .length = length, .chunk_bytes = chunk_bytes, .nthreads = nthreads,
+                        .thin_kind = format == 0 ? (int)ThinSource::kFastq : -1, .bgzf_uses_all_cores = true, .bgzf_overrides_caller = true};
   bool thinned = false;
-  const bool auto_threads = nthreads <= 0;
-  MG_TRY(open_source(path, offset, length, &chunk_bytes, &src, &gz, format == 0 ? (int)ThinSource::kFastq : -1, &thinned));
-  if (nthreads <= 0) nthreads = default_threads();
-  if (gz && src->parallel()) {  // BGZF: inflating is the work — every core the box has
-    unsigned hw = std::thread::hardware_concurrency();
-    if (dbg("stream_threads") <= 0 && hw > (unsigned)nthreads) nthreads = (int)(hw > 32 ? 32 : hw);
-  }
-  if (thinned && auto_threads) nthreads = thin_threads(nthreads);
-  const int dev_format = thinned ? 1 : format;  // (a thinned FASTQ piece is single-line FASTA: ">", the sequence line)
-  Consumer consume = [&](const uint8_t* d_text, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
+  return stream_file(path, plan, [&](const uint8_t* d_text, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
+    const int dev_format = thinned ? 1 : format;  // (a thinned FASTQ piece is single-line FASTA: ">", the sequence line)
     mg_reads* rd = nullptr;
     MG_TRY(mg_reads_parse_prefix_dev(d_text, nbytes, dev_format, final ? 1 : 0, consumed, &rd));
-    const uint8_t* d_b = nullptr;
-    const uint64_t* d_o = nullptr;
-    int rc = mg_reads_device_ptrs(rd, &d_b, &d_o);
-    if (rc == MG_OK) rc = mg_sketch_stream_add_dev(ss, d_b, d_o, mg_reads_count(rd), mg_reads_nbases(rd));
-    mg_reads_free(rd);  // (stream-ordered: the hashing kernel queued above still reads it; the pool hands it out behind that)
-    return rc;
-  };
-  return run_pipeline(*src, chunk_bytes, nthreads, consume, nullptr);
+    return add_reads(ss, rd);
+  }, &thinned);
 }
 
 // A whole BAM reads file -> one batch (the multi-rank path: rank 0 decodes, then shares the reads out)
@@ -1035,43 +1047,27 @@ int mg_sam_stream_file(const char* path, int paf, const mg_acc_index* ix, uint64
   *out = nullptr;
   if (err_kind) *err_kind = 0;
   if (err_line) *err_line = 0;
-  std::unique_ptr<Source> src;
-  bool gz = false;
+  // (a BGZF file's host readers stay at the eight of a plain file)
+  const StreamPlan plan{.offset = offset, .length = length, .chunk_bytes = chunk_bytes, .nthreads = nthreads,
+                        .thin_kind = paf ? -1 : (int)ThinSource::kSam, .bgzf_uses_all_cores = false};
   bool thinned = false;
-  const bool auto_threads = nthreads <= 0;
-  uint64_t gsize = 0;
-  int gfd = open_for_device_inflate(path, offset, length, &gsize);
-  if (gfd >= 0) {  // (room for the compressed file on the device? probed here, so that the host inflater can still take the file)
-    DevBuf probe;
-    if (probe.alloc(((gsize + 3) & ~3ull) + 64) != MG_OK) { close(gfd); gfd = -1; }
-  }
-  if (gfd < 0) MG_TRY(open_source(path, offset, length, &chunk_bytes, &src, &gz, paf ? -1 : (int)ThinSource::kSam, &thinned));
-  if (nthreads <= 0) nthreads = default_threads();
-  if (thinned && auto_threads) nthreads = thin_threads(nthreads);
   std::vector<std::unique_ptr<mg_sam_batch>> parts;
   std::string prev;
   uint64_t total = 0;
-  Consumer consume = [&](const uint8_t* d_text, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
+  MG_TRY(stream_file(path, plan, [&](const uint8_t* d_text, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
     mg_sam_batch* b = nullptr;
     MG_TRY(aln_tokenize_prefix_dev(d_text, nbytes, ix, prev.c_str(), paf != 0, final, consumed, &b, err_kind, err_line, thinned));
     prev = b->last_qname;
     total += b->nrecs;
     parts.emplace_back(b);
     return MG_OK;
-  };
-  if (gfd >= 0) {
-    const int rc = inflate_file_pipeline(gfd, gsize, consume, nullptr);
-    close(gfd);
-    MG_TRY(rc);
-  } else {
-    MG_TRY(run_pipeline(*src, chunk_bytes, nthreads, consume, nullptr));
-  }
+  }, &thinned));
   return concat_batches(parts, total, prev, out);
 }
 
-// BAM file (BGZF, or uncompressed) -> alignment records on the device: the SAME pipeline and the same inflaters as a `.sam.gz`
-// (the device's, or the host readers' when mg_inflate_config turned it off or the file does not fit), the header read here
-// with zlib and stepped over in the first piece(s), every piece cut after its last complete record (mg_bam.hip).
+// BAM file (BGZF, or uncompressed) -> alignment records on the device: the SAME pipeline and the same inflaters as a `.sam.gz`,
+// the header read here with zlib and stepped over in the first piece(s), every piece cut after its last complete record
+// (mg_bam.hip).
 int mg_bam_stream_file(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,
                        int* err_kind, uint64_t* err_rec) {
   MG_REQUIRE_READY();
@@ -1085,43 +1081,20 @@ int mg_bam_stream_file(const char* path, const mg_acc_index* ix, uint64_t chunk_
   DevBuf d_map;
   MG_TRY(d_map.alloc(map.size() * sizeof(int32_t)));
   MG_TRY(mg_memcpy_h2d(d_map.p, map.data(), map.size() * sizeof(int32_t)));
-  std::unique_ptr<Source> src;
-  bool gz = false;
-  uint64_t gsize = 0;
-  int gfd = open_for_device_inflate(path, 0, 0, &gsize);
-  if (gfd >= 0) {  // (room for the compressed file on the device? as mg_sam_stream_file)
-    DevBuf probe;
-    if (probe.alloc(((gsize + 3) & ~3ull) + 64) != MG_OK) { close(gfd); gfd = -1; }
-  }
-  if (gfd < 0) MG_TRY(open_source(path, 0, 0, &chunk_bytes, &src, &gz));
-  if (nthreads <= 0) nthreads = default_threads();
+  // (BGZF host readers as mg_sam_stream_file)
+  const StreamPlan plan{.chunk_bytes = chunk_bytes, .nthreads = nthreads, .bgzf_uses_all_cores = false};
   std::vector<std::unique_ptr<mg_sam_batch>> parts;
   std::string prev;
-  uint64_t total = 0, skip = hdr.bytes;
-  Consumer consume = [&](const uint8_t* d_text, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
-    const uint64_t off = skip < nbytes ? skip : nbytes;  // the header's bytes
-    skip -= off;
-    if (skip) {
-      *consumed = nbytes;
-      return final ? fail(MG_ERR_ARG, "%s: the BAM header runs past the end of the file", path) : MG_OK;
-    }
+  uint64_t total = 0;
+  MG_TRY(stream_file(path, plan, skip_bam_header(hdr.bytes, path, [&](const uint8_t* d_recs, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
     mg_sam_batch* b = nullptr;
-    uint64_t used = 0;
-    MG_TRY(bam_tokenize_prefix_dev(d_text + off, nbytes - off, d_map.as<int32_t>(), (int32_t)hdr.names.size(), prev.c_str(), final,
-                                   &used, &b, err_kind, err_rec));
-    *consumed = off + used;
+    MG_TRY(bam_tokenize_prefix_dev(d_recs, nbytes, d_map.as<int32_t>(), (int32_t)hdr.names.size(), prev.c_str(), final, consumed, &b,
+                                   err_kind, err_rec));
     prev = b->last_qname;
     total += b->nrecs;
     parts.emplace_back(b);
     return MG_OK;
-  };
-  if (gfd >= 0) {
-    const int rc = inflate_file_pipeline(gfd, gsize, consume, nullptr);
-    close(gfd);
-    MG_TRY(rc);
-  } else {
-    MG_TRY(run_pipeline(*src, chunk_bytes, nthreads, consume, nullptr));
-  }
+  })));
   return concat_batches(parts, total, prev, out);
 }
 

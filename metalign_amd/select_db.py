@@ -508,6 +508,13 @@ def expected_bases(path, kind):
     return int(size * (0.5 if kind == 'fastq' else 1.0)) + 1
 
 
+def _not_for_streaming(e, kind):
+    """This error of add_file means that the file does not suit the streaming pipeline, and the piece-wise path (whose host
+    parser decides) takes it: a record longer than a piece's headroom (capacity), or FASTA text the device parser refuses.
+    A malformed FASTQ record or a corrupt BAM is the caller's error, as on the whole-file path."""
+    return e.code == _hip.ERR_CAPACITY or (e.code == _hip.ERR_ARG and kind not in ('fastq', 'bam'))
+
+
 def stream_reads_file(hip, path, kind, ks, hmaxs, s, filts, offset=0, length=0):
     """The reads file -> read sketches of every k, streamed: reader threads fill page-locked chunks (plain files by
     positional reads in parallel, `.gz` inflated by zlib inside the library — BGZF blocks in parallel), chunk i + 1 goes up
@@ -526,9 +533,7 @@ def stream_reads_file(hip, path, kind, ks, hmaxs, s, filts, offset=0, length=0):
             try:
                 stream.add_file(path, fmt, offset=offset, length=length, chunk_bytes=chunk)
             except _hip.HipError as e:
-                # a record longer than a piece's headroom (capacity), or FASTA text the device parser refuses: not for
-                # this pipeline; a malformed FASTQ record is the caller's error, as on the whole-file path
-                if e.code == _hip.ERR_CAPACITY or (e.code == _hip.ERR_ARG and kind not in ('fastq', 'bam')):
+                if _not_for_streaming(e, kind):
                     return None
                 raise
             sks = stream.finish()
@@ -706,9 +711,7 @@ def _run_count_steps(args, hip, table, arrays, t_start):
             stream.add_file(args.reads, reads_format(kind), chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)))
             done = True
         except _hip.HipError as e:
-            # a record longer than a piece's headroom (capacity), or FASTA text the device parser refuses: the piece-wise path's
-            # host parser decides; a malformed FASTQ record or a corrupt BAM is the caller's error, as on the whole-file path
-            if not (e.code == _hip.ERR_CAPACITY or (e.code == _hip.ERR_ARG and kind not in ('fastq', 'bam'))):
+            if not _not_for_streaming(e, kind):
                 raise
             counts.reset()
         finally:
