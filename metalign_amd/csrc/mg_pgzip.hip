@@ -76,7 +76,7 @@ struct Huff {
   // bits 5..25 = offset of the sub-table
   std::vector<uint32_t> t;
   int pb = 0;
-  // lens[n] (0..15).  ok_incomplete_single: a code with exactly one symbol of length 1 is accepted (distance codes).
+  // lens[n] (0..15).  ok_incomplete_single: a code with exactly one symbol of length 1 is accepted (the codes of a block; not its code-length code).
   // Returns false for over-subscribed or incomplete codes.  *nused = symbols with a non-zero length.
   bool build(const uint8_t* lens, int n, int primary, bool ok_incomplete_single, int* nused) {
     int count[16] = {0};
@@ -186,7 +186,9 @@ bool read_dynamic_header(Bits& b, BlockCodes& bc, bool strict) {
   }
   if (lens[256] == 0) return false;  // no end-of-block symbol
   int nl = 0, nd = 0;
-  if (!bc.lit.build(lens, hlit, 11, false, &nl)) return false;
+  // (zlib, inflate_table: either code may be incomplete when its only code has one bit — for the literal/length code that is the
+  // end-of-block symbol alone, an empty block; libdeflate's decoder reads it too)
+  if (!bc.lit.build(lens, hlit, 11, true, &nl)) return false;
   if (!bc.dist.build(lens + hlit, hdist, 9, true, &nd)) return false;
   if (strict && nl < 2) return false;  // (a block of one repeated symbol: legal, never seen in text, common among false starts)
   return true;

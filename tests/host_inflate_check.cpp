@@ -2,8 +2,11 @@
 // whole members as bytes, jobs entered at block starts the finder reports (16-bit symbols resolved with the known window),
 // count-only / overflowing jobs, members and trailing garbage, stored and fixed blocks, damaged streams, CRC combination.
 // Prints "ok <checks>" or the first failure.  Test infrastructure (tests/test_inflate_core_host.py builds and runs it).
+// With a file name: the streams of that file instead (tests/test_inflate_foreign_host.py writes it with tests/deflate_writer.py: streams
+// zlib's compressor never makes, legal ones with their text and ones that must be refused).
 #include <zlib.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -109,14 +112,16 @@ static Result whole(const std::string& gz, std::string* out, std::vector<Event>*
   return res;
 }
 
-static void check_whole(const char* what, const std::string& text, const std::string& gz) {
+static void check_whole(const char* what, const std::string& text, const std::string& gz, size_t members = 1) {
   std::string got;
   std::vector<Event> ev;
   const Result r = whole(gz, &got, &ev);
   CHECK(r.status == ST_END, "%s: status %u", what, r.status);
   CHECK(got.size() == text.size() && got == text, "%s: %zu bytes against %zu", what, got.size(), text.size());
-  CHECK(ev.size() == 1 && ev[0].crc == (uint32_t)crc32(0, (const Bytef*)text.data(), (uInt)text.size()) && ev[0].isize == (uint32_t)text.size() &&
-            ev[0].out_pos == text.size(), "%s: trailer", what);
+  CHECK(ev.size() == members && ev.back().out_pos == text.size(), "%s: %zu members", what, ev.size());
+  for (size_t i = 0, a = 0; i < ev.size(); a = (size_t)ev[i++].out_pos)  // every member's trailer is that of its piece of the text
+    CHECK(ev[i].out_pos >= a && ev[i].crc == (uint32_t)crc32(0, (const Bytef*)text.data() + a, (uInt)(ev[i].out_pos - a)) && ev[i].isize == (uint32_t)(ev[i].out_pos - a),
+          "%s: trailer of member %zu", what, i);
   CHECK(r.end_bit == gz.size() * 8, "%s: end_bit", what);
   // count only, and a capacity that runs out: the same count, nothing written beyond the capacity
   const Result c = whole(gz, nullptr, nullptr, F_HEADER | F_MEMBER_START | F_COUNT_ONLY);
@@ -128,7 +133,10 @@ static void check_whole(const char* what, const std::string& text, const std::st
 }
 
 // jobs entered at every block start the finder reports in [from, to): 16-bit symbols, resolved with the true window
-static int check_entered(const char* what, const std::string& text, const std::string& gz, uint64_t step_bytes) {
+// strict: the finder's first pass (headers as encoders write them) or its second (the format's rules alone).  zlib_made: every block of the
+// stream is a dynamic one with a header as zlib writes it, so no true boundary may be passed over; otherwise a pass owes that only to the
+// boundaries in front of non-final dynamic blocks with complete codes, and the first pass only where the header's lists are trimmed.
+static int check_entered(const char* what, const std::string& text, const std::string& gz, uint64_t step_bytes, bool strict = true, bool zlib_made = true) {
   Words in(gz);
   HostExec ex;
   ex.sh = &g_sh;
@@ -173,16 +181,50 @@ static int check_entered(const char* what, const std::string& text, const std::s
       } else {
         CHECK(!probe_block_start(in.w.data(), in.w.size(), p), "%s: the strict probe accepts what the loose one refuses at bit %llu", what, (unsigned long long)p);
       }
-      if (!probe_block_start(in.w.data(), in.w.size(), p)) continue;
-      const bool heavy = validate_block_start(ex, g_sh, in.w.data(), in.nbytes, p);
-      CHECK(light_validate(in.w.data(), in.nbytes, p) == heavy, "%s: the two validators disagree at bit %llu (%d)", what, (unsigned long long)p, (int)heavy);
-      if (!heavy) continue;
+      if (!probe_block_start(in.w.data(), in.w.size(), p)) { if (strict) continue; }
+      else {
+        const bool heavy = validate_block_start(ex, g_sh, in.w.data(), in.nbytes, p);
+        CHECK(light_validate(in.w.data(), in.nbytes, p) == heavy, "%s: the two validators disagree at bit %llu (%d)", what, (unsigned long long)p, (int)heavy);
+        if (strict && !heavy) continue;
+      }
+      if (!strict && !(probe_block_start(in.w.data(), in.w.size(), p, false) && validate_block_start(ex, g_sh, in.w.data(), in.nbytes, p, false))) continue;
       found = p;
       break;
     }
     // every true boundary of a non-final dynamic block in the range must have been found no later than it stands
     size_t bi = 0;
     while (bi < bounds.size() && bounds[bi] < from) ++bi;
+    if (!zlib_made) {
+      const uint64_t scanned = found != ~0ull ? found : std::min<uint64_t>(from + step_bytes * 8, gz.size() * 8 > 64 ? gz.size() * 8 - 64 : 0);
+      // (what the second pass owes: a non-final dynamic block whose literal/length code is complete and whose distance code is complete or
+      // at most one code — the Kraft sums are taken here, from the lengths as the header gives them.  What the first pass owes: of those,
+      // the headers as encoders write them — none of the three length lists ends in a zero it could have left out; read off the header's
+      // bits and the lengths here, not asked of the finder)
+      auto bits_at = [&](uint64_t p, uint32_t n) {
+        const uint64_t w = p >> 5;
+        const uint64_t x = (uint64_t)in.w[w] | (w + 1 < in.w.size() ? (uint64_t)in.w[w + 1] << 32 : 0ull);
+        return (uint32_t)((x >> (p & 31u)) & ((1u << n) - 1u));
+      };
+      auto owed = [&](uint64_t b) {
+        if (bits_at(b, 3) != 4u) return false;
+        const uint32_t ncl = bits_at(b + 13, 4) + 4u;
+        if (strict && ncl > 4u && bits_at(b + 17 + 3 * (ncl - 1), 3) == 0u) return false;
+        BitReader br;
+        br.init(in.w.data(), (in.nbytes + 3) / 4, b);
+        br.refill();
+        br.drop(3);
+        uint32_t nlit = 0, ndist = 0, kl = 0, kd = 0, nd = 0;
+        if (read_dynamic_lengths(ex, g_sh, br, &nlit, &ndist)) return false;
+        for (uint32_t i = 0; i < nlit; ++i) kl += g_sh.cl[i] ? 32768u >> g_sh.cl[i] : 0u;
+        for (uint32_t i = nlit; i < nlit + ndist; ++i) { kd += g_sh.cl[i] ? 32768u >> g_sh.cl[i] : 0u; nd += g_sh.cl[i] != 0; }
+        if (strict && ((nlit > 257 && !g_sh.cl[nlit - 1]) || (ndist > 1 && !g_sh.cl[nlit + ndist - 1]))) return false;
+        return kl == 32768u && (kd == 32768u || nd == 0 || (nd == 1 && kd == 16384u));
+      };
+      for (size_t i = bi; i < bounds.size() && bounds[i] < scanned; ++i)
+        CHECK(!owed(bounds[i]), "%s: the finder's %s pass passed over the dynamic block at bit %llu", what, strict ? "first" : "second", (unsigned long long)bounds[i]);
+      bi = (size_t)(std::lower_bound(bounds.begin(), bounds.end(), found) - bounds.begin());
+      if (found == ~0ull || bi == bounds.size() || bounds[bi] != found) continue;  // nothing, or a false start: the chain's business
+    }
     if (found == ~0ull) continue;
     CHECK(bi < bounds.size() && bounds[bi] >= found, "%s: the finder skipped a boundary (%llu vs %llu)", what,
           (unsigned long long)(bi < bounds.size() ? bounds[bi] : 0), (unsigned long long)found);
@@ -190,10 +232,10 @@ static int check_entered(const char* what, const std::string& text, const std::s
     const uint64_t outpos = outs[bi];
     Job job{found, ~0ull, 0, sym.size(), 0, 0};
     Result res;
-    std::vector<Event> events(8);
+    std::vector<Event> events(64);
     uint32_t nev = 0;
     alignas(16) static uint16_t tail[32768];
-    run_job<HostExec, uint16_t>(ex, g_sh, in.w.data(), in.nbytes, true, job, 0, sym.data(), &res, events.data(), &nev, 8, tail);
+    run_job<HostExec, uint16_t>(ex, g_sh, in.w.data(), in.nbytes, true, job, 0, sym.data(), &res, events.data(), &nev, 64, tail);
     CHECK(res.status == ST_END, "%s: entered job status %u", what, res.status);
     {  // ... and by the lane decoder
       static LaneMem lmem;
@@ -201,7 +243,7 @@ static int check_entered(const char* what, const std::string& text, const std::s
       std::vector<uint16_t> sym2(sym.size());
       LaneDec<uint16_t> d;
       uint32_t nev2 = 0;
-      d.init(in.w.data(), in.nbytes, true, job, 0, sym2.data(), &lmem, &lscr, events.data(), &nev2, 8);
+      d.init(in.w.data(), in.nbytes, true, job, 0, sym2.data(), &lmem, &lscr, events.data(), &nev2, 64);
       while (d.state != LS_DONE) d.round();
       CHECK(d.status == res.status && d.outn == res.out_count && memcmp(sym.data(), sym2.data(), (size_t)res.out_count * 2) == 0, "%s: the lane decoder's symbols", what);
     }
@@ -251,7 +293,44 @@ static void check_entries() {
         "entries: %s", "long / empty");
 }
 
-int main() {
+// ---- a corpus file: per entry  u32 length of the name | name | u8 legal | u32 members | u64 length | gzip file | u64 length | its text ----
+static int run_corpus(const char* path) {
+  FILE* f = fopen(path, "rb");
+  if (!f) { printf("FAIL cannot open %s\n", path); return 1; }
+  auto rd = [&](void* p, size_t n) { return fread(p, 1, n, f) == n; };
+  auto rd_str = [&](std::string* s_, uint64_t n) { s_->resize((size_t)n); return n == 0 || rd(&(*s_)[0], (size_t)n); };
+  int legal = 0, refused = 0, first_pass = 0, second_pass = 0;
+  unsigned long long bytes = 0;
+  for (;;) {
+    uint32_t nname = 0, members = 0;
+    uint8_t ok = 0;
+    uint64_t ngz = 0, ntext = 0;
+    std::string name, gz, text;
+    if (!rd(&nname, 4)) break;
+    CHECK(rd_str(&name, nname) && rd(&ok, 1) && rd(&members, 4) && rd(&ngz, 8) && rd_str(&gz, ngz) && rd(&ntext, 8) && rd_str(&text, ntext), "%s: a cut corpus file", path);
+    const char* what = name.c_str();
+    if (!ok) {  // zlib refuses it: so do both decoders (whole() holds the lane decoder's status to the wavefront decoder's)
+      const Result r = whole(gz, nullptr, nullptr);
+      CHECK(r.status >= ST_ERR, "%s: must be refused, status %u after %llu bytes", what, r.status, (unsigned long long)r.out_count);
+      ++refused;
+      continue;
+    }
+    check_whole(what, text, gz, members);
+    // jobs at the starts the finder reports, by either of its passes, about a dozen places per stream
+    const uint64_t step = std::max<uint64_t>(16, gz.size() / 12);
+    first_pass += check_entered(what, text, gz, step, true, false);
+    second_pass += check_entered(what, text, gz, step, false, false);
+    ++legal;
+    bytes += text.size();
+  }
+  fclose(f);
+  printf("ok %d checks, %d legal streams, %d refused, %d jobs entered in the middle by the finder's first pass, %d by its second, %llu bytes\n", g_checks, legal, refused,
+         first_pass, second_pass, bytes);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1) return run_corpus(argv[1]);
   check_entries();
   const std::string fq = fastq(6000);  // ~1.9 MB
   std::string bin(300000, '\0');

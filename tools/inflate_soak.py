@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Random gzip streams through the device inflater (mg_inflate_dev) against zlib: texts, FASTQ-like records, binary noise, long runs,
 mixtures; levels 1-9, several members, Z_SYNC / Z_FULL flushes, Z_FIXED / Z_HUFFMAN_ONLY / Z_RLE strategies, small and large chunk / stage
-settings, both decoders.  python tools/inflate_soak.py [streams] [seed] [corrupt]
+settings, both decoders; one stream in four is not zlib's at all but assembled by tests/deflate_writer.py (random legal code lengths, header
+codings, distances up to 32768, block types, wrappers — what other encoders may write).  python tools/inflate_soak.py [streams] [seed] [corrupt]
 (corrupt: every stream damaged — bits flipped, cut — and zlib's verdict expected: an error, or the same text)."""
 import os
 import sys
@@ -10,7 +11,16 @@ import zlib
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+try:
+    import deflate_writer  # noqa: E402
+except ModuleNotFoundError as e:  # the tool without tests/deflate_writer.py beside it: zlib's streams alone, and main() says so
+    if e.name != "deflate_writer":  # (anything else — a module the assembler needs, an error in it — is an error)
+        raise
+    deflate_writer = None
 from metalign_amd import _hip  # noqa: E402
+
+FOREIGN = 0.25  # the share of streams that come from the assembler
 
 
 def payload(rng, n):
@@ -37,6 +47,10 @@ def payload(rng, n):
 
 
 def compress(rng, data):
+    """-> (gzip file, its text): zlib's compression of data, or (one time in four) a random stream of the assembler with a text of its own"""
+    if deflate_writer is not None and rng.random() < FOREIGN:
+        gz, text, _, _ = deflate_writer.random_gz(rng, max_tokens=int(rng.choice([1000, 20000])))
+        return gz, text
     out = b""
     nmem = int(rng.integers(1, 4))
     cuts = sorted(int(x) for x in rng.integers(0, len(data) + 1, size=nmem - 1))
@@ -52,7 +66,7 @@ def compress(rng, data):
             if rng.random() < 0.2:
                 out += c.flush(zlib.Z_SYNC_FLUSH if rng.random() < 0.5 else zlib.Z_FULL_FLUSH)
         out += c.flush()
-    return out
+    return out, data
 
 
 SIZES = ([0, 1, 100, 5000, 70_000, 400_000, 3_000_000, 12_000_000], [.02, .03, .1, .15, .2, .25, .2, .05])
@@ -64,7 +78,7 @@ def soak(hip, nstreams, seed, corrupt, sizes=SIZES):
     for i in range(nstreams):
         n = int(rng.choice(sizes[0], p=sizes[1]))
         data = payload(rng, n) if n else b""
-        gz = compress(rng, data)
+        gz, data = compress(rng, data)
         hip.inflate_config(chunk_bytes=int(rng.choice([4 << 10, 16 << 10, 32 << 10, 100_000])), stage_bytes=int(rng.choice([-1, -1, 300_000, 2 << 20])),
                            ratio=int(rng.choice([10, 10, 2, 40])), lane_jobs=0 if rng.random() < 0.2 else 1 << 40)
         if corrupt and len(gz) > 30:  # a damaged stream: zlib's verdict is the expected one (an error, or — a flipped header byte — the same text)
@@ -110,6 +124,8 @@ def main():
     nstreams = int(sys.argv[1]) if len(sys.argv) > 1 else 200
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     corrupt = len(sys.argv) > 3 and sys.argv[3] == "corrupt"
+    if deflate_writer is None:
+        print("tests/deflate_writer.py not found: no assembled streams, zlib's alone")
     total, refused = soak(_hip.Hip.get(0), nstreams, seed, corrupt)
     if corrupt:
         print("ok: %d damaged streams, %d refused by both, the rest read alike" % (nstreams, refused))
