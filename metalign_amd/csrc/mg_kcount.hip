@@ -162,6 +162,9 @@ constexpr uint32_t kKcListCap = MG_KC_LIST_CAP;  // closed runs a lane can hold 
 constexpr uint32_t kKcDirect = MG_KC_DIRECT;  // slots of a lane's list that the drain takes lane by lane; the rest are gathered (kc_drain)
 constexpr uint32_t kKcHitCap = 128;      // runs past the gate waiting for their look-up (hitq, hitl): it comes when 64 or more wait
 constexpr uint32_t kKcSlack = 8;         // dwords a k-mer taken at the end of the stream may read past it
+// (what sets it is kc_walk32's tail block: up to seven steps past the longest read's end, the next dword read eight steps ahead of its use
+// and a dword beside it — five dwords beyond a full stage; the general walk reaches four.  LDS reads, masked values: nothing to fault, but
+// below five the read-ahead would land in the next wavefront's stage for nothing.)
 
 // LDS of one wavefront (bytes), for a stage of sd dwords (sd a multiple of 64)
 struct KcLds {

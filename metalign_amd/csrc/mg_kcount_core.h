@@ -21,7 +21,8 @@
 // The sliding minimum is van Herk / Gil-Werman in registers: m-mers in blocks of w; a window that starts in block b and ends
 // in block b + 1 has min(suffix minimum of block b from its first m-mer on, prefix minimum of block b + 1 up to its last):
 // one v_min for the prefix, one for the combination, one per m-mer for the suffix minima after the block — no deque, no
-// branch, every index a compile-time constant (the block loop is unrolled, the block's keys live in w registers).
+// branch, every index a compile-time constant (the block loop is unrolled, the block's keys live in w registers).  (k with 32 or
+// 33 candidates: blocks of 32 whatever w is, aligned to the base stream's dwords — kc_walk32.)
 //
 // Host / device, one source: everything here is per-lane code without cross-lane operations; tests/host_kcount_check.cpp
 // compiles it with g++ (MG_HOST_CHECK) and holds it to the oracle where there is no GPU (tests/test_kcount_core_host.py).
@@ -378,9 +379,22 @@ MG_HD uint32_t kc_notbase16(const uint32_t v[4]) {
 //         2: no such base, ragged lengths.
 // fwd / inv: the staged tile; p0: stream position of this lane's first base; len: its read's length; maxlen: the longest of
 // the tile (wave-uniform: so are the loop bounds and the stream's refill points).
+//
+// Two walks compute this.  k with 32 or 33 candidates (k = 50, 51, 53, 55, ..., 63) take kc_walk32, whose blocks are 32 candidates
+// long and start at a multiple of 32 bases of the walk: where a step stands in the stream's dwords is then a compile-time
+// constant.  Every other k takes the general walk below, whose blocks are as long as the window (-DMG_KC_WALK33: every k does —
+// A/B builds, tools/kcount_variants.sh).
+#ifdef MG_KC_WALK33
+constexpr bool kKcAlignedBlocks = false;
+#else
+constexpr bool kKcAlignedBlocks = true;
+#endif
+constexpr bool kc_has_aligned_blocks(int k) { return kKcAlignedBlocks && (kc_cands(k) == 32 || kc_cands(k) == 33); }
+
+// the general walk: any k, blocks of W candidates from w0 on
 template <int K, int MODE, class Out>
-MG_HD uint32_t kc_walk(const MG_LDS uint32_t* fwd, const MG_LDS uint32_t* inv, uint32_t p0, uint32_t len, uint32_t maxlen, uint32_t w0,
-                       Out& out, uint32_t& cnt) {
+MG_HD uint32_t kc_walk_any(const MG_LDS uint32_t* fwd, const MG_LDS uint32_t* inv, uint32_t p0, uint32_t len, uint32_t maxlen, uint32_t w0,
+                           Out& out, uint32_t& cnt) {
   constexpr int M = kKcM, E = kc_flank(K), W = kc_cands(K);  // (candidate j: bases j + E .. j + E + 14 of the read; window i has j = i .. i + W - 1)
   constexpr uint32_t kCap = Out::kCap;
   static_assert(K >= kKcMinK && K <= kKcMaxK, "k out of range for the minimizer path");
@@ -397,6 +411,8 @@ MG_HD uint32_t kc_walk(const MG_LDS uint32_t* fwd, const MG_LDS uint32_t* inv, u
   if constexpr (MODE == 0) iw = kc_bits32(inv, p0 + (w0 & ~31u));
   uint32_t A[W];  // this block's keys; from the end of the block on, the block's suffix minima
   uint32_t P = kKcNone, Mprev = kKcNone;
+  // (kc_walk32 has a copy of this body and of the closing lines below — the key's bit layout and the event's must stay the same in both:
+  // change them together; one shared body means re-measuring every k's kernel)
   auto take = [&](uint32_t u) -> uint32_t {  // base u comes in; the word of the candidate that ends there (number u - 14)
     if ((u & 15u) == 0) word = kc_ext32(fwd, p0 + u);
     const uint32_t c = (word >> (30u - 2u * (u & 15u))) & 3u;
@@ -480,6 +496,133 @@ MG_HD uint32_t kc_walk(const MG_LDS uint32_t* fwd, const MG_LDS uint32_t* inv, u
   // a full list: everything up to its last event is recorded, what follows may not be
   const uint32_t safe = cnt >= kCap ? out.last_window(kCap - 1u) + 1u : walked;
   return out.wave_min(safe < walked ? safe : walked);
+}
+
+// The walk of the k with W = 32 or 33 candidates: blocks of B = 32 candidates whatever W is.  Van Herk / Gil-Werman needs blocks no
+// longer than the window and windows no longer than a block and one: a window of 33 that ends at element T of a block starts at
+// element T of the block before (min(S[T], P): S the suffix minima of that block, P the running prefix minimum with the new key
+// in); a window of 32 starts at element T + 1 (the general walk's rule).  With D = W - 32: the first window (`base`) is closed
+// before the blocks begin — by D candidates of its own and block 0, candidates base + D .. base + D + 31 — and step T of block
+// b >= 1 takes in candidate base + D + 32 b + T and closes window base + 32 (b - 1) + 1 + T.
+// `base` is a multiple of 32, so the base that step T takes in, u = base + 32 b + D + T + 14, has u & 31 = (D + T + 14) & 31
+// whatever the block: the shift that takes it out of the stream's dword is an immediate, the dword is renewed at two fixed steps
+// of a block — read from LDS kKcAhead steps before — and a candidate's number, an event's info word and
+// the lane's end compare are the block's scalar plus a literal: a block is straight-line code without scalar branches (the tail
+// block keeps the general walk's look every eighth step).
+// A call that starts anew after a full list has a w0 that is no multiple of 32: it walks from w0 rounded DOWN, and the windows
+// before w0 have no minimizer — the end compare `i < nw` taken as `i - w0 < nw - w0`, unsigned: the same one compare (MODE 1,
+// whose usual block has none: every block of such a call is the tail block's code).  The lane's list then opens with the empty
+// run of those windows (an event without a key: skipped by the reader like any other), every window from w0 on is in exactly one
+// event as before, and what is walked twice is at most 31 steps of a call that primes k - 1 bases anyway.
+constexpr int kKcAhead = 8;  // steps between the LDS read of the stream's next dword and its first use
+template <int K, int MODE, class Out>
+MG_HD uint32_t kc_walk32(const MG_LDS uint32_t* fwd, const MG_LDS uint32_t* inv, uint32_t p0, uint32_t len, uint32_t maxlen, uint32_t w0,
+                         Out& out, uint32_t& cnt) {
+  constexpr int M = kKcM, E = kc_flank(K), W = kc_cands(K), B = 32, D = W - B;
+  constexpr uint32_t kCap = Out::kCap;
+  constexpr uint32_t kXor = (kKcXor << 2) & ~kKcPos;  // (take: the relabelling of the bases, above a candidate's number)
+  static_assert(D == 0 || D == 1, "blocks of 32 serve windows of 32 or 33 candidates");
+  maxlen = MG_UNIFORM(maxlen);
+  w0 = MG_UNIFORM(w0);
+  if (maxlen < (uint32_t)K) return 0u;  // (uniform) no window in the whole tile
+  const uint32_t nw = len >= (uint32_t)K ? len - (uint32_t)K + 1u : 0u;
+  const uint32_t nwmax = maxlen - (uint32_t)K + 1u;  // windows of the longest read
+  if (w0 >= nwmax) return nwmax;
+  const uint32_t nmers = nwmax + (uint32_t)(W - 1);  // ... and its m-mers
+  const uint32_t base = w0 & ~31u;
+  const bool masked = base != w0;  // (uniform) windows base .. w0 - 1 are walked and have no minimizer
+  const uint32_t nwl = nw > w0 ? nw - w0 : 0u;  // window i is this lane's to record when i - w0 < nwl
+  uint32_t f = 0, r = 0, vrun = 0;
+  p0 += (uint32_t)E;  // (base u of the walk is base u + E of the read)
+  // sixteen bases from base 16 q of the walk on (a lane's dwords straddle the stream's by the same amount all along)
+  const uint32_t d0 = p0 >> 4, sh = (p0 & 15u) << 1;
+  // (the two dwords are READ kKcAhead steps before they are used and SHIFTED where they are used: with the shift at the read the
+  // compiler kept it there, and a wait for LDS five instructions behind the read)
+  uint32_t word = 0, na = fwd[d0 + (base >> 4)], nb = fwd[d0 + (base >> 4) + 1u], iw = 0;
+  // base u comes in, PH = u & 31; kj: the relabelling | the number of the candidate that ends there; its word (kc_walk_any: take)
+  // (a COPY of kc_walk_any's per-base body, as are the closing lines after the loop: change them together)
+  auto take = [&]<int PH>(uint32_t u, uint32_t kj) -> uint32_t {
+    if constexpr ((PH & 15) == 0) word = (uint32_t)(((((uint64_t)na) << 32 | nb) << sh) >> 32);
+    if constexpr ((PH & 15) == 16 - kKcAhead) { na = fwd[d0 + (u >> 4) + 1u]; nb = fwd[d0 + (u >> 4) + 2u]; }
+    const uint32_t c = (word >> (30 - 2 * (PH & 15))) & 3u;
+    f = (f << 2) | (c << 2);
+#ifdef MG_HOST_CHECK
+    r = (r >> 2) | ((c ^ 3u) << 30);
+#else
+    r = __builtin_amdgcn_alignbit(c ^ 3u, r, 2);
+#endif
+    const uint32_t ct = f < r ? f : r;
+    uint32_t key = (ct & ~kKcPos) ^ kj;
+    if constexpr (MODE == 0) {
+      if constexpr (PH == 0) iw = kc_bits32(inv, p0 + u);
+      const uint32_t bad = (iw >> (31 - PH)) & 1u;
+      vrun = bad ? 0u : vrun + 1u;
+      key = vrun >= (uint32_t)M ? key : kKcNone;
+    }
+    return key;
+  };
+  [&]<int... T>(std::integer_sequence<int, T...>) {
+    ((void)take.template operator()<T>(base + (uint32_t)T, 0u), ...);
+  }(std::make_integer_sequence<int, M - 1>{});
+  uint32_t A[B];  // this block's keys; from the end of the block on, the block's suffix minima
+  uint32_t P = kKcNone, Mprev = kKcNone;
+  if constexpr (D == 1) Mprev = take.template operator()<M - 1>(base + (uint32_t)(M - 1), kXor + base);
+  // block 0: with the D candidates before it, the first window — it opens the first run
+  [&]<int... T>(std::integer_sequence<int, T...>) {
+    ((A[T] = take.template operator()<(D + T + M - 1) & 31>(base + (uint32_t)(D + T + M - 1), kXor + base + (uint32_t)(D + T)),
+      P = T == 0 ? A[T] : (A[T] < P ? A[T] : P)), ...);
+  }(std::make_integer_sequence<int, B>{});
+  Mprev = P < Mprev ? P : Mprev;
+  Mprev = base - w0 < nwl ? Mprev : kKcNone;
+  uint32_t walked = base + 1u;  // the first window not walked
+  for (uint32_t b = 1;; ++b) {
+    [&]<int... T>(std::integer_sequence<int, T...>) {
+      ((A[B - 2 - T] = A[B - 2 - T] < A[B - 1 - T] ? A[B - 2 - T] : A[B - 1 - T]), ...);  // A[30] .. A[1 - D]
+    }(std::make_integer_sequence<int, B - 2 + D>{});
+    const uint32_t i0 = base + 1u + (b - 1u) * (uint32_t)B;  // the window that step 0 closes ...
+    const uint32_t j0 = i0 + (uint32_t)(W - 1);              // ... with the block's first m-mer
+    if (j0 >= nmers || out.any_full(cnt)) break;
+    const bool tail = j0 + (uint32_t)B > nmers;
+    const uint32_t kb = kXor + j0, ib = ((i0 - 1u) & 1023u) << 10, vb = i0 - w0;  // the block's scalars: a step adds its number
+    auto step = [&]<int T, bool ENDS>() -> bool {
+      if constexpr (ENDS && T % 8 == 0 && T > 0) { if (j0 + (uint32_t)T >= nmers) return false; }
+      const uint32_t key = take.template operator()<(D + T + M - 1) & 31>(j0 + (uint32_t)(T + M - 1), kb + (uint32_t)T);
+      P = T == 0 ? key : (key < P ? key : P);
+      uint32_t Mc = P;
+      if constexpr (D == 1 || T != B - 1) { const uint32_t s = A[D == 1 ? T : (T + 1 < B ? T + 1 : 0)]; Mc = s < P ? s : P; }
+      if constexpr (MODE != 1 || ENDS) Mc = vb + (uint32_t)T < nwl ? Mc : kKcNone;
+      out.put(cnt, Mprev, ib + ((uint32_t)T << 10));
+      const bool ch = Mc != Mprev;
+      cnt += ch ? 1u : 0u;  // (add with carry, then the cap: no scalar AND of two compares in between)
+      cnt = cnt < kCap ? cnt : kCap;
+      Mprev = Mc;
+      A[T] = key;
+      walked = i0 + (uint32_t)T + 1u;
+      return true;
+    };
+    bool whole;
+    if (tail || (MODE == 1 && masked))
+      whole = [&]<int... T>(std::integer_sequence<int, T...>) { return (step.template operator()<T, true>() && ...); }(
+          std::make_integer_sequence<int, B>{});
+    else
+      whole = [&]<int... T>(std::integer_sequence<int, T...>) { return (step.template operator()<T, false>() && ...); }(
+          std::make_integer_sequence<int, B>{});
+    if (!whole) break;
+  }
+  walked = walked < nwmax ? walked : nwmax;  // (the tail block may have walked past the end)
+  // the run still open (nothing, if its key is kKcNone: a lane whose read has ended closed its last run where it ended)
+  out.put(cnt, Mprev, ((walked - 1u) & 1023u) << 10);
+  cnt += cnt < kCap ? 1u : 0u;
+  // a full list: everything up to its last event is recorded, what follows may not be
+  const uint32_t safe = cnt >= kCap ? out.last_window(kCap - 1u) + 1u : walked;
+  return out.wave_min(safe < walked ? safe : walked);
+}
+
+template <int K, int MODE, class Out>
+MG_HD uint32_t kc_walk(const MG_LDS uint32_t* fwd, const MG_LDS uint32_t* inv, uint32_t p0, uint32_t len, uint32_t maxlen, uint32_t w0,
+                       Out& out, uint32_t& cnt) {
+  if constexpr (kc_has_aligned_blocks(K)) return kc_walk32<K, MODE>(fwd, inv, p0, len, maxlen, w0, out, cnt);
+  else return kc_walk_any<K, MODE>(fwd, inv, p0, len, maxlen, w0, out, cnt);
 }
 
 // the windows of a read that hold no "not a base" bit (KMC's total of k-mers, for the tiles that have such bases)

@@ -4,7 +4,7 @@
 #   bash tools/kcount_variants.sh "w3:-DMG_KC_WAVES_PER_EU=3" "w4:-DMG_KC_WAVES_PER_EU=4"
 set -eu
 cd "$(dirname "$0")/../metalign_amd/csrc"
-OBJS="mg_core.o mg_sort.o mg_sketch.o mg_sketch_cmash.o mg_sketch_multi.o mg_contain.o mg_refpipe.o mg_pgzip.o mg_inflate.o mg_profile.o mg_ingest.o mg_stream.o"
+OBJS="mg_core.o mg_sort.o mg_sketch.o mg_sketch_cmash.o mg_sketch_multi.o mg_contain.o mg_refpipe.o mg_pgzip.o mg_inflate.o mg_profile.o mg_ingest.o mg_bam.o mg_stream.o"
 for spec in "$@"; do
   tag=${spec%%:*}; flags=${spec#*:}
   /opt/rocm/bin/hipcc -O3 -std=c++20 -fPIC -Wall -Wno-unused-function --offload-arch=gfx950 -DMG_KC_ONLY_K=51 $flags -c mg_kcount.hip -o /tmp/mg_kcount_$tag.o
