@@ -82,7 +82,8 @@ int mg_device_count(void);
  *   stay in the caches, the runs dropped); kc_gate_extra (mg_refdb_index_kmers: the gate has 2^this bits per k-mer; default 6);
  * kc_grid, k1_grid, kb_grid (test hooks, k3_grid's meaning for stages A and B: a value > 0 below the computed grid becomes the
  *   grid of k_count_kmers, of k_sketch_reads / k_sketch_reads_multi[_resident], of k_contain_pairs / k_match_pairs /
- *   k_refpipe_count — few workgroups, so that each loops over many tiles).
+ *   k_refpipe_count — few workgroups, so that each loops over many tiles); collate_defer (test hook: the collated stream calls
+ *   return their batch keyed and not yet collated).
  * Needs no device and no mg_init.  MG_ERR_ARG for a key that does not exist. */
 int mg_debug_set(const char* key, int64_t value);
 int64_t mg_debug_get(const char* key);
@@ -782,6 +783,32 @@ int mg_bam_stream_file(const char* path, const mg_acc_index* ix, uint64_t chunk_
  * caller carries the rest); final = 1: the bytes must end on a record's end. */
 int mg_bam_tokenize_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* refmap, uint32_t nref, const mg_acc_index* ix,
                         const char* prev_qname, int final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec);
+/* COLLATING BY READ (metalign_amd/csrc/mg_collate.hip; the definition is metalign_amd/collate.py: collated_lines).  Stage C closes a
+ * read when the QNAME changes, so a coordinate-sorted file has to be regrouped first: the reads in the order of their first
+ * retained line, inside a read by (mate-2 class: FLAG has 1 and 128 and not 64; not primary: FLAG & 0x900; file index), and the
+ * new-read bit set where the read changes.  Names are compared through a 128-bit key (both halves of MurmurHash3_x64_128 of the
+ * QNAME bytes, fixed seed: mg_collate_core.h), 16 bytes per record beside the batch until it is collated.
+ * The KEYED tokenisers are mg_sam_tokenize_dev / mg_paf_tokenize_dev (paf = 0 / 1) and mg_bam_tokenize_dev with a batch that
+ * carries those keys; one file gives the same keys as SAM text and as BAM. */
+int mg_sam_tokenize_keyed_dev(const uint8_t* d_text, uint64_t nbytes, int paf, const mg_acc_index* ix, const char* prev_qname,
+                              mg_sam_batch** out, int* err_kind, uint64_t* err_line);
+int mg_bam_tokenize_keyed_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* refmap, uint32_t nref, const mg_acc_index* ix,
+                              const char* prev_qname, int final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec);
+/* keys2[2 r], keys2[2 r + 1] = the two halves of record r's key.  MG_ERR_STATE for a batch without keys. */
+int mg_sam_batch_keys_download(const mg_sam_batch* b, uint64_t* keys2);
+/* Keys (u64[2 n], as above) and the records' FLAGs -> d_perm[t] (u64[n]) = the index of the record that comes t-th in collated order.
+ * Two records are the same read exactly when BOTH halves of their keys agree.  n = 0 and n = 1 are legal.  Synchronises. */
+int mg_collate_order_dev(const uint64_t* d_keys2, const mg_aln_rec* d_recs, uint64_t n, uint64_t* d_perm);
+/* A keyed batch collated in place: its records permuted, their new-read bits recomputed, its keys freed (a second call:
+ * MG_ERR_STATE); the device pointer changes (mg_sam_batch_device_ptr).  d_perm_or_null: u64[count] on the device for the
+ * permutation, or NULL.  MG_ERR_NOMEM when the sort's buffers do not fit: the batch is then as it was. */
+int mg_sam_batch_collate_dev(mg_sam_batch* b, uint64_t* d_perm_or_null);
+/* mg_sam_stream_file / mg_bam_stream_file with the whole file's batch collated before it is returned (same arguments, same error
+ * contract).  The knob collate_defer (mg_debug_set; a test hook) returns the batch keyed and NOT yet collated. */
+int mg_sam_stream_file_collated(const char* path, int paf, const mg_acc_index* ix, uint64_t offset, uint64_t length,
+                                uint64_t chunk_bytes, int nthreads, mg_sam_batch** out, int* err_kind, uint64_t* err_line);
+int mg_bam_stream_file_collated(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,
+                                int* err_kind, uint64_t* err_rec);
 uint64_t mg_sam_batch_count(const mg_sam_batch* b);
 const char* mg_sam_batch_last_qname(const mg_sam_batch* b);
 int mg_sam_batch_device_ptr(const mg_sam_batch* b, const mg_aln_rec** d_recs);

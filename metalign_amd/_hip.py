@@ -39,6 +39,8 @@ EXPORTS = [
     "mg_reads_download", "mg_reads_free",
     "mg_acc_index_build", "mg_acc_index_free", "mg_sam_tokenize_dev", "mg_sam_tokenize", "mg_paf_tokenize_dev", "mg_paf_tokenize", "mg_sam_stream_file", "mg_bam_stream_file", "mg_bam_tokenize_dev", "mg_sam_batch_count",
     "mg_sam_batch_last_qname", "mg_sam_batch_device_ptr", "mg_sam_batch_download", "mg_sam_batch_free",
+    "mg_sam_tokenize_keyed_dev", "mg_bam_tokenize_keyed_dev", "mg_sam_batch_keys_download", "mg_collate_order_dev", "mg_sam_batch_collate_dev",
+    "mg_sam_stream_file_collated", "mg_bam_stream_file_collated",
     "mg_gunzip_open", "mg_gunzip_read", "mg_gunzip_close", "mg_zcat_files", "mg_stream_thin_file",
     "mg_inflate_dev", "mg_inflated_bytes", "mg_inflated_download", "mg_inflated_free", "mg_inflate_config", "mg_inflate_stats",
     "mg_sketch_genomes", "mg_sketch_genomes_prefix", "mg_db_upload", "mg_db_upload_sorted", "mg_db_ngenomes", "mg_db_max_hash", "mg_db_free",
@@ -884,6 +886,33 @@ class SamBatch:
         """QNAME of the last retained line ('' when there is none): what the next piece of the text is tokenised after."""
         return self.hip.lib.mg_sam_batch_last_qname(self.handle).decode("utf-8", "replace")
 
+    def download(self):
+        """The records, REC_DTYPE[count]."""
+        recs = np.zeros(self.count, dtype=REC_DTYPE)
+        if self.count:
+            self.hip._chk(self.hip.lib.mg_sam_batch_download(self.handle, _vp(recs.ctypes.data)))
+        return recs
+
+    def keys(self):
+        """A keyed batch's QNAME keys, uint64[count, 2] = (lo, hi) (mg_sam_batch_keys_download)."""
+        k = np.zeros((self.count, 2), dtype=np.uint64)
+        self.hip._chk(self.hip.lib.mg_sam_batch_keys_download(self.handle, _vp(k.ctypes.data)))
+        return k
+
+    def collate(self, want_perm=False):
+        """A keyed batch regrouped by read in place, its keys freed (mg_sam_batch_collate_dev; metalign_amd/collate.py is the
+        definition).  want_perm: -> uint64[count], the index of the record that now comes t-th."""
+        d_perm = self.hip.array(np.zeros(max(self.count, 1), dtype=np.uint64)) if want_perm else None
+        try:
+            self.hip._chk(self.hip.lib.mg_sam_batch_collate_dev(self.handle, _vp(d_perm.ptr if want_perm else None)))
+            p = _vp()
+            self.hip._chk(self.hip.lib.mg_sam_batch_device_ptr(self.handle, ctypes.byref(p)))
+            self.ptr = p.value or 0
+            return d_perm.download()[:self.count] if want_perm else None
+        finally:
+            if d_perm is not None:
+                d_perm.free()
+
     def free(self):
         if self.handle:
             self.hip.lib.mg_sam_batch_free(self.handle)
@@ -1304,13 +1333,42 @@ class Hip:
         self._chk(rc)
         return SamBatch(self, h)
 
-    def sam_stream_file(self, path, acc_index, paf=False, offset=0, length=0, chunk_bytes=0, nthreads=0):
+    def sam_tokenize_keyed_dev(self, d_text, nbytes, acc_index, prev_qname="", paf=False):
+        """sam_tokenize_dev_batch with a batch that carries the QNAME keys a collation reads (mg_sam_tokenize_keyed_dev)."""
+        h = _vp()
+        kind, line = ctypes.c_int(0), ctypes.c_uint64(0)
+        rc = self.lib.mg_sam_tokenize_keyed_dev(_vp(d_text), ctypes.c_uint64(nbytes), ctypes.c_int(1 if paf else 0), acc_index.handle,
+                                                ctypes.c_char_p(prev_qname.encode()), ctypes.byref(h), ctypes.byref(kind), ctypes.byref(line))
+        if rc != 0 and kind.value:
+            raise SamParseError(kind.value, line.value)
+        self._chk(rc)
+        return SamBatch(self, h)
+
+    def collate_order(self, keys2, recs):
+        """mg_collate_order_dev on host arrays: keys2 uint64[n, 2] (lo, hi), recs REC_DTYPE[n] -> the permutation uint64[n]."""
+        keys2 = np.ascontiguousarray(keys2, dtype=np.uint64).reshape(-1, 2)
+        recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
+        n = len(recs)
+        assert len(keys2) == n
+        d_k = self.array(keys2.reshape(-1).view(np.uint8) if n else np.zeros(16, np.uint8))
+        d_r = self.array(recs.view(np.uint8) if n else np.zeros(16, np.uint8))
+        d_p = self.array(np.zeros(max(n, 1), dtype=np.uint64))
+        try:
+            self._chk(self.lib.mg_collate_order_dev(_vp(d_k.ptr), _vp(d_r.ptr), ctypes.c_uint64(n), _vp(d_p.ptr)))
+            return d_p.download()[:n]
+        finally:
+            d_k.free()
+            d_r.free()
+            d_p.free()
+
+    def sam_stream_file(self, path, acc_index, paf=False, offset=0, length=0, chunk_bytes=0, nthreads=0, collate=False):
         """The alignment file (SAM; paf=True: PAF; plain, gzip or BGZF) -> SamBatch, streamed through page-locked chunks
         inside the library (mg_sam_stream_file): the file read, the upload and the tokeniser overlap, and the text never
         exists as a host array.  SamParseError for a line the reference cannot parse."""
         h = _vp()
         kind, line = ctypes.c_int(0), ctypes.c_uint64(0)
-        rc = self.lib.mg_sam_stream_file(os.fsencode(path), ctypes.c_int(1 if paf else 0), acc_index.handle,
+        fn = self.lib.mg_sam_stream_file_collated if collate else self.lib.mg_sam_stream_file  # (collate: regrouped by read)
+        rc = fn(os.fsencode(path), ctypes.c_int(1 if paf else 0), acc_index.handle,
                                          ctypes.c_uint64(int(offset)), ctypes.c_uint64(int(length)), ctypes.c_uint64(int(chunk_bytes)),
                                          ctypes.c_int(int(nthreads)), ctypes.byref(h), ctypes.byref(kind), ctypes.byref(line))
         if rc != 0 and kind.value:
@@ -1318,26 +1376,28 @@ class Hip:
         self._chk(rc)
         return SamBatch(self, h)
 
-    def bam_stream_file(self, path, acc_index, chunk_bytes=0, nthreads=0):
+    def bam_stream_file(self, path, acc_index, chunk_bytes=0, nthreads=0, collate=False):
         """A BAM file -> SamBatch: the records its SAM rendering gives through sam_stream_file (mg_bam_stream_file).  SamParseError
         for a record whose rendering the reference cannot parse, that the device does not decide (kind 6) or that is not a BAM
         record the package takes (kind 7); `line` is the record's number within its piece."""
         h = _vp()
         kind, rec = ctypes.c_int(0), ctypes.c_uint64(0)
-        rc = self.lib.mg_bam_stream_file(os.fsencode(path), acc_index.handle, ctypes.c_uint64(int(chunk_bytes)), ctypes.c_int(int(nthreads)),
+        fn = self.lib.mg_bam_stream_file_collated if collate else self.lib.mg_bam_stream_file  # (collate: regrouped by read)
+        rc = fn(os.fsencode(path), acc_index.handle, ctypes.c_uint64(int(chunk_bytes)), ctypes.c_int(int(nthreads)),
                                          ctypes.byref(h), ctypes.byref(kind), ctypes.byref(rec))
         if rc != 0 and kind.value:
             raise SamParseError(kind.value, rec.value)
         self._chk(rc)
         return SamBatch(self, h)
 
-    def bam_tokenize_dev(self, d_bytes, nbytes, refmap, acc_index, prev_qname="", final=True):
+    def bam_tokenize_dev(self, d_bytes, nbytes, refmap, acc_index, prev_qname="", final=True, keyed=False):
         """BAM record bytes resident in HBM (behind the header) -> (SamBatch, consumed) (mg_bam_tokenize_dev); refmap: the accession row
         of every header reference (-1: none, -2: not one SAM field).  SamParseError as bam_stream_file."""
         rm = np.ascontiguousarray(refmap, dtype=np.int32)
         h = _vp()
         kind, rec, used = ctypes.c_int(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
-        rc = self.lib.mg_bam_tokenize_dev(_vp(d_bytes), ctypes.c_uint64(nbytes), _np(rm if rm.size else np.zeros(1, np.int32), ctypes.c_int32),
+        fn = self.lib.mg_bam_tokenize_keyed_dev if keyed else self.lib.mg_bam_tokenize_dev  # (keyed: the batch carries QNAME keys)
+        rc = fn(_vp(d_bytes), ctypes.c_uint64(nbytes), _np(rm if rm.size else np.zeros(1, np.int32), ctypes.c_int32),
                                           ctypes.c_uint32(rm.size), acc_index.handle, ctypes.c_char_p(prev_qname.encode()),
                                           ctypes.c_int(1 if final else 0), ctypes.byref(used), ctypes.byref(h), ctypes.byref(kind),
                                           ctypes.byref(rec))

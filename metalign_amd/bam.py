@@ -219,15 +219,16 @@ def write_fastq(path, out_path, batch=1 << 12):
         out.write(b"".join(buf))
 
 
-def warn_about(path):
+def warn_about(path, collating=False):
     """The warnings a BAM input gets on stderr: a coordinate-sorted file (a read's alignments are not adjacent, so the result is
-    that of its SAM text, which breaks the same assumption), and a missing BGZF end-of-file block (accepted, as samtools does)."""
+    that of its SAM text, which breaks the same assumption) unless its records are being collated by read (`--collate`), and a
+    missing BGZF end-of-file block (accepted, as samtools does)."""
     rd = BamReader(path)
     rd.fh.close()
     for ln in rd.text.splitlines():
-        if ln.startswith("@HD") and "SO:coordinate" in ln.split("\t"):
-            print("Warning: %s is sorted by coordinate; a read's alignments are expected next to each other (sort by name)" % path,
-                  file=sys.stderr)
+        if not collating and ln.startswith("@HD") and "SO:coordinate" in ln.split("\t"):
+            print("Warning: %s is sorted by coordinate; a read's alignments are expected next to each other (sort by name)"
+                  ", or pass --collate auto to regroup them by read" % path, file=sys.stderr)
             break
     if _is_gzip(path) and not has_eof_block(path):
         print("Warning: %s has no BGZF end-of-file block (a truncated file?)" % path, file=sys.stderr)

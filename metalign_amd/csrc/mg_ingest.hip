@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "mg_collate_core.h"
 #include "mg_internal.h"
 
 namespace mg {
@@ -504,9 +505,12 @@ __global__ void k_sam_list(const uint32_t* __restrict__ retained, const uint64_t
 
 // record r = retained line ret_line[r]; new-read bit = QNAME differs from the previous retained line's
 // (the first one is compared with prev_qname, the QNAME carried over from the previous chunk; empty = none)
+// KEYED (the input of a collation, mg_collate.hip): also keys[2 r], keys[2 r + 1] = the QNAME's key (mg_collate_core.h) — the
+// one place where the SAM, PAF and BAM paths read a retained line's QNAME bytes, so one file gives the same keys as text and as BAM
+template <bool KEYED>
 __global__ void k_sam_emit(const uint8_t* __restrict__ text, const LineOut* __restrict__ lines,
                            const uint64_t* __restrict__ ret_line, uint64_t nret, const uint8_t* __restrict__ prev_qname,
-                           uint32_t prev_len, mg_aln_rec* __restrict__ recs) {
+                           uint32_t prev_len, mg_aln_rec* __restrict__ recs, uint64_t* __restrict__ keys) {
   uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (; r < nret; r += stride) {
@@ -520,6 +524,11 @@ __global__ void k_sam_emit(const uint8_t* __restrict__ text, const LineOut* __re
     mg_aln_rec rec = cur.rec;
     if (!same) rec.ref_new |= MG_REC_NEW_BIT;
     recs[r] = rec;
+    if constexpr (KEYED) {
+      uint64_t lo, hi;
+      mgc::qname_key(text, cur.qbeg, cur.qlen, &lo, &hi);
+      *reinterpret_cast<ulonglong2*>(keys + 2 * r) = make_ulonglong2(lo, hi);
+    }
   }
 }
 
@@ -823,7 +832,7 @@ __global__ void k_sam_last_qname(const uint8_t* __restrict__ text, const LineOut
 // the byte after the last newline (what follows is carried to the next piece by the caller, mg_stream.hip).
 int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg_acc_index* ix, const char* prev_qname,
                                 bool paf, bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_line,
-                                bool thin) {
+                                bool thin, bool keyed) {
   MG_REQUIRE_READY();
   if (!out || !ix) return fail(MG_ERR_ARG, "null argument");
   *out = nullptr;
@@ -839,8 +848,10 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
   uint64_t last_end = 0;
   MG_TRY(build_line_index(d_text, nbytes, &d_le, &nlines, &vlast, final, (!final && consumed) ? &last_end : nullptr));
   if (consumed) *consumed = final ? nbytes : 0;
+  sb->keyed = keyed;
   if (nlines == 0) {
     MG_TRY(sb->recs.alloc(16));
+    if (keyed) MG_TRY(sb->keys.alloc(16));
     *out = sb.release();
     return MG_OK;
   }
@@ -879,7 +890,7 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
       if (err_line) *err_line = h_err;
       return fail(MG_ERR_ARG, "%s line %llu: parse error kind %u", paf ? "PAF" : "SAM", h_err, kind);
     }
-    MG_TRY(aln_emit_retained(d_text, d_lines, d_ret, d_rank, nlines, nret, d_prev, (uint32_t)plen, sb.get()));
+    MG_TRY(aln_emit_retained(d_text, d_lines, d_ret, d_rank, nlines, nret, d_prev, (uint32_t)plen, sb.get(), keyed));
   }
   sb->nrecs = nret;
   *out = sb.release();
@@ -889,17 +900,23 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
 // The retained lines (d_ret[l] = 1, d_rank = its exclusive prefix, nret of them) -> sb->recs with the new-read bit, and
 // sb->last_qname.  The SAM / PAF tokeniser above and the BAM decoder (mg_bam.hip) end here.
 int mg::aln_emit_retained(const uint8_t* d_text, const LineOut* d_lines, const uint32_t* d_ret, const uint64_t* d_rank, uint64_t nlines,
-                          uint64_t nret, const uint8_t* d_prev, uint32_t plen, mg_sam_batch* sb) {
+                          uint64_t nret, const uint8_t* d_prev, uint32_t plen, mg_sam_batch* sb, bool keyed) {
   Context& c = ctx();
   hipStream_t st = c.stream;
   MG_TRY(sb->recs.alloc((nret + 1) * sizeof(mg_aln_rec)));
+  sb->keyed = keyed;
+  if (keyed) MG_TRY(sb->keys.alloc((nret + 1) * 2 * sizeof(uint64_t)));
   if (nret) {
     uint64_t* d_list = (uint64_t*)scratch("sam_list", nret * sizeof(uint64_t));
     if (!d_list) return MG_ERR_NOMEM;
     hipLaunchKernelGGL(k_sam_list, dim3(grid_for(nlines, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_ret, d_rank,
                        nlines, d_list);
-    hipLaunchKernelGGL(k_sam_emit, dim3(grid_for(nret, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_text, d_lines,
-                       d_list, nret, d_prev, plen, sb->recs.as<mg_aln_rec>());
+    if (keyed)
+      hipLaunchKernelGGL(k_sam_emit<true>, dim3(grid_for(nret, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_text, d_lines,
+                         d_list, nret, d_prev, plen, sb->recs.as<mg_aln_rec>(), sb->keys.as<uint64_t>());
+    else
+      hipLaunchKernelGGL(k_sam_emit<false>, dim3(grid_for(nret, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_text, d_lines,
+                         d_list, nret, d_prev, plen, sb->recs.as<mg_aln_rec>(), (uint64_t*)nullptr);
     MG_HIP(hipGetLastError());
     // QNAME of the last retained line, for the next chunk: its span and its first kQnameInline bytes in ONE round trip
     // (three dependent ones — line number, span, bytes — were a quarter of a streamed piece's host time)

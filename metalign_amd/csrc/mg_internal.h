@@ -213,6 +213,10 @@ int reduce_pairs(const uint64_t* d_keys, const uint32_t* d_vals, uint64_t n, uin
 int segmented_sort_keys(const uint64_t* d_in, uint64_t* d_out, uint64_t n, const uint64_t* d_offsets, uint64_t nseg);
 // Sort (key u64, value u32) pairs by key (all 64 bits); used once per table upload.
 int sort_pairs(const uint64_t* d_kin, uint64_t* d_kout, const uint32_t* d_vin, uint32_t* d_vout, uint64_t n);
+// Stable sort of (key u64, value u64) pairs by the key's bits [0, end_bit); used by the collation (mg_collate.hip).
+int sort_pairs_u64(const uint64_t* d_kin, uint64_t* d_kout, const uint64_t* d_vin, uint64_t* d_vout, uint64_t n, unsigned end_bit);
+// out[i] = max(in[0..i]); out may not alias in.
+int inclusive_max_u64(const uint64_t* d_in, uint64_t* d_out, uint64_t n);
 // Exclusive prefix sums; *h_total receives the grand total.
 int exclusive_sum_u32_to_u64(const uint32_t* d_in, uint64_t* d_out, uint64_t n, uint64_t* h_total);
 
@@ -312,6 +316,9 @@ struct mg_sam_batch {
   mg::DevBuf recs;
   uint64_t nrecs = 0;
   std::string last_qname;
+  // the keyed tokenisers (mg_collate.hip): u64[2 nrecs], record r's QNAME key (mg_collate_core.h: lo, hi) — until the batch is collated
+  mg::DevBuf keys;
+  bool keyed = false;
 };
 
 namespace mg {
@@ -324,7 +331,7 @@ struct LineOut {
   uint32_t retained;
 };
 int aln_emit_retained(const uint8_t* d_text, const LineOut* d_lines, const uint32_t* d_ret, const uint64_t* d_rank, uint64_t nlines,
-                      uint64_t nret, const uint8_t* d_prev, uint32_t plen, mg_sam_batch* sb);
+                      uint64_t nret, const uint8_t* d_prev, uint32_t plen, mg_sam_batch* sb, bool keyed = false);
 // BAM (mg_bam.hip): the header as zlib reads it from the file; a piece of the records behind it -> the batch, as
 // aln_tokenize_prefix_dev for text (d_refmap: int32[1 + n_ref], bam_refmap's); *consumed = the end of its last complete record.
 struct BamHeader {
@@ -335,14 +342,17 @@ struct BamHeader {
 int bam_read_header(const char* path, BamHeader* h);
 std::vector<int32_t> bam_refmap(const std::vector<std::string>& names, const mg_acc_index* ix);
 int bam_tokenize_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* d_refmap, int32_t n_ref, const char* prev_qname,
-                            bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec);
+                            bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec, bool keyed = false);
 // The reads of a piece of BAM records (`samtools fastq -F 0x900`, mg_bam_core.h) -> *out, as mg_reads_parse_prefix_dev for text;
 // a break in the chain: MG_ERR_ARG, *err_at = its byte in the piece.
 int bam_reads_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, int32_t n_ref, bool final, uint64_t* consumed, mg_reads** out,
                          uint64_t* err_at);
 // thin: the piece comes from the file reader's thinning (mg_stream.hip: a SEQ field is MG_THIN_MARK + its length in decimal).
 int aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg_acc_index* ix, const char* prev_qname, bool paf,
-                            bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_line, bool thin = false);
+                            bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_line, bool thin = false,
+                            bool keyed = false);
+// mg_collate.hip: a keyed batch -> its records regrouped by read (metalign_amd/collate.py is the definition), the keys freed.
+int collate_batch(mg_sam_batch* b, uint64_t* d_perm_or_null);
 }
 
 struct mg_filter {

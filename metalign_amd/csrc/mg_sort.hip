@@ -66,6 +66,29 @@ int sort_pairs(const uint64_t* d_kin, uint64_t* d_kout, const uint32_t* d_vin, u
   return MG_OK;
 }
 
+int sort_pairs_u64(const uint64_t* d_kin, uint64_t* d_kout, const uint64_t* d_vin, uint64_t* d_vout, uint64_t n, unsigned end_bit) {
+  if (n == 0) return MG_OK;
+  if (end_bit == 0 || end_bit > 64) end_bit = 64;
+  hipStream_t st = ctx().stream;
+  size_t tmp = 0;
+  MG_HIP(rocprim::radix_sort_pairs(nullptr, tmp, d_kin, d_kout, d_vin, d_vout, n, 0u, end_bit, st));
+  void* t = scratch("sort_tmp", tmp);
+  if (!t) return MG_ERR_NOMEM;
+  MG_HIP(rocprim::radix_sort_pairs(t, tmp, d_kin, d_kout, d_vin, d_vout, n, 0u, end_bit, st));
+  return MG_OK;
+}
+
+int inclusive_max_u64(const uint64_t* d_in, uint64_t* d_out, uint64_t n) {
+  if (n == 0) return MG_OK;
+  hipStream_t st = ctx().stream;
+  size_t tmp = 0;
+  MG_HIP(rocprim::inclusive_scan(nullptr, tmp, d_in, d_out, (size_t)n, rocprim::maximum<uint64_t>(), st));
+  void* t = scratch("scan_tmp", tmp);
+  if (!t) return MG_ERR_NOMEM;
+  MG_HIP(rocprim::inclusive_scan(t, tmp, d_in, d_out, (size_t)n, rocprim::maximum<uint64_t>(), st));
+  return MG_OK;
+}
+
 int rle_keys(const uint64_t* d_sorted, uint64_t n, uint64_t* d_unique, uint32_t* d_counts, uint64_t* d_runs) {
   hipStream_t st = ctx().stream;
   if (n == 0) { MG_HIP(hipMemsetAsync(d_runs, 0, sizeof(uint64_t), st)); return MG_OK; }

@@ -1013,20 +1013,26 @@ int mg_reads_from_bam_file(const char* path, uint64_t chunk_bytes, int nthreads,
   return MG_OK;
 }
 
-// The batches of a file's pieces -> one (a single piece's records are taken over as they are)
-static int concat_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uint64_t total, const std::string& prev, mg_sam_batch** out) {
+// The batches of a file's pieces -> one (a single piece's records are taken over as they are); keyed pieces: their keys likewise
+static int concat_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uint64_t total, const std::string& prev, bool keyed,
+                          mg_sam_batch** out) {
   std::unique_ptr<mg_sam_batch> all(new mg_sam_batch());
   all->last_qname = prev;
   all->nrecs = total;
+  all->keyed = keyed;
   if (parts.size() == 1) {
     all->recs = std::move(parts[0]->recs);
+    all->keys = std::move(parts[0]->keys);
   } else {
     MG_TRY(all->recs.alloc((total + 1) * sizeof(mg_aln_rec)));
+    if (keyed) MG_TRY(all->keys.alloc((total + 1) * 2 * sizeof(uint64_t)));
     uint64_t at = 0;
     hipStream_t st = ctx().stream;
     for (auto& p : parts) {
       if (p->nrecs)
         MG_HIP(hipMemcpyAsync(all->recs.as<mg_aln_rec>() + at, p->recs.p, p->nrecs * sizeof(mg_aln_rec), hipMemcpyDeviceToDevice, st));
+      if (p->nrecs && keyed)
+        MG_HIP(hipMemcpyAsync(all->keys.as<uint64_t>() + 2 * at, p->keys.p, p->nrecs * 2 * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
       at += p->nrecs;
     }
     MG_HIP(hipStreamSynchronize(st));
@@ -1035,13 +1041,28 @@ static int concat_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uin
   return MG_OK;
 }
 
+// ... and, for the collated entry points, regrouped by read (mg_collate.hip).  The knob collate_defer (a test hook) leaves the
+// batch as it was tokenised, keys and all, for the caller to look at and collate (mg_sam_batch_collate_dev).
+static int finish_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uint64_t total, const std::string& prev, bool collate,
+                          mg_sam_batch** out) {
+  mg_sam_batch* all = nullptr;
+  MG_TRY(concat_batches(parts, total, prev, collate, &all));
+  if (collate && !dbg("collate_defer")) {
+    parts.clear();  // (the pieces' buffers go back to the pool before the sort asks for its own)
+    const int rc = collate_batch(all, nullptr);
+    if (rc != MG_OK) { delete all; return rc; }
+  }
+  *out = all;
+  return MG_OK;
+}
+
 // SAM (paf = 0) or PAF text file -> alignment records on the device, through the same pipeline: every piece is cut at its
 // last newline, tokenised (mg_sam_tokenize_dev's rules; the previous retained QNAME carried from piece to piece so that
 // the new-read bit is the whole file's) and its records appended.  Replaces the per-line Python of map_and_process,
 // scripts/map_and_profile.py:201-217.  A line the reference cannot parse: MG_ERR_ARG with err_kind (the caller streams
 // the file through the host tokeniser, which raises what the reference raises).
-int mg_sam_stream_file(const char* path, int paf, const mg_acc_index* ix, uint64_t offset, uint64_t length,
-                       uint64_t chunk_bytes, int nthreads, mg_sam_batch** out, int* err_kind, uint64_t* err_line) {
+static int sam_stream_file_impl(const char* path, int paf, const mg_acc_index* ix, uint64_t offset, uint64_t length,
+                                uint64_t chunk_bytes, int nthreads, mg_sam_batch** out, int* err_kind, uint64_t* err_line, bool collate) {
   MG_REQUIRE_READY();
   if (!path || !ix || !out) return fail(MG_ERR_ARG, "null argument");
   *out = nullptr;
@@ -1056,20 +1077,30 @@ int mg_sam_stream_file(const char* path, int paf, const mg_acc_index* ix, uint64
   uint64_t total = 0;
   MG_TRY(stream_file(path, plan, [&](const uint8_t* d_text, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
     mg_sam_batch* b = nullptr;
-    MG_TRY(aln_tokenize_prefix_dev(d_text, nbytes, ix, prev.c_str(), paf != 0, final, consumed, &b, err_kind, err_line, thinned));
+    MG_TRY(aln_tokenize_prefix_dev(d_text, nbytes, ix, prev.c_str(), paf != 0, final, consumed, &b, err_kind, err_line, thinned, collate));
     prev = b->last_qname;
     total += b->nrecs;
     parts.emplace_back(b);
     return MG_OK;
   }, &thinned));
-  return concat_batches(parts, total, prev, out);
+  return finish_batches(parts, total, prev, collate, out);
+}
+
+int mg_sam_stream_file(const char* path, int paf, const mg_acc_index* ix, uint64_t offset, uint64_t length,
+                       uint64_t chunk_bytes, int nthreads, mg_sam_batch** out, int* err_kind, uint64_t* err_line) {
+  return sam_stream_file_impl(path, paf, ix, offset, length, chunk_bytes, nthreads, out, err_kind, err_line, false);
+}
+
+int mg_sam_stream_file_collated(const char* path, int paf, const mg_acc_index* ix, uint64_t offset, uint64_t length,
+                                uint64_t chunk_bytes, int nthreads, mg_sam_batch** out, int* err_kind, uint64_t* err_line) {
+  return sam_stream_file_impl(path, paf, ix, offset, length, chunk_bytes, nthreads, out, err_kind, err_line, true);
 }
 
 // BAM file (BGZF, or uncompressed) -> alignment records on the device: the SAME pipeline and the same inflaters as a `.sam.gz`,
 // the header read here with zlib and stepped over in the first piece(s), every piece cut after its last complete record
 // (mg_bam.hip).
-int mg_bam_stream_file(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,
-                       int* err_kind, uint64_t* err_rec) {
+static int bam_stream_file_impl(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,
+                                int* err_kind, uint64_t* err_rec, bool collate) {
   MG_REQUIRE_READY();
   if (!path || !ix || !out) return fail(MG_ERR_ARG, "null argument");
   *out = nullptr;
@@ -1089,13 +1120,23 @@ int mg_bam_stream_file(const char* path, const mg_acc_index* ix, uint64_t chunk_
   MG_TRY(stream_file(path, plan, skip_bam_header(hdr.bytes, path, [&](const uint8_t* d_recs, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
     mg_sam_batch* b = nullptr;
     MG_TRY(bam_tokenize_prefix_dev(d_recs, nbytes, d_map.as<int32_t>(), (int32_t)hdr.names.size(), prev.c_str(), final, consumed, &b,
-                                   err_kind, err_rec));
+                                   err_kind, err_rec, collate));
     prev = b->last_qname;
     total += b->nrecs;
     parts.emplace_back(b);
     return MG_OK;
   })));
-  return concat_batches(parts, total, prev, out);
+  return finish_batches(parts, total, prev, collate, out);
+}
+
+int mg_bam_stream_file(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,
+                       int* err_kind, uint64_t* err_rec) {
+  return bam_stream_file_impl(path, ix, chunk_bytes, nthreads, out, err_kind, err_rec, false);
+}
+
+int mg_bam_stream_file_collated(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,
+                                int* err_kind, uint64_t* err_rec) {
+  return bam_stream_file_impl(path, ix, chunk_bytes, nthreads, out, err_kind, err_rec, true);
 }
 
 // What the file readers hand to the device for a plain FASTQ (kind 0) or SAM (kind 1) file, written to out_path instead: the

@@ -29,7 +29,7 @@ import time
 
 import numpy as np
 
-from . import _hip, bam, cli
+from . import _hip, bam, cli, collate
 
 start = time.time()
 RANKS = ['superkingdom', 'phylum', 'class', 'order', 'family', 'genus', 'species', 'strain']
@@ -392,12 +392,14 @@ def assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=True):
     return taxids2abs, multimapped, {}
 
 
-def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _resident=False, _paf=False, _bam=False):
+def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _resident=False, _paf=False, _bam=False, _collate=False):
     """map_and_process for a plain SAM FILE, without the text or the records ever being host arrays: the file goes up
     through page-locked chunks (Hip.upload_file), is tokenised where it lands and stage C runs on the records the
     tokeniser left in HBM.  A line the reference cannot parse makes this return None: the caller then takes the
     streaming path, which reproduces the reference's exception for that line.  _bam: a BAM file (mg_bam_stream_file), None
-    likewise for a record the device does not decide — the caller then streams the file's SAM rendering (bam.sam_lines)."""
+    likewise for a record the device does not decide — the caller then streams the file's SAM rendering (bam.sam_lines).
+    _collate: the file's records regrouped by read on the device before stage C (mg_*_stream_file_collated; the definition is
+    collate.collated_lines, which the caller falls back to on None)."""
     acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
     _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
     hip = _hip.Hip.get()
@@ -412,11 +414,19 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
         free, _, pooled = hip.mem_info()
         streamed = os.environ.get('MG_NO_STREAM') != '1'
         # (streamed: only the 16-byte records — ~1/20 of the text — and three chunks of text are ever resident)
-        if (os.path.getsize(path) // 8 if streamed else 2 * os.path.getsize(path)) > free + pooled:
+        need = os.path.getsize(path) // 8 if streamed or _collate else 2 * os.path.getsize(path)
+        if _collate:
+            # beside the records, per record: 16 B of key, four 8 B sort arrays, ~16 B of the radix sort's own storage and the
+            # 16 B of the regrouped copy = 80 B; a record is at least ~50 B of BAM / compressed text, ~100 B of plain text
+            compressed = _bam or _is_gzip(path)
+            need += 80 * (os.path.getsize(path) // (50 if compressed else 100))
+        if need > free + pooled:
             return None
         try:
             if _bam:  # (a BAM is always streamed: ~16 B of records per ~60 B of the compressed file stay resident)
-                batch = hip.bam_stream_file(path, index, chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)))
+                batch = hip.bam_stream_file(path, index, chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)), collate=_collate)
+            elif _collate:  # (always streamed: the keys ride on the stream's batches)
+                batch = hip.sam_stream_file(path, index, paf=_paf, chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)), collate=True)
             elif not streamed:  # the whole text up, then one tokeniser call (round 2's path)
                 d_text, size = hip.upload_file(path)
                 batch = hip.sam_tokenize_dev_batch(d_text.ptr, size, index, '', paf=_paf)
@@ -831,6 +841,9 @@ def compute_abundances(args, infile, acc2info, tax2info):
     if args.input_type == 'sam' and not paf and bam.is_bam(infile):  # decided per file: a BAM is never SAM text
         instream.close()
         return _compute_abundances_bam(args, infile, acc2info, tax2info, on_device, seams_untouched)
+    if args.input_type == 'sam' and not paf and _wants_collation(args, lambda: _sam_header_lines(infile)):
+        instream.close()
+        return _compute_abundances_collated(args, infile, acc2info, tax2info, on_device, seams_untouched)
     if args.input_type == 'sam' and seams_untouched and not paf:
         from .select_db import dist_context
         ctx = dist_context()
@@ -854,20 +867,78 @@ def compute_abundances(args, infile, acc2info, tax2info):
     return _abundances_tail(args, taxids2abs, mm, tax2info, on_device)
 
 
+def _is_gzip(path):
+    with open(path, 'rb') as fh:
+        return fh.read(2) == b'\x1f\x8b'
+
+
+def _sam_file_lines(path):
+    """The lines (bytes) of a SAM file, plain or gzip / BGZF."""
+    import gzip
+    with (gzip.open(path, 'rb') if _is_gzip(path) else open(path, 'rb')) as fh:
+        yield from fh
+
+
+def _sam_header_lines(path):
+    """The leading '@' lines of a SAM file."""
+    out = []
+    for ln in _sam_file_lines(path):
+        if not ln.startswith(b'@'):
+            break
+        out.append(ln)
+    return out
+
+
+def _wants_collation(args, header_lines):
+    """--collate: never (the default) / always / auto = when the file's @HD line says SO:coordinate (header_lines() -> its header).
+    Only alignment FILES are collated (SAM text, BAM); an aligner's pipe and a PAF replay never are."""
+    mode = getattr(args, 'collate', 'never')  # (callers build Namespaces without it)
+    if mode == 'always':
+        return True
+    return mode == 'auto' and collate.header_says_coordinate(header_lines())
+
+
+def _compute_abundances_collated(args, infile, acc2info, tax2info, on_device, seams_untouched):
+    """A SAM file whose records are regrouped by read before stage C: on the device (map_and_process_file, _collate), or — for a
+    line the device does not decide, a file it refuses or keys that do not fit — through collate.collated_lines, the definition,
+    whose line stream goes to map_and_process and raises there what the reference raises.  A multi-GPU launch leaves a collated
+    input to rank 0, as a BAM (sharing keys between the ranks is not done)."""
+    if int(os.environ.get('RANK', '0')) != 0:
+        return None
+    done = None
+    if seams_untouched:
+        done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _collate=True)
+    if done is None:
+        done = map_and_process(args, collate.collated_lines(_sam_file_lines(infile)), acc2info, tax2info, _want_lists=False,
+                               _resident=on_device)
+    taxids2abs, mm, _ = done
+    return _abundances_tail(args, taxids2abs, mm, tax2info, on_device)
+
+
 def _compute_abundances_bam(args, infile, acc2info, tax2info, on_device, seams_untouched):
     """A BAM file -> clade abundances: its records decoded on the device (map_and_process_file), or — for a record the device does
     not decide, or a file it refuses — its SAM rendering through the SAM path, which raises what the reference raises on that line.
     A multi-GPU launch leaves a BAM to rank 0 (sharing one between the ranks is not done)."""
     if int(os.environ.get('RANK', '0')) != 0:
         return None
-    bam.warn_about(infile)
+    collating = _wants_collation(args, lambda: _bam_header_lines(infile))
+    bam.warn_about(infile, collating=collating)
     done = None
     if seams_untouched:
-        done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _bam=True)
+        done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _bam=True,
+                                    _collate=collating)
     if done is None:
-        done = map_and_process(args, bam.sam_lines(infile), acc2info, tax2info, _want_lists=False, _resident=on_device)
+        lines = bam.sam_lines(infile)
+        done = map_and_process(args, collate.collated_lines(lines) if collating else lines, acc2info, tax2info, _want_lists=False,
+                               _resident=on_device)
     taxids2abs, mm, _ = done
     return _abundances_tail(args, taxids2abs, mm, tax2info, on_device)
+
+
+def _bam_header_lines(path):
+    rd = bam.BamReader(path)
+    rd.fh.close()
+    return rd.text.splitlines()
 
 
 def _abundances_tail(args, taxids2abs, mm, tax2info, on_device):
