@@ -23,6 +23,8 @@ hashes and counts), all of them queued before the first is waited for.
 The compute calls go through an `engine` (HipEngine below: libmetalign_hip.so on this rank's GPU).  The
 CPU tests substitute an oracle-backed engine to check the choreography under gloo; product code never does.
 """
+import contextlib
+import gc
 import os
 
 import numpy as np
@@ -83,6 +85,63 @@ def compose_incoming(maps, rank):
     return x
 
 
+class WordsLayout:
+    """The int64 words a rank publishes in a pass's ONE all-gather: per SKETCHED k (number ki of K) a block of W + 4 — W slice
+    sizes (how many entries of its sketch go to each rank) | truncated | last hash | n | overflow (a counting table overflowed: the
+    block is stale) — then the tail: m0 | m1 (the shard's carried-state map) | groups (its reads)."""
+
+    def __init__(self, K, W):
+        self.K, self.W, self.tail, self.total = K, W, K * (W + 4), K * (W + 4) + 3
+
+    def sizes(self, ki):
+        return ki * (self.W + 4)
+
+    def truncated(self, ki):
+        return ki * (self.W + 4) + self.W
+
+    def last(self, ki):
+        return ki * (self.W + 4) + self.W + 1
+
+    def n(self, ki):
+        return ki * (self.W + 4) + self.W + 2
+
+    def overflow(self, ki):
+        return ki * (self.W + 4) + self.W + 3
+
+    def encode(self, eng, sks, bounds, tail):
+        """The host-side encoder: settled sketches cut at their k's bounds (eng.split_sketch) -> this rank's words.  Blocks without a
+        sketch stay zero (stage A by k-mer identity: sks is empty, nothing to cut into slices)."""
+        W, word = self.W, []
+        for ki, sk in enumerate(sks):
+            n = sk.size
+            cuts = [0] + eng.split_sketch(sk, bounds[ki][1:W]) + [n]
+            last = sk.last_hash  # two's complement into the int64 word
+            word += [cuts[q + 1] - cuts[q] for q in range(W)] + [int(sk.truncated), last - (1 << 64) if last >= (1 << 63) else last, n, 0]
+        return np.asarray(word + [0] * (self.tail - len(word)) + list(tail), dtype=np.int64)
+
+
+def red_layout(K, G, T, W):
+    """THE all-reduce's int64 buffer: [hits K x G | sizes K x G | count T | bases T | first_seen W x T (a row per rank) | sketch
+    sizes K | tot_rds, n_ambig] -> the offsets of sizes, count, bases, first_seen, sketch sizes, scalars, and the total."""
+    o_sizes, o_count = K * G, 2 * K * G
+    o_bases, o_first = o_count + T, o_count + 2 * T
+    o_qn = o_first + W * T
+    return o_sizes, o_count, o_bases, o_first, o_qn, o_qn + K, o_qn + K + 2
+
+
+@contextlib.contextmanager
+def _no_gc():
+    """Around a loop that keeps the GPU's queue full: a generation-2 collection in the middle of it is a 2-3 ms hole in that queue
+    (measured: one per ~160 passes); nothing cyclic is created there, reference counting frees what a pass drops."""
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_on:
+            gc.enable()
+
+
 class _CudaView:
     """Zero-copy view of a library-owned HBM range for torch (via __cuda_array_interface__)."""
 
@@ -125,15 +184,20 @@ class _KmerSketch:
 
 
 class HipEngine:
-    wg_per_cu_exchange = 3  # the hashing kernel's workgroups per CU beside the exchange chain (x_begin)
-
     """Compute side of one rank: device-resident inputs + calls into libmetalign_hip.so."""
+
+    wg_per_cu_exchange = 3  # the hashing kernel's workgroups per CU beside the exchange chain (x_begin)
 
     def __init__(self, hip, torch_mod=None):
         self.hip = hip
         self.torch = torch_mod  # None in single-process mode: results are returned as numpy arrays
         self.keep = []
         self.filters = []  # one membership pre-filter per k (set_filter), None = unfiltered
+        # what a job says before it loads (ShardJob.load), and what load() makes of it
+        self.match_kmer, self.count_share, self.mark_exchange = False, None, None
+        self.reftable, self.kmer, self.kmer_count_sharded = None, False, False
+        self._xturn = 1  # (x_front)
+        self._pool, self._xbounds = [], None  # result sets (_result_set), grown as passes ask for them; x_setup's bounds
 
     # ---- inputs ----
     def load(self, rbases, roffsets, recs, has_lookahead, ref2tax, ntax, tables, reftable=None):
@@ -159,20 +223,14 @@ class HipEngine:
             self.nk = len(tables)
         self.nsk = len(self.tables)  # k the reads are sketched at (the reference pipeline: the largest only)
         self.ngen_local = self.tables[0].ngenomes
-        g = self.gpad = max(self.ngen_local, 1)
-        # per k: [hits g | sizes g], all k in one buffer: one read-back
-        self.d_hs = hip.empty(2 * g * self.nk, np.uint32)
-        # [count T | bases T | first_seen T | scalars 2]
-        self.d_acc = hip.empty(3 * ntax + 2, np.uint64)
-        # page-locked landing buffers: a step queues both read-backs behind its kernels and syncs once
-        self.h_hs = hip.pinned(2 * g * self.nk, np.uint32)
-        self.h_acc = hip.pinned(3 * ntax + 2, np.uint64)
+        self.gpad = max(self.ngen_local, 1)
+        self._pool, self._xbounds = [], None  # (sized for THIS batch and table)
         self.filters += [None] * (self.nsk - len(self.filters))
         # stage A by k-mer identity (ShardJob(match="kmer")): the counters of the passes in flight, handed out and taken back
-        self.kmer = reftable is not None and bool(getattr(self, "match_kmer", False))
+        self.kmer = reftable is not None and bool(self.match_kmer)
         self._kc_free = []
         # (several ranks, each with the whole table: a rank streams its share of the count lists, the columns of k < k_max are summed)
-        share = getattr(self, "count_share", None)
+        share = self.count_share
         self.kmer_count_sharded = bool(self.kmer and share and share[1] > 1)
         if reftable is not None and hasattr(reftable, "set_count_share"):
             reftable.set_count_share(*(share if self.kmer_count_sharded else (0, 1)))  # (the handle remembers: a job says it every time)
@@ -285,7 +343,7 @@ class HipEngine:
     def sketch_local_async(self, ks, hmaxs, s):
         """The read sketches for every k, queued without a host sync (one fused launch when the library has the k set).
         match = "kmer": the reads' k_max-mers counted against the table's by identity instead (one launch, no sync)."""
-        if getattr(self, "kmer", False):
+        if self.kmer:
             # (a set of counters comes zeroed: when it was made, or when it was handed back — the one handed back longest ago first)
             kc = self._kc_free.pop(0) if self._kc_free else self.reftable.kmer_counts()
             kc.add_dev(self.d_rb.ptr, self.d_ro.ptr, self.nreads, int(self.d_rb.count))
@@ -343,9 +401,9 @@ class HipEngine:
         """Stage B of every k: one launch of each kernel for all of them (mg_containment_multi_dev; at most four k per call).
         The reference pipeline: the one sketch of the largest k against the table's pairs and count lists
         (mg_refpipe_containment_dev), a column per k."""
-        if getattr(self, "reftable", None) is not None:
+        if self.reftable is not None:
             ptrs = [self._hs_ptrs(base_ptr, ki) for ki in range(self.nk)]
-            hook = getattr(self, "mark_exchange", None)
+            hook = self.mark_exchange
             if isinstance(sks[0], _KmerSketch):
                 # (a rank of a multi-GPU job holds the whole table, and its counters the whole sample's sums by now: every rank
                 # computes every column, ShardJob._fill_reduce lets rank 0's through)
@@ -375,8 +433,13 @@ class HipEngine:
 
     def _stage_b_again(self, sks, ki, ci, base_ptr):
         """Stage B of sketch number ki once more (its counting table overflowed and it was rebuilt at resolution)."""
+        if self.reftable is not None and self.mark_exchange is not None:
+            # (this stage B contains a collective — the prefix bitmaps — that one rank alone cannot repeat: the sketches of such a job are
+            # settled in the phase that queues them — merge_sketches, x_merge — so a rebuilt one cannot turn up here; if it ever does,
+            # the columns would be stale)
+            raise RuntimeError("a reference-pipeline sketch was rebuilt after its stage B had run: x_merge must settle it")
         self.hip.sync()
-        if getattr(self, "reftable", None) is not None:
+        if self.reftable is not None:
             self._stage_b(sks, ci, base_ptr)
         else:
             self.hip.containment_dev(sks[ki], self.tables[ki], ci, *self._hs_ptrs(base_ptr, ki))
@@ -387,44 +450,9 @@ class HipEngine:
         hs = np.asarray(hs).reshape(self.nk, 2, g)
         return hs[:, 0, :G].copy(), hs[:, 1, :G].copy()
 
-    def containment(self, sks, ci):
-        """-> (hits[K][G], sizes[K][G]) of this rank's table slices."""
-        self._stage_b(sks, ci, self.d_hs.ptr)
-        return self._hs_split(self.d_hs.download())
-
-    def containment_and_commit_results(self, sks, ci, want_multimapped):
-        """Stage B's kernels, then BOTH read-backs (containment counts, stage-C accumulators of a commit queued
-        earlier with profile_commit_launch) behind them: one synchronisation."""
-        T = self.ntax
-        # the per-genome counts (8 B per genome) are written by the kernel straight into page-locked host memory
-        self._stage_b(sks, ci, self.h_hs.ptr)
-        self.hip.stage_c_join()  # the accumulators are read on the main stream: it waits for stage C's stream here
-        self.h_acc.fetch_async(self.d_acc.ptr)
-        self.hip.sync()
-        for ki, sk in enumerate(sks):
-            if sk.resolve():  # stage A's counting table overflowed and the sketch was rebuilt: stage B again
-                self._stage_b_again(sks, ki, ci, self.h_hs.ptr)
-        hs, acc = self._hs_split(self.h_hs.array), self.h_acc.array.copy()
-        mm = self.shard.multimapped() if want_multimapped else None
-        self.shard.free()
-        return hs, (acc[:T], acc[T:2 * T], acc[2 * T:3 * T], acc[3 * T:], mm)
-
     # ---- stage C ----
     def set_sketch_bound(self, sk, truncated, bound):
         sk.set_bound(truncated, bound)
-
-    def profile_begin(self, pct_id, need_map=True):
-        """Pass A of stage C.  The composed state map / read count are only read back (one stream sync) when a
-        neighbouring shard needs them."""
-        self.shard = self.hip.profile_begin_dev(self.d_recs.ptr, self.nrecs, self.has_lookahead, self.d_r2t.ptr,
-                                                self.nref, self.ntax, pct_id)
-        if not need_map:
-            return (0, 1), 0
-        return self.shard.state_map(), self.shard.ngroups
-
-    def profile_begin_async(self, pct_id):
-        """Pass A of stage C queued without a sync; profile_map() fetches its two words later."""
-        self.shard = self.new_shard_async(pct_id)
 
     def new_shard_async(self, pct_id):
         """A stage-C handle over the resident records with its map-only pass already queued (a pipelined job starts
@@ -437,81 +465,101 @@ class HipEngine:
     def profile_map(self):
         return self.shard.state_map(), self.shard.ngroups
 
+    # ---- a pass's results: queued into a result set, read back from it.  Every schedule goes through these five: step()
+    # (profile_commit_launch / containment_and_commit_results), a single shard's queue-ahead passes (queue_pass / finish_pass)
+    # and the four passes in flight of the exchange (x_commit / x_stage_b / x_collect).
+    def _result_set(self, slot, nwords=0, nred=0):
+        """Result set number `slot` of the pool, made when first asked for: the pass's stage-C accumulators on the device
+        (d_acc: [count T | bases T | first_seen T | scalars 2]), the page-locked buffers its read-backs land in — the
+        accumulators (h_acc) and the per-genome counts, which stage B's kernels write straight into host memory (h_hs: per k
+        [hits g | sizes g], 8 B per genome) — and the event recorded behind them; for the exchange also where the gathered
+        words and the reduce buffer land.  The caller numbers the slots: a pass's slot is not handed out again before that
+        pass has been read back."""
+        hip, T = self.hip, self.ntax
+        while len(self._pool) <= slot:
+            self._pool.append(dict(d_acc=hip.empty(3 * T + 2, np.uint64), h_acc=hip.pinned(3 * T + 2, np.uint64),
+                                   h_hs=hip.pinned(2 * self.gpad * self.nk, np.uint32), ev=hip.event()))
+        rs = self._pool[slot]
+        if nwords and "h_words" not in rs:
+            rs.update(h_words=hip.pinned(nwords, np.int64), h_red=hip.pinned(nred, np.int64),
+                      h_red_in=hip.pinned(nred, np.int64), d_red=hip.empty(nred, np.int64))
+        return rs
+
+    def _commit(self, shard, rs, incoming, first_shard, group_base):
+        """Stage C's pass into the set's accumulators (reset in the pass's own preparation launch); nothing is read back."""
+        T, base = self.ntax, rs["d_acc"].ptr
+        shard.commit(incoming, first_shard, group_base, base, base + T * 8, base + 2 * T * 8, base + 3 * T * 8, reset=True)
+
+    def _acc_split(self, acc):
+        T = self.ntax
+        return acc[:T], acc[T:2 * T], acc[2 * T:3 * T], acc[3 * T:]
+
+    def _queue_tail(self, rs, sks, ci):
+        """Stage B's kernels, then the accumulators' read-back behind them (of a commit queued earlier) and the set's event."""
+        self._stage_b(sks, ci, rs["h_hs"].ptr)
+        self.hip.stage_c_join()  # the accumulators are read on the main stream: it waits for stage C's stream here
+        rs["h_acc"].fetch_async(rs["d_acc"].ptr)
+        rs["ev"].record()
+
+    def _read_back(self, rs, sks, shard, ci, want_multimapped, spent=(), copy=True):
+        """The other end of _queue_tail: ONE wait, for this pass only (the next one may already be running).
+        spent: sketches nothing reads any more once the event is through, freed right behind it.
+        copy=False: the accumulators as views of the set's landing buffer, for a caller that is done with them before the
+        slot's next pass.  -> (hits[K][G], sizes[K][G]), (count, bases, first_seen, scalars, multimapped)"""
+        rs["ev"].synchronize()
+        for sk in spent:
+            sk.free()
+        for ki, sk in enumerate(sks):
+            if sk.resolve():  # stage A's counting table overflowed and the sketch was rebuilt: stage B again
+                self._stage_b_again(sks, ki, ci, rs["h_hs"].ptr)
+        hs, acc = self._hs_split(rs["h_hs"].array), rs["h_acc"].array
+        mm = shard.multimapped() if want_multimapped else None
+        shard.free()
+        return hs, self._acc_split(acc.copy() if copy else acc) + (mm,)
+
     # ---- queue-ahead passes (single shard): everything of a pass is queued, a marker is recorded behind it, and
     # the pass is read back later — after the NEXT pass has been queued, so the GPU runs pass after pass without
     # waiting for the host in between.  Two result sets alternate.
-    def _result_sets(self):
-        if not hasattr(self, "_sets"):
-            hip, g, T = self.hip, self.gpad, self.ntax
-            self._sets = [dict(d_acc=self.d_acc, h_acc=self.h_acc, h_hs=self.h_hs, ev=hip.event()),
-                          dict(d_acc=hip.empty(3 * T + 2, np.uint64), h_acc=hip.pinned(3 * T + 2, np.uint64),
-                               h_hs=hip.pinned(2 * g * self.nk, np.uint32), ev=hip.event())]
-        return self._sets
-
     def queue_pass(self, slot, ks, hmaxs, s, ci, pct_id, side=False):
-        rs = self._result_sets()[slot]
-        T = self.ntax
+        rs = self._result_set(slot)
         if side:  # stage A of consecutive passes on alternating streams: pass i+1's overlaps pass i's tail
             # (3 / 4: the two stage-A streams at the lowest priority — no collective in this schedule, and the short kernels of stage B and C
             # then get in ahead of the next pass's persistent stage-A kernel: 2.33 -> 2.22 ms per pass at configs[2])
             # (by hash value the sketch's own small kernels — sort, pack — ride the stage-A streams: default priority, as measured: 5.4 against 5.6 ms)
-            self.hip.stage_a_side_stream((3 if getattr(self, "kmer", False) else 1) + (slot & 1))
+            self.hip.stage_a_side_stream((3 if self.kmer else 1) + (slot & 1))
         sks = self.sketch_local_async(ks, hmaxs, s)                                               # stage A
         shard = self.hip.profile_begin_dev(self.d_recs.ptr, self.nrecs, self.has_lookahead, self.d_r2t.ptr,
                                            self.nref, self.ntax, pct_id)
-        base = rs["d_acc"].ptr
-        shard.commit(True, True, 0, base, base + T * 8, base + 2 * T * 8, base + 3 * T * 8, reset=True)  # stage C (2nd stream)
-        self._stage_b(sks, ci, rs["h_hs"].ptr)                                                    # stage B (main)
-        self.hip.stage_c_join()
-        rs["h_acc"].fetch_async(base)
-        rs["ev"].record()
-        return dict(slot=slot, sks=sks, shard=shard, ci=ci)
+        self._commit(shard, rs, True, True, 0)                                                    # stage C (2nd stream)
+        self._queue_tail(rs, sks, ci)                                                             # stage B (main)
+        return dict(rs=rs, sks=sks, shard=shard, ci=ci)
 
     def finish_pass(self, q, want_multimapped):
-        rs = self._result_sets()[q["slot"]]
-        T = self.ntax
-        rs["ev"].synchronize()  # this pass only: the next one may already be running
-        sks, shard = q["sks"], q["shard"]
-        for ki, sk in enumerate(sks):
-            if sk.resolve():  # stage A's counting table overflowed and the sketch was rebuilt: stage B again
-                self._stage_b_again(sks, ki, q["ci"], rs["h_hs"].ptr)
-        hs, acc = self._hs_split(rs["h_hs"].array), rs["h_acc"].array.copy()
-        mm = shard.multimapped() if want_multimapped else None
-        shard.free()
-        return sks, hs, (acc[:T], acc[T:2 * T], acc[2 * T:3 * T], acc[3 * T:], mm)
+        return (q["sks"],) + self._read_back(q["rs"], q["sks"], q["shard"], q["ci"], want_multimapped)
 
+    # ---- step() with the exchange: the map-only pass is self.shard (new_shard_async), the result set number 0
     def profile_commit_launch(self, incoming, first_shard, group_base):
         """Asynchronous part of the commit: accumulator reset + the stage-C pass; nothing is read back."""
-        T = self.ntax
-        base = self.d_acc.ptr
-        self.shard.commit(incoming, first_shard, group_base, base, base + T * 8, base + 2 * T * 8, base + 3 * T * 8,
-                          reset=True)
+        self._commit(self.shard, self._result_set(0), incoming, first_shard, group_base)
 
-    def profile_commit_finish(self, want_multimapped=True):
-        T = self.ntax
-        acc = self.d_acc.download()
-        mm = self.shard.multimapped() if want_multimapped else None
-        self.shard.free()
-        return acc[:T], acc[T:2 * T], acc[2 * T:3 * T], acc[3 * T:], mm
-
-    def profile_commit(self, incoming, first_shard, group_base, want_multimapped=True):
-        self.profile_commit_launch(incoming, first_shard, group_base)
-        return self.profile_commit_finish(want_multimapped)
+    def containment_and_commit_results(self, sks, ci, want_multimapped):
+        """Stage B's kernels, then BOTH read-backs (containment counts, stage-C accumulators of a commit queued
+        earlier with profile_commit_launch) behind them: one synchronisation."""
+        rs = self._result_set(0)
+        self._queue_tail(rs, sks, ci)
+        return self._read_back(rs, sks, self.shard, ci, want_multimapped)
 
     # ---- the device side of ShardJob._run_exchange_pipelined (four passes in flight): every method queues work and
     # returns, except the x_wait_* / x_collect ones, which wait for ONE event recorded a tick earlier.
     def x_setup(self, W, G, T, bounds, nslot):
         """bounds: per k, the W+1 hash-range bounds."""
-        hip, g, K = self.hip, self.gpad, self.nk
         # (words: per SKETCHED k; the reduce buffer: per column)
-        self._xW, self._xNW, self._xnred = W, self.nsk * (W + 4) + 3, 2 * K * G + 2 * T + W * T + K + 2
-        if not hasattr(self, "_xs"):
-            self._xs = [dict(d_acc=hip.empty(3 * T + 2, np.uint64), h_acc=hip.pinned(3 * T + 2, np.uint64),
-                             h_hs=hip.pinned(2 * g * K, np.uint32), h_words=hip.pinned(W * self._xNW, np.int64),
-                             h_red=hip.pinned(self._xnred, np.int64), h_red_in=hip.pinned(self._xnred, np.int64),
-                             d_red=hip.empty(self._xnred, np.int64), ev=hip.event()) for _ in range(nslot)]
-            self._xbounds = [hip.array(np.asarray(b[1:W] if W > 1 else [0], dtype=np.uint64)) for b in bounds]
-        if getattr(self, "kmer", False):
+        self._xwords, self._xnred = WordsLayout(self.nsk, W), red_layout(self.nk, G, T, W)[-1]
+        for slot in range(nslot):
+            self._result_set(slot, W * self._xwords.total, self._xnred)
+        if self._xbounds is None:
+            self._xbounds = [self.hip.array(np.asarray(b[1:W] if W > 1 else [0], dtype=np.uint64)) for b in bounds]
+        if self.kmer:
             self.reserve_counters(nslot + 4)  # (four passes in flight and three fronts queued ahead of them)
 
     def x_begin(self):
@@ -533,36 +581,30 @@ class HipEngine:
         self.hip.stage_a_side_stream(False)
 
     def x_front(self, ks, hmaxs, s, pct_id):
-        if getattr(self, "kmer", False):
+        if self.kmer:
             # the counting kernels of consecutive passes on the two stage-A streams in turn: the next one's launch does not wait
             # for the previous one's last wavefronts (measured for the hash path's sketch, x_begin: worse; for this kernel: better)
-            self._xturn = 1 - getattr(self, "_xturn", 1)
+            self._xturn = 1 - self._xturn
             self.hip.stage_a_side_stream(1 + self._xturn)
         return dict(sks=self.sketch_local_async(ks, hmaxs, s), shard=self.new_shard_async(pct_id))
 
     def x_words(self, P, slot):
         """This rank's words, assembled on the device from the still pending sketches and the map-only pass."""
-        P["rs"] = self._xs[slot]
-        W, t = self._xW, self.torch
-        kmer = getattr(self, "kmer", False)  # (no sketch to cut into slices: those words stay zero)
-        word_t = (t.zeros if kmer else t.empty)(self._xNW, dtype=t.int64, device="cuda")
+        P["rs"] = self._result_set(slot)
+        lay, t = self._xwords, self.torch
+        kmer = self.kmer  # (no sketch to cut into slices: those words stay zero)
+        word_t = (t.zeros if kmer else t.empty)(lay.total, dtype=t.int64, device="cuda")
         for ki, sk in enumerate(P["sks"]):
             if not kmer:
-                sk.slice_words_dev(self._xbounds[ki].ptr, W - 1, word_t.data_ptr() + 8 * ki * (W + 4))
-        P["shard"].map_words_dev(word_t.data_ptr() + 8 * self.nsk * (W + 4))
+                sk.slice_words_dev(self._xbounds[ki].ptr, lay.W - 1, word_t.data_ptr() + 8 * lay.sizes(ki))
+        P["shard"].map_words_dev(word_t.data_ptr() + 8 * lay.tail)
         return word_t
 
     def x_redo_words(self, P, bounds, tail):
         """Host path, after a table overflow made the published words stale: settle the sketches and cut them again."""
-        W, word = self._xW, []
-        for ki, sk in enumerate(P["sks"]):
+        for sk in P["sks"]:
             sk.resolve()
-            n = sk.size
-            cuts = [0] + self.split_sketch(sk, bounds[ki][1:W]) + [n]
-            last = sk.last_hash
-            word += [cuts[q + 1] - cuts[q] for q in range(W)] + [int(sk.truncated), last - (1 << 64) if last >= (1 << 63) else last, n, 0]
-        word += list(tail)
-        return self.torch.as_tensor(np.asarray(word, dtype=np.int64), device="cuda")
+        return self.torch.as_tensor(self._xwords.encode(self, P["sks"], bounds, tail), device="cuda")
 
     def x_fetch_words(self, P, words_t, hold):
         rs = P["rs"]
@@ -574,52 +616,34 @@ class HipEngine:
         rs = P["rs"]
         rs["ev"].synchronize()
         P["hold"] = None
-        return rs["h_words"].array.reshape(self._xW, self._xNW).tolist()
+        return rs["h_words"].array.reshape(self._xwords.W, self._xwords.total).tolist()
 
     def x_commit(self, P, incoming, first_shard, group_base):
-        T, base = self.ntax, P["rs"]["d_acc"].ptr
-        P["shard"].commit(incoming, first_shard, group_base, base, base + T * 8, base + 2 * T * 8, base + 3 * T * 8,
-                          reset=True)
+        self._commit(P["shard"], P["rs"], incoming, first_shard, group_base)
 
     def x_merge(self, P, rh, rc, k, lo, hi, any_trunc, bound):
         P.setdefault("keep", []).append((rh, rc))  # a deferred merge reads its inputs again if it has to be redone
-        if getattr(self, "reftable", None) is not None:
+        if self.reftable is not None:
             # the reference pipeline's stage B contains a collective (the prefix bitmaps): a merge that had to be redone a
             # phase later could not repeat it on one rank alone — settled here instead (one sketch per pass, not one per k)
             return self.hip.sketch_merge_dev(rh.data_ptr(), rc.data_ptr(), int(rh.numel()), k, lo, hi, 0, any_trunc, bound)
         return self.hip.sketch_merge_dev_async(rh.data_ptr(), rc.data_ptr(), int(rh.numel()), k, lo, hi, 0, any_trunc, bound)
 
     def x_stage_b(self, P, merged, ci):
-        rs = P["rs"]
         P["merged"] = merged
-        self._stage_b(merged, ci, rs["h_hs"].ptr)
-        self.hip.stage_c_join()
-        rs["h_acc"].fetch_async(rs["d_acc"].ptr)
-        rs["ev"].record()
+        self._queue_tail(P["rs"], merged, ci)
 
     def x_collect(self, P, ci, want_multimapped):
-        rs, T = P["rs"], self.ntax
-        rs["ev"].synchronize()
         merged = P["merged"]
-        for sk in P["sks"]:
-            sk.free()  # their buffers were the all-to-all's send buffers: back to the pool only now
-        for ki, m in enumerate(merged):
-            if m.resolve():
-                # (a reference-pipeline merge is settled in the phase that queues it — x_merge: its redo needs the prefix-bitmap collective on
-                # every rank — so a rebuilt sketch cannot turn up here; if it ever does, the columns below would be stale)
-                if self.reftable is not None:
-                    raise RuntimeError("a reference-pipeline sketch was rebuilt after its stage B had run: x_merge must settle it")
-                self.hip.sync()
-                self.hip.containment_dev(m, self.tables[ki], ci, *self._hs_ptrs(rs["h_hs"].ptr, ki))
-                self.hip.sync()
-        (hits, sizes), acc = self._hs_split(rs["h_hs"].array), rs["h_acc"].array
-        mm = P["shard"].multimapped() if want_multimapped else None
+        # (P["sks"]: their buffers were the all-to-all's send buffers: back to the pool only now.  The accumulators as views: they
+        # go straight into the reduce buffer — ShardJob._fill_reduce — long before the slot's next pass)
+        (hits, sizes), (count, bases, first, scalars, mm) = self._read_back(P["rs"], merged, P["shard"], ci, want_multimapped,
+                                                                            spent=P["sks"], copy=False)
         qn = [m.size for m in merged]
-        P["shard"].free()
         for m in merged:
             m.free()
         P["keep"] = None
-        return hits, sizes, acc[:T], acc[T:2 * T], acc[2 * T:3 * T], acc[3 * T:], mm, qn
+        return hits, sizes, count, bases, first, scalars, mm, qn
 
     def x_reduce_buffer(self, P):
         buf = P["rs"]["h_red_in"].array
@@ -799,6 +823,12 @@ class ShardJob:
                                         % (getattr(hip, "main_stream", None), cur))
             self.engine = HipEngine(hip, tm)
         self.device = getattr(self.engine, "device", "cuda")
+        # The engine's kind, decided here once for every pass.  queued: it queues a pass on the device and reads it back later
+        # (HipEngine: queue_pass / finish_pass, profile_commit_launch / containment_and_commit_results); otherwise every call computes
+        # where it stands (a host engine of the tests: profile_begin / profile_commit / containment).  pipelined: it serves the x_*
+        # calls of the four-passes-in-flight schedule.
+        self.queued, self.pipelined = hasattr(self.engine, "queue_pass"), hasattr(self.engine, "x_front")
+        self.words, self.words_redone = WordsLayout(len(self.sks_k), world), 0
         if dist is not None and self.device != "cpu" and dist.get_backend() == "gloo":
             self.dist = _HostStagedGloo(dist, self.torch)  # (tests: several ranks on one GPU)
 
@@ -1083,84 +1113,81 @@ class ShardJob:
 
     def _merge_args(self, words, ki):
         """From the gathered words of k number ki: (any source truncated?, the completeness bound, this rank's range)."""
-        W, o = self.world, ki * (self.world + 4)
+        lay = self.words
         # completeness: a source truncated at its s-th hash knows nothing above it
-        lasts = [_u64(w[o + W + 1]) for w in words if w[o + W] and w[o + W + 2]]
+        lasts = [_u64(w[lay.last(ki)]) for w in words if w[lay.truncated(ki)] and w[lay.n(ki)]]
         complete_to = min(lasts) if lasts else U64_MAX
         b = self.bounds[ki]
         return bool(lasts), complete_to, b[self.rank], b[self.rank + 1] - 1
 
-    def _exchange_step(self):
+    def _exchange_step(self, want_multimapped):
         """Stage A + pass A of stage C locally, then ONE all-gather of per-rank words (slice sizes and sketch
         completeness of every k, carried-state map) and ONE all-to-all round of sketch slices, during which stage C's
         commit runs (it only needs the gathered state maps).
-        -> (this rank's slice of the sample sketch for every k, commit results)."""
-        eng, t, dist, W, K = self.engine, self.torch, self.dist, self.world, len(self.sks_k)
-        if hasattr(eng, "profile_begin_async"):
+        -> (this rank's slice of the sample sketch for every k, commit results: None when the engine left the commit in flight)."""
+        eng, t, dist, W = self.engine, self.torch, self.dist, self.world
+        if self.queued:
             # stage C's map-only pass is queued first: stage A's one synchronisation covers it too
-            if self._given is not None:
-                sks, eng.shard = self._given  # queued a pass ahead by run()
-            else:
-                eng.profile_begin_async(self.pct_id)
-                sks = eng.sketch_local(self.sks_k, self.hmaxs, self.s)
+            eng.shard = eng.new_shard_async(self.pct_id)
+            sks = eng.sketch_local(self.sks_k, self.hmaxs, self.s)
             (m0, m1), ngroups = eng.profile_map()
+            commit = eng.profile_commit_launch  # read back with stage B's counts (step())
         else:
             sks = eng.sketch_local(self.sks_k, self.hmaxs, self.s)
             (m0, m1), ngroups = eng.profile_begin(self.pct_id, True)
-        kmer = self.match == "kmer"
-        word, send_counts = [], []
-        if kmer:
-            word = [0] * (K * (W + 4))
-        for ki, sk in enumerate([] if kmer else sks):
-            n = sk.size
-            cuts = [0] + eng.split_sketch(sk, self.bounds[ki][1:W]) + [n]
-            sc = [cuts[q + 1] - cuts[q] for q in range(W)]
-            send_counts.append(sc)
-            last = sk.last_hash  # two's complement into the int64 word
-            word += sc + [int(sk.truncated), last - (1 << 64) if last >= (1 << 63) else last, n, 0]
-        word += [m0, m1, ngroups]
-        NW = K * (W + 4) + 3
-        words = [t.zeros(NW, dtype=t.int64, device=self.device) for _ in range(W)]
-        dist.all_gather(words, t.as_tensor(np.asarray(word, dtype=np.int64), device=self.device))
+            commit = lambda *a: eng.profile_commit(*a, want_multimapped)  # noqa: E731
+        word = self.words.encode(eng, [] if self.match == "kmer" else sks, self.bounds, [m0, m1, ngroups])
+        words = [t.zeros(len(word), dtype=t.int64, device=self.device) for _ in range(W)]
+        dist.all_gather(words, t.as_tensor(word, device=self.device))
         self._sent("words_all_gather", 8 * len(word) * (W - 1))
         words = t.stack(words).cpu().numpy().tolist()
+        merged, committed, keep = self._exchange_back_half(
+            words, sks, commit, lambda rh, rc, k, lo, hi, any_trunc, bound: eng.merge_sketches(rh, rc, k, 0, any_trunc, bound, (lo, hi)))
+        if self.match == "kmer":
+            self._kmer_keep = keep  # (until the next pass: stage B is queued behind it)
+            return sks, committed
+        # the sketches' buffers were the all-to-all's send buffers: they go back to the pool only now that the merges
+        # (which read what the all-to-all delivered, and synchronised) are done
+        for sk in sks:
+            sk.free()
+        if self.queued:
+            eng.keep = []
+        return merged, committed
+
+    def _exchange_back_half(self, words, sks, commit, merge):
+        """What follows a pass's all-gather, from the gathered words (a row per rank) and this rank's sketches: the all-to-all of
+        the slices, stage C's commit(incoming, first_shard, group_base) during it, and merge(rh, rc, k, lo, hi, any_truncated, bound)
+        of what each k received.  -> (this rank's slice of the sample sketch for every k, what commit returned, None); by k-mer
+        identity (sks, what commit returned, the tensors the queued sum of the counters must outlive)."""
+        eng, W, lay = self.engine, self.world, self.words
+        kmer = self.match == "kmer"
         received, inflight = [], []
         for ki, sk in enumerate([] if kmer else sks):
-            recv_counts = [words[p][ki * (W + 4) + self.rank] for p in range(W)]
+            o = lay.sizes(ki)
+            send_counts = [int(x) for x in words[self.rank][o:o + W]]  # (the numbers this rank put there)
+            recv_counts = [int(words[p][o + self.rank]) for p in range(W)]
             h, c = eng.export_sketch(sk)
-            rh, rc, fl = self._all_to_all(h, c, send_counts[ki], recv_counts)
+            rh, rc, fl = self._all_to_all(h, c, send_counts, recv_counts)
             received.append((rh, rc))
             inflight += fl
-        # stage C commit overlaps the all-to-all: it depends on the gathered maps only
-        tail = K * (W + 4)
-        maps = [(w[tail], w[tail + 1]) for w in words]
+        # stage C's commit runs during the all-to-all: it depends on the gathered maps only
+        maps = [(w[lay.tail], w[lay.tail + 1]) for w in words]
         incoming = compose_incoming(maps, self.rank)
-        group_base = int(sum(w[tail + 2] for w in words[: self.rank]))
+        group_base = int(sum(w[lay.tail + 2] for w in words[: self.rank]))
         first_shard = self.nonempty[self.rank] and not any(self.nonempty[: self.rank])
-        if hasattr(eng, "profile_commit_launch"):
-            eng.profile_commit_launch(incoming, first_shard, group_base)  # read back with stage B's counts (step())
-            committed = None
-        else:
-            committed = eng.profile_commit(incoming, first_shard, group_base, self._want_mm)
+        committed = commit(incoming, first_shard, group_base)
         if kmer:
-            self._kmer_keep = self._sum_kmer_counts(sks[0].counts)  # (until the next pass: stage B is queued behind it)
-            return sks, committed
+            return sks, committed, self._sum_kmer_counts(sks[0].counts)
         for wk in inflight:
             wk.wait()
         merged = []
         for ki, (rh, rc) in enumerate(received):
             any_trunc, complete_to, lo, hi = self._merge_args(words, ki)
-            m = eng.merge_sketches(rh, rc, self.sks_k[ki], 0, any_trunc, complete_to, (lo, hi))
+            m = merge(rh, rc, self.sks_k[ki], lo, hi, any_trunc, complete_to)
             if self.s or any_trunc:
                 m = self._bottom_s(m, any_trunc, self.sks_k[ki])
             merged.append(m)
-        # the sketches' buffers were the all-to-all's send buffers: they go back to the pool only now that the merges
-        # (which read what the all-to-all delivered, and synchronised) are done
-        for sk in sks:
-            sk.free()
-        if hasattr(eng, "keep"):
-            eng.keep = []
-        return merged, committed
+        return merged, committed, None
 
     def _bottom_s(self, merged, any_trunc, k):
         """bottom-s over the rank-ordered slices: keep the first s entries of the global order and tell every
@@ -1196,23 +1223,20 @@ class ShardJob:
         eng = self.engine
         if nsteps < 1:
             return None
-        if self.exchange and hasattr(eng, "x_front") and os.environ.get("MG_EXCHANGE_PIPELINE", "1") != "0":
+        if self.exchange and self.pipelined:
             return self._run_exchange_pipelined(nsteps, want_multimapped)
-        if not hasattr(eng, "sketch_local_async"):
+        if self.exchange or not self.queued:
             out = None
             for _ in range(nsteps):
                 out = self.step(want_multimapped)
             return out
-        if not self.exchange:
-            # Single shard: no exchange to hide.  The GPU is not left waiting for the host between passes: pass i+1 is
-            # queued (behind pass i) BEFORE pass i is read back ...
-            # ... and stage A of consecutive passes goes to two alternating streams at full occupancy: pass i+1's
-            # k_sketch_reads fills the GPU while pass i's sort / pack / stage B tail (small kernels) drains.
-            import gc
-            side = os.environ.get("MG_SINGLE_STREAM", "0") != "1"  # (=1: everything on one stream, for clean profiles)
-            eng.hip.stage_a_workgroups_per_cu(0)
-            gc_was_on = gc.isenabled()
-            gc.disable()  # (a cyclic collection in the loop is a hole of milliseconds in the GPU's queue)
+        # Single shard: no exchange to hide.  The GPU is not left waiting for the host between passes: pass i+1 is
+        # queued (behind pass i) BEFORE pass i is read back ...
+        # ... and stage A of consecutive passes goes to two alternating streams at full occupancy: pass i+1's
+        # k_sketch_reads fills the GPU while pass i's sort / pack / stage B tail (small kernels) drains.
+        side = os.environ.get("MG_SINGLE_STREAM", "0") != "1"  # (=1: everything on one stream, for clean profiles)
+        eng.hip.stage_a_workgroups_per_cu(0)
+        with _no_gc():
             try:
                 q = eng.queue_pass(0, self.sks_k, self.hmaxs, self.s, self.ci, self.pct_id, side)
                 out = None
@@ -1225,24 +1249,7 @@ class ShardJob:
             finally:
                 if side:
                     eng.hip.stage_a_side_stream(0)
-                if gc_was_on:
-                    gc.enable()
-            return out
-        # (MG_EXCHANGE_PIPELINE=0: the older schedule, one pass at a time with stage A a pass ahead)
-        eng.hip.stage_a_workgroups_per_cu(2)
-        eng.hip.stage_a_side_stream(True)
-        try:
-            def front():  # what does not depend on the other ranks: stage A and stage C's map-only pass
-                return eng.sketch_local_async(self.sks_k, self.hmaxs, self.s), eng.new_shard_async(self.pct_id)
-            nxt = front()
-            out = None
-            for i in range(nsteps):
-                cur = nxt
-                nxt = front() if i + 1 < nsteps else None
-                out = self.step(want_multimapped, _sketch=cur)
-            return out
-        finally:
-            eng.hip.stage_a_side_stream(False)
+        return out
 
     # ---- the exchange path with several passes in flight -------------------------------------------------------
     # A pass with an exchange is a chain: local sketch -> [sync] split -> all-gather -> [sync] all-to-all -> merge
@@ -1254,22 +1261,18 @@ class ShardJob:
     # every rank, so the collectives match up), stage A of passes t+1 and t+2 is already queued on the stage-A
     # stream.  By the time a phase looks at its inputs a whole tick has passed: the waits find finished work.
     def _red_layout(self):
-        G, T, W, K = self.G, self.T, self.world, len(self.ks)
-        o_sizes, o_count = K * G, 2 * K * G
-        o_bases, o_first = o_count + T, o_count + 2 * T
-        o_qn = o_first + W * T
-        return o_sizes, o_count, o_bases, o_first, o_qn, o_qn + K, o_qn + K + 2  # ..., scalars, total
+        return red_layout(len(self.ks), self.G, self.T, self.world)
 
     def _fill_reduce(self, buf, hits, sizes, count, bases, first, scalars, qn):
         G, T, K = self.G, self.T, len(self.ks)
         o_sizes, o_count, o_bases, o_first, o_qn, o_scal, _ = self._red_layout()
-        if getattr(self, "match", None) == "kmer":
+        if self.match == "kmer":
             # every rank holds the whole table and the sample's summed counters: every rank's columns ARE the sample's — rank 0's
             # go into the sum (the matched pairs of the largest k stand in for a sketch size)
             qn = [int(np.asarray(hits)[-1].sum()) if q is None else q for q in qn]
             if self.rank != 0:
                 part = np.asarray(hits).copy()
-                if getattr(self.engine, "kmer_count_sharded", False):
+                if getattr(self.engine, "kmer_count_sharded", False):  # (a host engine of the tests has none)
                     part[-1] = 0  # (the columns of k < k_max are this rank's share of the count lists: they add up; the k_max column is whole)
                 else:
                     part[:] = 0
@@ -1296,7 +1299,7 @@ class ShardJob:
     def _pack_out(self, hits, sizes, count, bases, first, scalars, qn, mm):
         out = dict(hits_k=hits, sizes_k=sizes, hits=hits[-1], sizes=sizes[-1], count=count, bases=bases, first_seen=first,
                    tot_rds=int(scalars[0]), n_ambig=int(scalars[1]), sketch_sizes=qn, sketch_size=qn[-1], multimapped=mm,
-                   ks=list(self.ks), sketched_ks=list(self.sks_k), definition=self.definition, match=getattr(self, "match", None))
+                   ks=list(self.ks), sketched_ks=list(self.sks_k), definition=self.definition, match=self.match)
         ci_vals = hits / np.maximum(sizes, 1)
         out["containment_k"] = ci_vals
         out["containment"] = ci_vals[-1]  # the largest k: the column the cutoff reads (select_db.py:85-86)
@@ -1304,15 +1307,14 @@ class ShardJob:
         return out
 
     def _run_exchange_pipelined(self, nsteps, want_multimapped):
-        eng, t, dist, W, K = self.engine, self.torch, self.dist, self.world, len(self.sks_k)
-        G, T = self.G, self.T
-        NSLOT, NW = 4, K * (W + 4) + 3  # per rank, per k: W slice sizes | truncated | last hash | n | overflows; then m0 | m1 | reads
-        eng.x_setup(W, G, T, self.bounds, NSLOT)
+        eng, t, dist, W, lay = self.engine, self.torch, self.dist, self.world, self.words
+        NSLOT = 4
+        eng.x_setup(W, self.G, self.T, self.bounds, NSLOT)
 
         def gather_words(P, word_t):
-            words = t.empty((W, NW), dtype=t.int64, device=word_t.device)
+            words = t.empty((W, lay.total), dtype=t.int64, device=word_t.device)
             dist.all_gather(list(words.unbind(0)), word_t)
-            self._sent("words_all_gather", 8 * NW * (W - 1))
+            self._sent("words_all_gather", 8 * lay.total * (W - 1))
             eng.x_fetch_words(P, words, word_t)
 
         def phase_a(P, slot):  # this rank's words into the all-gather: no host wait at all
@@ -1320,41 +1322,16 @@ class ShardJob:
 
         def phase_b(P):  # all-to-all of the slices, stage-C commit, merge, stage B
             words = eng.x_wait_words(P)
-            tail = K * (W + 4)
-            if any(w[ki * (W + 4) + W + 3] for w in words for ki in range(K)):
+            if any(w[lay.overflow(ki)] for w in words for ki in range(lay.K)):
                 # some rank's counting table overflowed (a sample unlike the previous one): its words are stale.  Every
                 # rank sees the same flags, so every rank repeats the all-gather once that sketch has been rebuilt.
-                self.words_redone = getattr(self, "words_redone", 0) + 1
-                gather_words(P, eng.x_redo_words(P, self.bounds, words[self.rank][tail:]))
+                self.words_redone += 1
+                gather_words(P, eng.x_redo_words(P, self.bounds, words[self.rank][lay.tail:]))
                 words = eng.x_wait_words(P)
-            received, inflight = [], []
-            for ki, sk in enumerate(P["sks"] if self.match != "kmer" else []):
-                o = ki * (W + 4)
-                sc = [int(x) for x in words[self.rank][o:o + W]]
-                recv_counts = [int(words[p][o + self.rank]) for p in range(W)]
-                h, c = eng.export_sketch(sk)
-                rh, rc, fl = self._all_to_all(h, c, sc, recv_counts)
-                received.append((rh, rc))
-                inflight += fl
-            maps = [(w[tail], w[tail + 1]) for w in words]
-            incoming = compose_incoming(maps, self.rank)
-            group_base = int(sum(w[tail + 2] for w in words[: self.rank]))
-            first_shard = self.nonempty[self.rank] and not any(self.nonempty[: self.rank])
-            eng.x_commit(P, incoming, first_shard, group_base)  # runs during the all-to-all: it needs the maps only
-            if self.match == "kmer":
-                P["keep"] = self._sum_kmer_counts(P["sks"][0].counts)
-                eng.x_stage_b(P, P["sks"], self.ci)
-                return
-            for wk in inflight:
-                wk.wait()
-            merged = []
-            for ki, (rh, rc) in enumerate(received):
-                any_trunc, complete_to, lo, hi = self._merge_args(words, ki)
-                # queued, not waited for: the merged slice is consumed on the device by stage B; phase C settles it
-                m = eng.x_merge(P, rh, rc, self.sks_k[ki], lo, hi, any_trunc, complete_to)
-                if self.s or any_trunc:
-                    m = self._bottom_s(m, any_trunc, self.sks_k[ki])
-                merged.append(m)
+            # (the merge: queued, not waited for: the merged slice is consumed on the device by stage B; phase C settles it)
+            merged, _, keep = self._exchange_back_half(words, P["sks"], lambda *a: eng.x_commit(P, *a), lambda *a: eng.x_merge(P, *a))
+            if keep is not None:
+                P["keep"] = keep
             eng.x_stage_b(P, merged, self.ci)
 
         def phase_c(P):  # this rank's counts -> THE all-reduce
@@ -1370,68 +1347,53 @@ class ShardJob:
         def phase_d(P):
             return self._read_reduce(eng.x_wait_reduced(P), P["mm"])
 
-        import gc
-        gc_was_on = gc.isenabled()
-        gc.disable()  # a generation-2 collection in the middle of a tick is a 2-3 ms hole in the GPU's queue (measured:
-        eng.x_begin()  # one per ~160 passes); nothing cyclic is created here, reference counting frees what a pass drops
-        try:
-            AHEAD = 3  # stage A queued this many passes ahead: the GPU keeps hashing through a host stall of a millisecond or two
+        with _no_gc():
+            eng.x_begin()
+            try:
+                AHEAD = 3  # stage A queued this many passes ahead: the GPU keeps hashing through a host stall of a millisecond or two
 
-            def front():
-                return eng.x_front(self.sks_k, self.hmaxs, self.s, self.pct_id)
-            fronts = [front() for _ in range(min(AHEAD, nsteps))]
-            passes, out = {}, None
-            for tick in range(nsteps + 3):
-                if 0 <= tick - 3 < nsteps:
-                    out = phase_d(passes.pop(tick - 3))
-                if 0 <= tick - 2 < nsteps:
-                    phase_c(passes[tick - 2])
-                if 0 <= tick - 1 < nsteps:
-                    phase_b(passes[tick - 1])
-                # phase A last: it makes the main stream wait (on the device) for the NEWEST sketch, and whatever is
-                # queued behind that wait only runs once that hashing kernel is through
-                if tick < nsteps:
-                    passes[tick] = P = fronts.pop(0)
-                    phase_a(P, tick % NSLOT)
-                    if tick + AHEAD < nsteps:
-                        fronts.append(front())
-            return out
-        finally:
-            eng.x_end()
-            if gc_was_on:
-                gc.enable()
+                def front():
+                    return eng.x_front(self.sks_k, self.hmaxs, self.s, self.pct_id)
+                fronts = [front() for _ in range(min(AHEAD, nsteps))]
+                passes, out = {}, None
+                for tick in range(nsteps + 3):
+                    if 0 <= tick - 3 < nsteps:
+                        out = phase_d(passes.pop(tick - 3))
+                    if 0 <= tick - 2 < nsteps:
+                        phase_c(passes[tick - 2])
+                    if 0 <= tick - 1 < nsteps:
+                        phase_b(passes[tick - 1])
+                    # phase A last: it makes the main stream wait (on the device) for the NEWEST sketch, and whatever is
+                    # queued behind that wait only runs once that hashing kernel is through
+                    if tick < nsteps:
+                        passes[tick] = P = fronts.pop(0)
+                        phase_a(P, tick % NSLOT)
+                        if tick + AHEAD < nsteps:
+                            fronts.append(front())
+                return out
+            finally:
+                eng.x_end()
 
-    def step(self, want_multimapped=False, _sketch=None):
-        """One pass of the hot path over the resident batch.  Returns the sample-wide results (every rank).
-        _sketch: this pass's stage A, already queued (run())."""
+    def step(self, want_multimapped=False):
+        """One pass of the hot path over the resident batch.  Returns the sample-wide results (every rank)."""
         eng = self.engine
-        self._want_mm = want_multimapped
-        self._given = _sketch
         if self.exchange:
-            sks, committed = self._exchange_step()
-            if committed is None:  # commit is in flight: one read-back for stage B's counts and its accumulators
+            sks, committed = self._exchange_step(want_multimapped)
+            if self.queued:  # the commit is in flight: one read-back for stage B's counts and its accumulators
                 (hits, sizes), committed = eng.containment_and_commit_results(sks, self.ci, want_multimapped)
             else:
                 hits, sizes = eng.containment(sks, self.ci)
+        elif self.queued:
+            # single shard: the whole pass is queued, then read back once.  Stage A is queued first (its persistent grid
+            # takes the CUs); stage C follows on the second stream and fills in as stage A drains; its results come back with
+            # the containment counts
+            sks, (hits, sizes), committed = eng.finish_pass(
+                eng.queue_pass(0, self.sks_k, self.hmaxs, self.s, self.ci, self.pct_id, side=False), want_multimapped)
         else:
-            # single shard: stage C is queued first, its results come back with the containment counts ...
-            split = hasattr(eng, "profile_commit_launch")
-            # stage A does not synchronise: the whole step is queued, then read back once.  Stage A is queued first
-            # (its persistent grid takes the CUs); stage C follows on the second stream and fills in as stage A drains.
-            if _sketch is not None:
-                sks, ahead = _sketch
-                ahead.free()  # (a single shard needs no map-only pass; its handle is created below)
-            else:
-                sks = (eng.sketch_local_async(self.sks_k, self.hmaxs, self.s) if split
-                       else eng.sketch_local(self.sks_k, self.hmaxs, self.s))
+            sks = eng.sketch_local(self.sks_k, self.hmaxs, self.s)
             eng.profile_begin(self.pct_id, False)
-            if split:
-                eng.profile_commit_launch(1, True, 0)
-            if split:
-                (hits, sizes), committed = eng.containment_and_commit_results(sks, self.ci, want_multimapped)
-            else:
-                hits, sizes = eng.containment(sks, self.ci)
-                committed = eng.profile_commit(1, True, 0, want_multimapped)
+            hits, sizes = eng.containment(sks, self.ci)
+            committed = eng.profile_commit(1, True, 0, want_multimapped)
         return self._results(sks, hits, sizes, committed)
 
     def _results(self, sks, hits, sizes, committed):

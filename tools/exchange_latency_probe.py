@@ -1,4 +1,4 @@
-"""How the two exchange schedules (one pass at a time / four passes in flight) react to collective latency that one
+"""How the exchange schedule (four passes in flight) reacts to collective latency that one
 GPU cannot show: every collective of the path is preceded by a spin kernel of `delay` microseconds on the stream it
 synchronises with (torch.cuda._sleep), world size 1 under RCCL.
 Usage: python tools/exchange_latency_probe.py            (prints ms per pass for delays 0 / 100 / 300 us)"""
@@ -44,15 +44,12 @@ def delayed(fn):
 for name in ("all_gather", "all_gather_into_tensor", "all_to_all_single", "all_reduce"):
     setattr(dist, name, delayed(getattr(dist, name)))
 
-for mode in ("0", "1"):
-    os.environ["MG_EXCHANGE_PIPELINE"] = mode
-    for d in (0, 100, 300):
-        delay_us[0] = d
-        job.run(6)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        job.run(30)
-        torch.cuda.synchronize()
-        print("%s  +%3d us per collective: %.3f ms per pass" % ("four passes in flight" if mode == "1" else "one pass at a time  ", d,
-                                                                 (time.perf_counter() - t0) / 30 * 1e3), flush=True)
+for d in (0, 100, 300):
+    delay_us[0] = d
+    job.run(6)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    job.run(30)
+    torch.cuda.synchronize()
+    print("four passes in flight  +%3d us per collective: %.3f ms per pass" % (d, (time.perf_counter() - t0) / 30 * 1e3), flush=True)
 dist.destroy_process_group()

@@ -41,7 +41,8 @@ def timed(obj, name, label=None):
     setattr(obj, name, wrap)
 
 
-for n in ("sketch_local", "profile_begin", "export_sketch", "split_sketch", "merge_sketches", "containment", "profile_commit"):
+for n in ("new_shard_async", "sketch_local", "profile_map", "export_sketch", "split_sketch", "profile_commit_launch", "merge_sketches",
+          "containment_and_commit_results"):
     timed(job.engine, n)
 timed(job, "_all_to_all")
 timed(dist, "all_gather", "dist.all_gather")
