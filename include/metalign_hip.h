@@ -83,7 +83,9 @@ int mg_device_count(void);
  * kc_grid, k1_grid, kb_grid (test hooks, k3_grid's meaning for stages A and B: a value > 0 below the computed grid becomes the
  *   grid of k_count_kmers, of k_sketch_reads / k_sketch_reads_multi[_resident], of k_contain_pairs / k_match_pairs /
  *   k_refpipe_count — few workgroups, so that each loops over many tiles); collate_defer (test hook: the collated stream calls
- *   return their batch keyed and not yet collated).
+ *   return their batch keyed and not yet collated); genome_slab_bytes (mg_genomes_stream_open: the size of a page-locked slab,
+ *   default 8 MiB, at least 4 KiB), genome_guard (test hook: mg_genomes_parse_dev fills the 16 bytes behind its bases and the
+ *   word behind its offsets with 0xa5 before its kernels run).
  * Needs no device and no mg_init.  MG_ERR_ARG for a key that does not exist. */
 int mg_debug_set(const char* key, int64_t value);
 int64_t mg_debug_get(const char* key);
@@ -384,6 +386,51 @@ int mg_reads_download(const mg_reads* r, uint8_t* bases, uint64_t* offsets);
 void mg_reads_free(mg_reads* r);
 
 /* ------------------------------------------------------------------------ *
+ * Organism FASTA files -> one genome per FILE (mg_genome.hip; `build_db --ingest device`).  The definition is what
+ * metalign_amd/build_db.py: genome_bases(path) returns: a line that starts with '>' opens a record; every other line after the
+ * file's first header is stripped of white space at both ends and appended; lines in front of the first header are dropped; case
+ * and non-ACGT bytes are kept.  The records of a file are joined by exactly one 'N': every header line but the file's first
+ * emits one, an empty record's too (">a\n>b\n>c\n" is "NN"); a file without a header is an empty genome.  A file's last line
+ * needs no '\n' and never runs into the next file.
+ * UNDECIDED files.  Python's text mode and these byte rules part on a '\r' that no '\n' follows, on a byte 0x1c-0x1f and on a
+ * byte >= 0x80; and on a header line that is '>' and white space only genome_bases raises (the record's name is missing), so
+ * nothing is defined.  A file that holds one of these is not decided on the device: undecided[f] = 1, what the batch holds for it is void, and
+ * the caller parses that file alone with genome_bases (the contract of the BAM decoder's err_kind 6).
+ *   mg_genomes_parse_dev: d_text = the text of nfiles files back to back in HBM, file f = bytes [file_extents[f],
+ *     file_extents[f + 1]) (file_extents: HOST, nfiles + 1 ascending values) -> bases u8[] + offsets u64[nfiles + 1], one entry per
+ *     file.  undecided: HOST u8[nfiles], may be null.  d_text must be readable up to the next 16-byte boundary on both sides.
+ *   mg_genomes_count / _nbases / _device_ptrs / _download / _free: as their mg_reads namesakes.
+ * ------------------------------------------------------------------------ */
+typedef struct mg_genomes mg_genomes;
+int mg_genomes_parse_dev(const uint8_t* d_text, const uint64_t* file_extents, uint64_t nfiles, mg_genomes** out, uint8_t* undecided);
+uint64_t mg_genomes_count(const mg_genomes* g);
+uint64_t mg_genomes_nbases(const mg_genomes* g);
+int mg_genomes_device_ptrs(const mg_genomes* g, const uint8_t** d_bases, const uint64_t** d_offsets);
+int mg_genomes_download(const mg_genomes* g, uint8_t* bases, uint64_t* offsets);
+void mg_genomes_free(mg_genomes* g);
+
+/* The files themselves (mg_stream.hip): reader threads take WHOLE files — a plain file by positional reads, a path that ends in
+ * ".gz" (gzip, BGZF, any number of members) inflated by that thread with zlib — straight into page-locked slabs; an uploader
+ * thread sends the slabs up on the copy stream in file order while the caller sketches the previous batch.  A batch closes at a
+ * file boundary once it holds batch_bases bytes of text; a file larger than a slab spans slabs and is still one genome.
+ *   open:  nthreads <= 0 = 16 (never more than 16).  batch_bases = 0: 1 << 27.  The knob genome_slab_bytes (mg_debug_set) sets
+ *          the slab size (default 8 MiB).  One streaming call at a time: the slabs are those of the other file pipelines.
+ *   next:  the next batch, parsed (mg_genomes_parse_dev): files [*first_file, *first_file + *nfiles_in_batch) of paths;
+ *          undecided_flags: HOST u8[nfiles of the open call], entry i of it = file *first_file + i.  *batch = NULL, *nfiles_in_batch
+ *          = 0 after the last file.  The caller frees the batch.
+ *          A file that cannot be opened or read, a ".gz" that is not gzip, is corrupt or ends inside a member FAILS the call
+ *          (MG_ERR_ARG, the path and zlib's wording in mg_last_error): no file is skipped.
+ *   stats: seconds since open — [0] reader threads in read + inflate (summed over the threads), [1] the uploader queueing
+ *          copies, [2] next() waiting for a batch to be up, [3] next() parsing; [4] bytes of text sent up.
+ * ------------------------------------------------------------------------ */
+typedef struct mg_genomes_stream mg_genomes_stream;
+int mg_genomes_stream_open(const char* const* paths, uint64_t nfiles, uint64_t batch_bases, int nthreads, mg_genomes_stream** out);
+int mg_genomes_stream_next(mg_genomes_stream* h, mg_genomes** batch, uint64_t* first_file, uint64_t* nfiles_in_batch,
+                           uint8_t* undecided_flags);
+int mg_genomes_stream_stats(const mg_genomes_stream* h, double out[5]);
+void mg_genomes_stream_close(mg_genomes_stream* h);
+
+/* ------------------------------------------------------------------------ *
  * A gzip file's text through the library's PARALLEL inflater (mg_pgzip.hip) — the reference takes `.gz` reads as ordinary
  * input (scripts/select_db.py:146-148; zcat of the selected genomes :103-105).  One gzip stream is entered in the middle by
  * many host threads (deflate block starts found speculatively, back-references into the unknown 32 KB window kept symbolic
@@ -554,6 +601,14 @@ int mg_sketch_genomes_kmers(const uint8_t* bases, const uint64_t* offsets, uint6
                             uint64_t* out_hashes, uint64_t* out_kmer_hi, uint64_t* out_kmer_lo, uint64_t* out_offsets);
 int mg_sketch_genomes_kmers_forward(const uint8_t* bases, const uint64_t* offsets, uint64_t ngenomes, int k, uint64_t n,
                                     uint64_t* out_hashes, uint64_t* out_kmer_hi, uint64_t* out_kmer_lo, uint64_t* out_offsets);
+/* The genome sketchers over bases ALREADY IN HBM (a parsed batch, mg_genomes): the same HOST outputs as mg_sketch_genomes,
+ * mg_sketch_genomes_prefix and mg_sketch_genomes_kmers (forward != 0: mg_sketch_genomes_kmers_forward) for the batch's genomes,
+ * without the upload — one parsed batch serves every k.  What the batch holds for an undecided file is sketched like the rest;
+ * the caller replaces that genome's entries. */
+int mg_sketch_genomes_dev(const mg_genomes* g, int k, uint64_t n, uint64_t* out_hashes, uint64_t* out_offsets);
+int mg_sketch_genomes_prefix_dev(const mg_genomes* g, int kmax, int k, uint64_t n, uint64_t* out_hashes, uint64_t* out_offsets);
+int mg_sketch_genomes_kmers_dev(const mg_genomes* g, int k, uint64_t n, int forward, uint64_t* out_hashes, uint64_t* out_kmer_hi,
+                                uint64_t* out_kmer_lo, uint64_t* out_offsets);
 int mg_refdb_build(const uint64_t* hashes, const uint64_t* kmer_hi, const uint64_t* kmer_lo, const uint64_t* offsets,
                    uint64_t ngenomes, int nk, const int* ks, mg_refdb** out);
 int mg_refdb_upload(uint64_t ngenomes, int nk, const int* ks, uint64_t npairs, const uint64_t* pair_hash,

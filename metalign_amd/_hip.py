@@ -37,6 +37,9 @@ EXPORTS = [
     "mg_sketch_stream_begin", "mg_sketch_stream_begin_counts", "mg_sketch_stream_add_dev", "mg_sketch_stream_add_file", "mg_sketch_stream_finish", "mg_sketch_stream_nreads", "mg_sketch_stream_nbases", "mg_sketch_stream_free",
     "mg_reads_parse_dev", "mg_reads_parse_prefix_dev", "mg_reads_parse", "mg_reads_parse_bam_prefix_dev", "mg_reads_from_bam_file", "mg_reads_count", "mg_reads_nbases", "mg_reads_device_ptrs",
     "mg_reads_download", "mg_reads_free",
+    "mg_genomes_parse_dev", "mg_genomes_count", "mg_genomes_nbases", "mg_genomes_device_ptrs", "mg_genomes_download", "mg_genomes_free",
+    "mg_genomes_stream_open", "mg_genomes_stream_next", "mg_genomes_stream_stats", "mg_genomes_stream_close",
+    "mg_sketch_genomes_dev", "mg_sketch_genomes_prefix_dev", "mg_sketch_genomes_kmers_dev",
     "mg_acc_index_build", "mg_acc_index_free", "mg_sam_tokenize_dev", "mg_sam_tokenize", "mg_paf_tokenize_dev", "mg_paf_tokenize", "mg_sam_stream_file", "mg_bam_stream_file", "mg_bam_tokenize_dev", "mg_sam_batch_count",
     "mg_sam_batch_last_qname", "mg_sam_batch_device_ptr", "mg_sam_batch_download", "mg_sam_batch_free",
     "mg_sam_tokenize_keyed_dev", "mg_bam_tokenize_keyed_dev", "mg_sam_batch_keys_download", "mg_collate_order_dev", "mg_sam_batch_collate_dev",
@@ -86,10 +89,10 @@ def load_library(path=LIB_PATH):
             "(hipcc --offload-arch=gfx950). There is no CPU fallback." % path)
     lib = ctypes.CDLL(path)
     lib.mg_last_error.restype = ctypes.c_char_p
-    for name in ("mg_reads_count", "mg_reads_nbases", "mg_sam_batch_count", "mg_sketch_stream_nreads", "mg_sketch_stream_nbases"):
+    for name in ("mg_reads_count", "mg_reads_nbases", "mg_genomes_count", "mg_genomes_nbases", "mg_sam_batch_count", "mg_sketch_stream_nreads", "mg_sketch_stream_nbases"):
         getattr(lib, name).restype = ctypes.c_uint64
     lib.mg_sam_batch_last_qname.restype = ctypes.c_char_p
-    for name in ("mg_reads_free", "mg_acc_index_free", "mg_sam_batch_free"):
+    for name in ("mg_reads_free", "mg_genomes_free", "mg_genomes_stream_close", "mg_acc_index_free", "mg_sam_batch_free"):
         getattr(lib, name).restype = None
     for name in ("mg_sketch_size", "mg_sketch_kmers_seen", "mg_sketch_last_hash", "mg_db_ngenomes", "mg_db_max_hash", "mg_profile_ngroups"):
         getattr(lib, name).restype = ctypes.c_uint64
@@ -503,6 +506,48 @@ class Reads:
     def free(self):
         if self.handle:
             self.hip.lib.mg_reads_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class Genomes:
+    """Device-resident genomes, ONE PER ORGANISM FILE (bases + offsets), produced by the on-device parser of organism FASTA files
+    (mg_genomes_parse_dev; the definition is build_db.genome_bases).  `undecided`: per file, 1 = the file holds a byte on which
+    Python's text mode and the device's byte rules part — what the batch holds for it is void and the caller parses that file
+    with genome_bases."""
+
+    def __init__(self, hip, handle, undecided, first_file=0):
+        self.hip, self.handle = hip, handle
+        self.undecided = undecided
+        self.first_file = first_file
+
+    @property
+    def count(self):
+        return int(self.hip.lib.mg_genomes_count(self.handle))
+
+    @property
+    def nbases(self):
+        return int(self.hip.lib.mg_genomes_nbases(self.handle))
+
+    def device_ptrs(self):
+        b, o = _vp(), _vp()
+        self.hip._chk(self.hip.lib.mg_genomes_device_ptrs(self.handle, ctypes.byref(b), ctypes.byref(o)))
+        return b.value, o.value
+
+    def download(self):
+        bases = np.empty(max(self.nbases, 1), dtype=np.uint8)
+        offs = np.empty(self.count + 1, dtype=np.uint64)
+        self.hip._chk(self.hip.lib.mg_genomes_download(self.handle, _np(bases, ctypes.c_uint8), _np(offs, ctypes.c_uint64)))
+        return bases[: self.nbases], offs
+
+    def free(self):
+        if self.handle:
+            self.hip.lib.mg_genomes_free(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -950,6 +995,10 @@ class Hip:
         else:
             self._chk(self.lib.mg_init_on_stream(ctypes.c_int(device), _vp(stream)))
         self.device = device
+        # `build_db --ingest device`: the files of the last build that were parsed on the host (undecided on the device), and the
+        # seconds of the last genome_batches stream's phases
+        self.genomes_host_parsed = 0
+        self.genome_stream_stats = None
 
     @classmethod
     def get(cls, device=None, stream=None):
@@ -1284,6 +1333,42 @@ class Hip:
                                               ctypes.c_int(_READS_FORMAT[fmt]), ctypes.byref(h)))
         return Reads(self, h)
 
+    def parse_genomes_dev(self, d_text, file_extents):
+        """The text of organism files back to back in HBM, file f = bytes [file_extents[f], file_extents[f + 1]) -> Genomes, one
+        per file (mg_genomes_parse_dev)."""
+        ext = np.ascontiguousarray(file_extents, dtype=np.uint64)
+        nfiles = len(ext) - 1
+        und = np.zeros(max(nfiles, 1), dtype=np.uint8)
+        h = _vp()
+        self._chk(self.lib.mg_genomes_parse_dev(_vp(d_text), _np(ext, ctypes.c_uint64), ctypes.c_uint64(nfiles), ctypes.byref(h),
+                                                _np(und, ctypes.c_uint8)))
+        return Genomes(self, h, und[:nfiles])
+
+    def genome_batches(self, paths, batch_bases=1 << 27, nthreads=0):
+        """Organism files -> Genomes batches in file order, each closed at a file boundary once it holds batch_bases bytes of text
+        (mg_genomes_stream_*: reader threads read / inflate whole files into page-locked slabs, the next batch goes up while the
+        caller works on this one).  A batch's files are paths[batch.first_file : batch.first_file + batch.count]; the caller frees
+        it.  A file that cannot be read or a broken `.gz` raises HipError with the path.  self.genome_stream_stats: the seconds of
+        the last stream's phases (mg_genomes_stream_stats)."""
+        paths = [os.fsencode(p) for p in paths]
+        c_paths = (ctypes.c_char_p * max(len(paths), 1))(*paths)
+        h = _vp()
+        self._chk(self.lib.mg_genomes_stream_open(c_paths, ctypes.c_uint64(len(paths)), ctypes.c_uint64(int(batch_bases)),
+                                                  ctypes.c_int(int(nthreads)), ctypes.byref(h)))
+        try:
+            und = np.zeros(max(len(paths), 1), dtype=np.uint8)
+            while True:
+                g, first, nf = _vp(), ctypes.c_uint64(0), ctypes.c_uint64(0)
+                self._chk(self.lib.mg_genomes_stream_next(h, ctypes.byref(g), ctypes.byref(first), ctypes.byref(nf), _np(und, ctypes.c_uint8)))
+                if not g.value:
+                    break
+                yield Genomes(self, g, und[: nf.value].copy(), int(first.value))
+        finally:
+            st = (ctypes.c_double * 5)()
+            self.lib.mg_genomes_stream_stats(h, st)
+            self.genome_stream_stats = dict(read_inflate_s=st[0], upload_s=st[1], wait_s=st[2], parse_s=st[3], text_bytes=int(st[4]))
+            self.lib.mg_genomes_stream_close(h)
+
     def parse_bam_reads_dev(self, d_bytes, nbytes, n_ref, final=True):
         """BAM record bytes resident in HBM (behind the header) -> (Reads, consumed) (mg_reads_parse_bam_prefix_dev): the reads
         `samtools fastq` writes for them.  A break in the record chain raises HipError whose `err_at` is its byte."""
@@ -1480,6 +1565,35 @@ class Hip:
         out_o = np.zeros(g + 1, dtype=np.uint64)
         self._chk(fn(_np(bases, ctypes.c_uint8), _np(offsets, ctypes.c_uint64), ctypes.c_uint64(g), ctypes.c_int(k), ctypes.c_uint64(n),
                      _np(out_h, ctypes.c_uint64), _np(out_hi, ctypes.c_uint64), _np(out_lo, ctypes.c_uint64), _np(out_o, ctypes.c_uint64)))
+        e = int(out_o[-1])
+        return out_h[:e].copy(), out_hi[:e].copy(), out_lo[:e].copy(), out_o
+
+    # ... of a batch already parsed in HBM (Genomes): the same results without the upload, one batch for every k
+    def sketch_genomes_dev(self, genomes, k, n):
+        g = genomes.count
+        out_h = np.zeros(max(g * n, 1), dtype=np.uint64)
+        out_o = np.zeros(g + 1, dtype=np.uint64)
+        self._chk(self.lib.mg_sketch_genomes_dev(genomes.handle, ctypes.c_int(k), ctypes.c_uint64(n),
+                                                 _np(out_h, ctypes.c_uint64), _np(out_o, ctypes.c_uint64)))
+        return out_h[: int(out_o[-1])].copy(), out_o
+
+    def sketch_genomes_prefix_dev(self, genomes, kmax, k, n):
+        g = genomes.count
+        out_h = np.zeros(max(g * n, 1), dtype=np.uint64)
+        out_o = np.zeros(g + 1, dtype=np.uint64)
+        self._chk(self.lib.mg_sketch_genomes_prefix_dev(genomes.handle, ctypes.c_int(kmax), ctypes.c_int(k), ctypes.c_uint64(n),
+                                                        _np(out_h, ctypes.c_uint64), _np(out_o, ctypes.c_uint64)))
+        return out_h[: int(out_o[-1])].copy(), out_o
+
+    def sketch_genomes_kmers_dev(self, genomes, k, n, sketch_hash="canonical"):
+        if sketch_hash not in ("canonical", "forward"):
+            raise ValueError("sketch_hash: 'canonical' or 'forward'")
+        g = genomes.count
+        out_h, out_hi, out_lo = (np.zeros(max(g * n, 1), dtype=np.uint64) for _ in range(3))
+        out_o = np.zeros(g + 1, dtype=np.uint64)
+        self._chk(self.lib.mg_sketch_genomes_kmers_dev(genomes.handle, ctypes.c_int(k), ctypes.c_uint64(n),
+                                                       ctypes.c_int(1 if sketch_hash == "forward" else 0), _np(out_h, ctypes.c_uint64),
+                                                       _np(out_hi, ctypes.c_uint64), _np(out_lo, ctypes.c_uint64), _np(out_o, ctypes.c_uint64)))
         e = int(out_o[-1])
         return out_h[:e].copy(), out_hi[:e].copy(), out_lo[:e].copy(), out_o
 

@@ -303,6 +303,13 @@ struct mg_reads {
   uint64_t nreads = 0, nbases = 0;
 };
 
+// One genome per organism file (mg_genome.hip).  The offsets are kept on the host too: the sketchers cut their batches by them.
+struct mg_genomes {
+  mg::DevBuf bases, offsets;
+  uint64_t ngenomes = 0, nbases = 0;
+  std::vector<uint64_t> h_offsets;  // u64[ngenomes + 1]
+};
+
 struct mg_acc_index {
   mg::DevBuf slot_hash, slot_row, names, name_off;
   std::map<std::string, uint32_t> host_rows;  // (the same names on the host: a BAM header's references are looked up there)

@@ -1809,31 +1809,38 @@ __global__ __launch_bounds__(256) void k_entry_identity(const uint64_t* __restri
 
 }  // namespace mg
 
-extern "C" {
+// Where a batch's bases come from: a host array (uploaded to scratch, batch by batch) or a parsed batch already in HBM (mg_genomes).
+struct GenomeBases {
+  const uint8_t* host = nullptr;
+  const uint8_t* dev = nullptr;
+};
+// ... bases [at, at + nb) of it on the device
+static int genome_bases_dev(const GenomeBases& src, uint64_t at, uint64_t nb, hipStream_t st, const uint8_t** d_bases) {
+  if (src.dev) { *d_bases = src.dev + at; return MG_OK; }
+  uint8_t* d = (uint8_t*)scratch("g_bases", nb + 16);
+  if (!d) return MG_ERR_NOMEM;
+  if (nb) MG_HIP(hipMemcpyAsync(d, src.host + at, nb, hipMemcpyHostToDevice, st));
+  *d_bases = d;
+  return MG_OK;
+}
 
-int mg_sketch_genomes_prefix(const uint8_t* bases, const uint64_t* offsets, uint64_t ngenomes, int kmax, int k, uint64_t n,
-                             uint64_t* out_hashes, uint64_t* out_offsets) {
-  MG_REQUIRE_READY();
-  if (!offsets || !out_offsets) return fail(MG_ERR_ARG, "null argument");
-  if (kmax < 1 || kmax > MG_MAX_K || k < 1 || k > kmax) return fail(MG_ERR_ARG, "need 1 <= k=%d <= kmax=%d <= %d", k, kmax, MG_MAX_K);
-  if (n == 0) return fail(MG_ERR_ARG, "n must be positive");
+// a parsed batch as the sketchers take it
+static int genomes_src(const mg_genomes* g, GenomeBases* src) {
+  if (!g) return fail(MG_ERR_ARG, "null genomes");
+  src->dev = g->bases.as<uint8_t>();
+  return MG_OK;
+}
+
+// The batch body of mg_sketch_genomes_prefix (arguments as sketch_genomes_batch's)
+static int sketch_prefix_batch(const uint8_t* d_bases, uint64_t* d_off, const uint64_t* rel, uint64_t ng, uint64_t nb, int kmax, int k,
+                               uint64_t n, uint64_t* out_hashes, uint64_t* out_offsets, uint64_t* written_io) {
   Context& c = ctx();
   hipStream_t st = c.stream;
-  out_offsets[0] = 0;
-  const uint64_t kBatchBases = 1ull << 27;
-  uint64_t g0 = 0, written = 0;
-  std::vector<uint64_t> h_slots, rel, seg;
+  uint64_t written = *written_io;
+  std::vector<uint64_t> h_slots, seg(ng + 1);
   std::vector<uint32_t> h_cnt;
-  while (g0 < ngenomes) {
-    uint64_t g1 = g0 + 1;
-    while (g1 < ngenomes && offsets[g1 + 1] - offsets[g0] <= kBatchBases && g1 - g0 < (1u << 20)) ++g1;
-    const uint64_t ng = g1 - g0, nb = offsets[g1] - offsets[g0];
-    if (nb > 0xffffffffull) return fail(MG_ERR_ARG, "single genome of %llu bases exceeds 2^32-1", (unsigned long long)nb);
-    rel.resize(ng + 1);
-    seg.resize(ng + 1);
-    for (uint64_t i = 0; i <= ng; ++i) { rel[i] = offsets[g0 + i] - offsets[g0]; seg[i] = i * n; }
-    uint8_t* d_bases = (uint8_t*)scratch("g_bases", nb + 16);
-    uint64_t* d_off = (uint64_t*)scratch("g_off", (ng + 1) * sizeof(uint64_t));
+  for (uint64_t i = 0; i <= ng; ++i) seg[i] = i * n;
+  {
     uint64_t* d_seg = (uint64_t*)scratch("gp_seg", (ng + 1) * sizeof(uint64_t));
     uint64_t* d_tag = (uint64_t*)scratch("gp_tag", (nb + 1) * sizeof(uint64_t));
     uint64_t* d_hk = (uint64_t*)scratch("gp_hk", (nb + 1) * sizeof(uint64_t));
@@ -1845,11 +1852,10 @@ int mg_sketch_genomes_prefix(const uint8_t* bases, const uint64_t* offsets, uint
     uint64_t* d_keys_sorted = (uint64_t*)scratch("gp_keys_sorted", ng * n * sizeof(uint64_t));
     uint64_t* d_out2 = (uint64_t*)scratch("gp_out", ng * n * sizeof(uint64_t));
     uint32_t* d_cnt2 = (uint32_t*)scratch("gp_cnt", ng * sizeof(uint32_t));
-    if (!d_bases || !d_off || !d_seg || !d_tag || !d_hk || !d_pos || !d_sorted || !d_out || !d_cnt || !d_keys || !d_keys_sorted ||
+    if (!d_seg || !d_tag || !d_hk || !d_pos || !d_sorted || !d_out || !d_cnt || !d_keys || !d_keys_sorted ||
         !d_out2 || !d_cnt2)
       return MG_ERR_NOMEM;
-    if (nb) MG_HIP(hipMemcpyAsync(d_bases, bases + offsets[g0], nb, hipMemcpyHostToDevice, st));
-    MG_HIP(hipMemcpyAsync(d_off, rel.data(), (ng + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    MG_HIP(hipMemcpyAsync(d_off, rel, (ng + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     MG_HIP(hipMemcpyAsync(d_seg, seg.data(), (ng + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     const unsigned g256 = grid_for(nb ? nb : 1, 256, (unsigned)c.num_cus * 8);
     if (nb) {
@@ -1882,32 +1888,23 @@ int mg_sketch_genomes_prefix(const uint8_t* bases, const uint64_t* offsets, uint
     for (uint64_t i = 0; i < ng; ++i) {
       for (uint32_t j = 0; j < h_cnt[i]; ++j) out_hashes[written + j] = h_slots[i * n + j];
       written += h_cnt[i];
-      out_offsets[g0 + i + 1] = written;
+      out_offsets[i + 1] = written;
     }
-    g0 = g1;
   }
+  *written_io = written;
   return MG_OK;
 }
 
-}  // extern "C"
-
-// mg_sketch_genomes, and (out_khi / out_klo given) mg_sketch_genomes_kmers
-// forward_select (with the k-mers only): the n smallest MurmurHash3(k-mer as it stands) mod the prime select a genome's entries, the
-// k-mer is kept as it stands, and out_hashes = what it matches by (the mode in force) — neither ascending nor necessarily distinct
-// within a genome (a genome may hold a k-mer and its reverse complement).  oracle: mgo_sketch_genomes_kmers_forward
-static int sketch_genomes_impl(const uint8_t* bases, const uint64_t* offsets, uint64_t ngenomes, int k, uint64_t n,
-                               uint64_t* out_hashes, uint64_t* out_khi, uint64_t* out_klo, uint64_t* out_offsets, bool forward_select = false) {
+static int sketch_genomes_prefix_impl(const GenomeBases& src, const uint64_t* offsets, uint64_t ngenomes, int kmax, int k, uint64_t n,
+                                      uint64_t* out_hashes, uint64_t* out_offsets) {
   MG_REQUIRE_READY();
   if (!offsets || !out_offsets) return fail(MG_ERR_ARG, "null argument");
-  if (k < 1 || k > MG_MAX_K) return fail(MG_ERR_ARG, "k=%d outside [1,%d]", k, MG_MAX_K);
+  if (kmax < 1 || kmax > MG_MAX_K || k < 1 || k > kmax) return fail(MG_ERR_ARG, "need 1 <= k=%d <= kmax=%d <= %d", k, kmax, MG_MAX_K);
   if (n == 0) return fail(MG_ERR_ARG, "n must be positive");
-  Context& c = ctx();
-  hipStream_t st = c.stream;
+  hipStream_t st = ctx().stream;
   out_offsets[0] = 0;
-  const uint64_t kBatchBases = 1ull << 28;  // 2 GiB of position hashes per batch
+  const uint64_t kBatchBases = 1ull << 27;
   uint64_t g0 = 0, written = 0;
-  std::vector<uint64_t> h_slots, h_hi, h_lo;
-  std::vector<uint32_t> h_cnt;
   std::vector<uint64_t> rel;
   while (g0 < ngenomes) {
     uint64_t g1 = g0 + 1;
@@ -1916,13 +1913,47 @@ static int sketch_genomes_impl(const uint8_t* bases, const uint64_t* offsets, ui
     if (nb > 0xffffffffull) return fail(MG_ERR_ARG, "single genome of %llu bases exceeds 2^32-1", (unsigned long long)nb);
     rel.resize(ng + 1);
     for (uint64_t i = 0; i <= ng; ++i) rel[i] = offsets[g0 + i] - offsets[g0];
-    uint8_t* d_bases = (uint8_t*)scratch("g_bases", nb + 16);
     uint64_t* d_off = (uint64_t*)scratch("g_off", (ng + 1) * sizeof(uint64_t));
+    if (!d_off) return MG_ERR_NOMEM;
+    const uint8_t* d_bases = nullptr;
+    MG_TRY(genome_bases_dev(src, offsets[g0], nb, st, &d_bases));
+    MG_TRY(sketch_prefix_batch(d_bases, d_off, rel.data(), ng, nb, kmax, k, n, out_hashes, out_offsets + g0, &written));
+    g0 = g1;
+  }
+  return MG_OK;
+}
+
+extern "C" {
+
+int mg_sketch_genomes_prefix(const uint8_t* bases, const uint64_t* offsets, uint64_t ngenomes, int kmax, int k, uint64_t n,
+                             uint64_t* out_hashes, uint64_t* out_offsets) {
+  return sketch_genomes_prefix_impl(GenomeBases{bases, nullptr}, offsets, ngenomes, kmax, k, n, out_hashes, out_offsets);
+}
+
+int mg_sketch_genomes_prefix_dev(const mg_genomes* g, int kmax, int k, uint64_t n, uint64_t* out_hashes, uint64_t* out_offsets) {
+  GenomeBases src;
+  MG_TRY(genomes_src(g, &src));
+  return sketch_genomes_prefix_impl(src, g->h_offsets.data(), g->ngenomes, kmax, k, n, out_hashes, out_offsets);
+}
+
+}  // extern "C"
+
+// The batch body of mg_sketch_genomes / _kmers / _kmers_forward: ng genomes, nb bases at d_bases; rel = their offsets from the
+// batch's first base on the host, d_off = room for them on the device.  out_offsets = the entry of the batch's first genome.
+static int sketch_genomes_batch(const uint8_t* d_bases, uint64_t* d_off, const uint64_t* rel, uint64_t ng, uint64_t nb, int k, uint64_t n,
+                                uint64_t* out_hashes, uint64_t* out_khi, uint64_t* out_klo, uint64_t* out_offsets, uint64_t* written_io,
+                                bool forward_select) {
+  Context& c = ctx();
+  hipStream_t st = c.stream;
+  uint64_t written = *written_io;
+  std::vector<uint64_t> h_slots, h_hi, h_lo;
+  std::vector<uint32_t> h_cnt;
+  {
     uint64_t* d_pos = (uint64_t*)scratch("g_pos", (nb + 1) * sizeof(uint64_t));
     uint64_t* d_sorted = (uint64_t*)scratch("g_sorted", (nb + 1) * sizeof(uint64_t));
     uint64_t* d_out = (uint64_t*)scratch("g_out", ng * n * sizeof(uint64_t));
     uint32_t* d_cnt = (uint32_t*)scratch("g_cnt", ng * sizeof(uint32_t));
-    if (!d_bases || !d_off || !d_pos || !d_sorted || !d_out || !d_cnt) return MG_ERR_NOMEM;
+    if (!d_pos || !d_sorted || !d_out || !d_cnt) return MG_ERR_NOMEM;
     const bool kmers = out_khi != nullptr;
     const bool tagged = kmers && !forward_select && ctx().hash_mode == kHashCmash;  // the kept strand rides in bit 63 of the position hashes
     uint64_t* d_key = d_pos;  // what is sorted (the untagged hashes)
@@ -1938,8 +1969,7 @@ static int sketch_genomes_impl(const uint8_t* bases, const uint64_t* offsets, ui
       d_klo = (uint64_t*)scratch("gk_lo", ng * n * sizeof(uint64_t));
       if (!d_first || !d_khi || !d_klo) return MG_ERR_NOMEM;
     }
-    if (nb) MG_HIP(hipMemcpyAsync(d_bases, bases + offsets[g0], nb, hipMemcpyHostToDevice, st));
-    MG_HIP(hipMemcpyAsync(d_off, rel.data(), (ng + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    MG_HIP(hipMemcpyAsync(d_off, rel, (ng + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     const unsigned g256 = grid_for(nb ? nb : 1, 256, (unsigned)c.num_cus * 8);
     if (nb) {
       ProfScope ps("hash_positions");
@@ -2006,8 +2036,41 @@ static int sketch_genomes_impl(const uint8_t* bases, const uint64_t* offsets, ui
         if (kmers) { out_khi[written + j] = h_hi[i * n + j]; out_klo[written + j] = h_lo[i * n + j]; }
       }
       written += h_cnt[i];
-      out_offsets[g0 + i + 1] = written;
+      out_offsets[i + 1] = written;
     }
+  }
+  *written_io = written;
+  return MG_OK;
+}
+
+// mg_sketch_genomes, and (out_khi / out_klo given) mg_sketch_genomes_kmers
+// forward_select (with the k-mers only): the n smallest MurmurHash3(k-mer as it stands) mod the prime select a genome's entries, the
+// k-mer is kept as it stands, and out_hashes = what it matches by (the mode in force) — neither ascending nor necessarily distinct
+// within a genome (a genome may hold a k-mer and its reverse complement).  oracle: mgo_sketch_genomes_kmers_forward
+static int sketch_genomes_impl(const GenomeBases& src, const uint64_t* offsets, uint64_t ngenomes, int k, uint64_t n,
+                               uint64_t* out_hashes, uint64_t* out_khi, uint64_t* out_klo, uint64_t* out_offsets, bool forward_select = false) {
+  MG_REQUIRE_READY();
+  if (!offsets || !out_offsets) return fail(MG_ERR_ARG, "null argument");
+  if (k < 1 || k > MG_MAX_K) return fail(MG_ERR_ARG, "k=%d outside [1,%d]", k, MG_MAX_K);
+  if (n == 0) return fail(MG_ERR_ARG, "n must be positive");
+  hipStream_t st = ctx().stream;
+  out_offsets[0] = 0;
+  const uint64_t kBatchBases = 1ull << 28;  // 2 GiB of position hashes per batch
+  uint64_t g0 = 0, written = 0;
+  std::vector<uint64_t> rel;
+  while (g0 < ngenomes) {
+    uint64_t g1 = g0 + 1;
+    while (g1 < ngenomes && offsets[g1 + 1] - offsets[g0] <= kBatchBases && g1 - g0 < (1u << 20)) ++g1;
+    const uint64_t ng = g1 - g0, nb = offsets[g1] - offsets[g0];
+    if (nb > 0xffffffffull) return fail(MG_ERR_ARG, "single genome of %llu bases exceeds 2^32-1", (unsigned long long)nb);
+    rel.resize(ng + 1);
+    for (uint64_t i = 0; i <= ng; ++i) rel[i] = offsets[g0 + i] - offsets[g0];
+    uint64_t* d_off = (uint64_t*)scratch("g_off", (ng + 1) * sizeof(uint64_t));
+    if (!d_off) return MG_ERR_NOMEM;
+    const uint8_t* d_bases = nullptr;
+    MG_TRY(genome_bases_dev(src, offsets[g0], nb, st, &d_bases));
+    MG_TRY(sketch_genomes_batch(d_bases, d_off, rel.data(), ng, nb, k, n, out_hashes, out_khi, out_klo, out_offsets + g0, &written,
+                                forward_select));
     g0 = g1;
   }
   return MG_OK;
@@ -2015,21 +2078,35 @@ static int sketch_genomes_impl(const uint8_t* bases, const uint64_t* offsets, ui
 
 extern "C" {
 
+int mg_sketch_genomes_dev(const mg_genomes* g, int k, uint64_t n, uint64_t* out_hashes, uint64_t* out_offsets) {
+  GenomeBases src;
+  MG_TRY(genomes_src(g, &src));
+  return sketch_genomes_impl(src, g->h_offsets.data(), g->ngenomes, k, n, out_hashes, nullptr, nullptr, out_offsets);
+}
+
+int mg_sketch_genomes_kmers_dev(const mg_genomes* g, int k, uint64_t n, int forward, uint64_t* out_hashes, uint64_t* out_kmer_hi,
+                                uint64_t* out_kmer_lo, uint64_t* out_offsets) {
+  if (!out_kmer_hi || !out_kmer_lo) return fail(MG_ERR_ARG, "null argument");
+  GenomeBases src;
+  MG_TRY(genomes_src(g, &src));
+  return sketch_genomes_impl(src, g->h_offsets.data(), g->ngenomes, k, n, out_hashes, out_kmer_hi, out_kmer_lo, out_offsets, forward != 0);
+}
+
 int mg_sketch_genomes(const uint8_t* bases, const uint64_t* offsets, uint64_t ngenomes, int k, uint64_t n,
                       uint64_t* out_hashes, uint64_t* out_offsets) {
-  return sketch_genomes_impl(bases, offsets, ngenomes, k, n, out_hashes, nullptr, nullptr, out_offsets);
+  return sketch_genomes_impl(GenomeBases{bases, nullptr}, offsets, ngenomes, k, n, out_hashes, nullptr, nullptr, out_offsets);
 }
 
 int mg_sketch_genomes_kmers(const uint8_t* bases, const uint64_t* offsets, uint64_t ngenomes, int k, uint64_t n,
                             uint64_t* out_hashes, uint64_t* out_kmer_hi, uint64_t* out_kmer_lo, uint64_t* out_offsets) {
   if (!out_kmer_hi || !out_kmer_lo) return fail(MG_ERR_ARG, "null argument");
-  return sketch_genomes_impl(bases, offsets, ngenomes, k, n, out_hashes, out_kmer_hi, out_kmer_lo, out_offsets);
+  return sketch_genomes_impl(GenomeBases{bases, nullptr}, offsets, ngenomes, k, n, out_hashes, out_kmer_hi, out_kmer_lo, out_offsets);
 }
 
 int mg_sketch_genomes_kmers_forward(const uint8_t* bases, const uint64_t* offsets, uint64_t ngenomes, int k, uint64_t n,
                                     uint64_t* out_hashes, uint64_t* out_kmer_hi, uint64_t* out_kmer_lo, uint64_t* out_offsets) {
   if (!out_kmer_hi || !out_kmer_lo) return fail(MG_ERR_ARG, "null argument");
-  return sketch_genomes_impl(bases, offsets, ngenomes, k, n, out_hashes, out_kmer_hi, out_kmer_lo, out_offsets, true);
+  return sketch_genomes_impl(GenomeBases{bases, nullptr}, offsets, ngenomes, k, n, out_hashes, out_kmer_hi, out_kmer_lo, out_offsets, true);
 }
 
 }  // extern "C"

@@ -28,6 +28,9 @@
 //
 // and reader_threads says how many readers the host pipeline gets.  What an entry point adds is its StreamPlan (data), its
 // consumer, a BAM file's header (skip_bam_header) and the assembly of its result.
+//
+// The organism files of `build_db --ingest device` are MANY files, each one genome: mg_genomes_stream (at the end of this file)
+// gives every reader thread whole files and the same page-locked slots and copy stream.
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -37,9 +40,12 @@
 #endif
 
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <cstring>
+#include <deque>
 #include <functional>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -1184,6 +1190,372 @@ int mg_stream_thin_file(const char* path, int kind, uint64_t piece_bytes, int nt
   for (auto& o : outs) ok = ok && (o.empty() || fwrite(o.data(), 1, o.size(), fo) == o.size());
   ok = (fclose(fo) == 0) && ok;
   return ok ? MG_OK : fail(MG_ERR_ARG, "writing %s failed", out_path);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// organism files -> batches of genomes (mg_genomes_stream_*; `build_db --ingest device`)
+// ---------------------------------------------------------------------------------------------------------------------
+// Reader threads take WHOLE files in the order of the list (hundreds of thousands of them: parallelism across files is free) and
+// leave each as a run of page-locked slabs — a plain file by positional reads, a ".gz" inflated by that thread with zlib, every
+// member of it.  ONE uploader thread takes the slabs in file order and queues them on the copy stream into the text buffer of the
+// batch it is filling (two buffers: batch i + 1 goes up while the caller parses and sketches batch i), closes the batch at a file
+// boundary once it holds batch_bases bytes, and hands it to mg_genomes_stream_next, which parses it on the library stream.
+// A slab goes to the reader of the file the uploader is waiting for, or to any reader while two are free: later files never
+// starve the one everything waits for.  The text buffers are the uploader thread's own (hipMalloc: the pool is the caller
+// thread's), so no block the main stream may still use is written on the copy stream; a buffer is written again only behind
+// the event the main stream records after parsing its previous batch.
+// Inflating these files ON THE DEVICE is not done: DevInflater takes one stream per call and does not tell which member ends
+// belong to which file of a concatenation (DESIGN.md §8 f2').
+struct mg_genomes_stream {
+  struct Piece { int slab; uint64_t bytes; };
+  struct FileQ { std::deque<Piece> pieces; bool done = false; };
+  struct Batch { int buf = 0; const uint8_t* text = nullptr; std::vector<uint64_t> ext; uint64_t first = 0; };
+  std::vector<std::string> paths;
+  uint64_t batch_bases = 0, slab_bytes = 0;
+  size_t nslots = 0;
+  int device = 0;
+  std::mutex m;
+  std::condition_variable cv;
+  // (under m)
+  uint64_t next_file = 0, head = 0;  // the next file a reader takes; the file the uploader is at
+  bool stop = false, failed = false, end = false;
+  std::string error;
+  std::vector<int> free_slabs;
+  std::map<uint64_t, FileQ> active;
+  std::deque<Batch> ready;
+  uint64_t parsed = 0;  // batches whose parse has been queued on the library stream
+  double read_s = 0, upload_s = 0, wait_s = 0, parse_s = 0;
+  uint64_t text_bytes = 0;
+  // (the uploader thread's)
+  uint8_t* dtext[2] = {nullptr, nullptr};
+  uint64_t cap[2] = {0, 0};
+  std::vector<char> slab_used;  // (a slab's event has been recorded: under m with free_slabs)
+  std::vector<std::thread> readers;
+  std::thread uploader;
+};
+
+namespace mg {
+
+using GS = mg_genomes_stream;
+using Clock = std::chrono::steady_clock;
+static double secs_since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
+
+static void gs_fail(GS* h, const std::string& msg) {
+  std::lock_guard<std::mutex> lk(h->m);
+  if (!h->failed) { h->failed = true; h->error = msg; }
+  h->stop = true;
+  h->cv.notify_all();
+}
+
+// a free slab for the reader of file i (-1: the stream stops); *waited += the seconds spent waiting for one
+static int gs_acquire(GS* h, uint64_t i, double* waited) {
+  int s = -1;
+  bool used = false;
+  const Clock::time_point t0 = Clock::now();
+  struct Waited { double* w; Clock::time_point t0; ~Waited() { *w += secs_since(t0); } } add{waited, t0};
+  {
+    std::unique_lock<std::mutex> lk(h->m);
+    h->cv.wait(lk, [&] { return h->stop || (!h->free_slabs.empty() && (i == h->head || h->free_slabs.size() >= 2)); });
+    if (h->stop) return -1;
+    s = h->free_slabs.back();
+    h->free_slabs.pop_back();
+    used = h->slab_used[s] != 0;
+  }
+  if (used) (void)hipEventSynchronize(g_res.ev_slot[s]);  // its last copy has left it
+  return s;
+}
+
+static void gs_push(GS* h, uint64_t i, int slab, uint64_t bytes, bool done) {
+  std::lock_guard<std::mutex> lk(h->m);
+  GS::FileQ& q = h->active[i];
+  if (slab >= 0) {
+    if (bytes) q.pieces.push_back(GS::Piece{slab, bytes});
+    else h->free_slabs.push_back(slab);
+  }
+  q.done = q.done || done;
+  h->cv.notify_all();
+}
+
+// file i -> slabs; false = failed (the error is set) or stopped
+static bool gs_read_file(GS* h, uint64_t i, std::vector<uint8_t>& in, double* waited) {
+  const std::string& path = h->paths[i];
+  const int fd = open(path.c_str(), O_RDONLY);
+  if (fd < 0) { gs_fail(h, "cannot open " + path + ": " + strerror(errno)); return false; }
+  struct Closer { int fd; ~Closer() { close(fd); } } closer{fd};
+  const bool gz = path.size() >= 3 && path.compare(path.size() - 3, 3, ".gz") == 0;  // (what formats.read_sequences goes by)
+  if (!gz) {
+    struct stat sb;
+    if (fstat(fd, &sb) != 0) { gs_fail(h, "cannot stat " + path + ": " + strerror(errno)); return false; }
+    const uint64_t size = (uint64_t)sb.st_size;
+    for (uint64_t at = 0; at < size;) {
+      const int s = gs_acquire(h, i, waited);
+      if (s < 0) return false;
+      const uint64_t want = size - at < h->slab_bytes ? size - at : h->slab_bytes;
+      uint64_t got = 0;
+      while (got < want) {
+        const ssize_t n = pread(fd, g_res.slots[s] + got, want - got, (off_t)(at + got));
+        if (n < 0) { gs_fail(h, path + ": read failed: " + strerror(errno)); return false; }
+        if (n == 0) { gs_fail(h, path + ": file is shorter than its size said"); return false; }
+        got += (uint64_t)n;
+      }
+      at += want;
+      gs_push(h, i, s, want, at >= size);
+    }
+    if (size == 0) gs_push(h, i, -1, 0, true);
+    return true;
+  }
+  z_stream zs;
+  memset(&zs, 0, sizeof(zs));
+  if (inflateInit2(&zs, 15 + 16) != Z_OK) { gs_fail(h, path + ": inflateInit2 failed"); return false; }
+  struct Ender { z_stream* z; ~Ender() { inflateEnd(z); } } ender{&zs};
+  uint64_t in_off = 0;
+  bool in_member = false, eof = false;  // between members only zero padding or another member may stand (Python's gzip module)
+  while (!eof) {
+    const int s = gs_acquire(h, i, waited);
+    if (s < 0) return false;
+    zs.next_out = g_res.slots[s];
+    uint64_t room = h->slab_bytes;
+    while (room > 0) {
+      if (zs.avail_in == 0) {
+        const ssize_t n = pread(fd, in.data(), in.size(), (off_t)in_off);
+        if (n < 0) { gs_fail(h, path + ": read failed: " + strerror(errno)); return false; }
+        if (n == 0) {
+          if (in_member) { gs_fail(h, path + ": unexpected end of file (the gzip stream ends inside a member)"); return false; }
+          eof = true;
+          break;
+        }
+        in_off += (uint64_t)n;
+        zs.next_in = in.data();
+        zs.avail_in = (uInt)n;
+      }
+      if (!in_member) {
+        while (zs.avail_in && zs.next_in[0] == 0) { ++zs.next_in; --zs.avail_in; }
+        if (!zs.avail_in) continue;
+        in_member = true;
+      }
+      zs.avail_out = (uInt)(room > 0x40000000ull ? 0x40000000ull : room);
+      const uInt before = zs.avail_out;
+      const int rc = inflate(&zs, Z_NO_FLUSH);
+      room -= before - zs.avail_out;
+      if (rc == Z_STREAM_END) {
+        in_member = false;
+        if (inflateReset(&zs) != Z_OK) { gs_fail(h, path + ": inflateReset failed"); return false; }
+      } else if (rc != Z_OK && rc != Z_BUF_ERROR) {
+        gs_fail(h, path + ": inflate failed: " + (zs.msg ? zs.msg : "corrupt gzip data"));
+        return false;
+      }
+    }
+    gs_push(h, i, s, h->slab_bytes - room, eof);
+  }
+  return true;
+}
+
+static void gs_reader(GS* h) {
+  (void)hipSetDevice(h->device);
+  std::vector<uint8_t> in(1u << 20);
+  for (;;) {
+    uint64_t i;
+    {
+      std::lock_guard<std::mutex> lk(h->m);
+      if (h->stop || h->next_file >= h->paths.size()) return;
+      i = h->next_file++;
+    }
+    const Clock::time_point t0 = Clock::now();
+    double waited = 0;
+    const bool ok = gs_read_file(h, i, in, &waited);
+    {
+      std::lock_guard<std::mutex> lk(h->m);
+      h->read_s += secs_since(t0) - waited;  // (read + inflate: not the wait for a free slab)
+    }
+    if (!ok) return;
+  }
+}
+
+static void gs_uploader(GS* h) {
+  (void)hipSetDevice(h->device);
+  StreamRes& r = g_res;
+  const uint64_t nfiles = h->paths.size();
+  auto hip_fail = [&](const char* what, hipError_t e) { gs_fail(h, std::string(what) + " failed: " + hipGetErrorString(e)); };
+  for (uint64_t b = 0;; ++b) {
+    const int buf = (int)(b & 1);
+    {
+      std::unique_lock<std::mutex> lk(h->m);
+      h->cv.wait(lk, [&] { return h->stop || b < 2 || h->parsed + 2 > b; });  // the buffer's previous batch has been parsed
+      if (h->stop) return;
+      if (h->head >= nfiles) { h->end = true; h->cv.notify_all(); return; }
+    }
+    hipError_t e = hipSuccess;
+    if (b >= 2 && (e = hipStreamWaitEvent(r.copy, r.ev_parsed[buf], 0)) != hipSuccess) { hip_fail("hipStreamWaitEvent", e); return; }
+    GS::Batch batch;
+    batch.buf = buf;
+    batch.ext.push_back(0);
+    uint64_t fill = 0;
+    {
+      std::lock_guard<std::mutex> lk(h->m);
+      batch.first = h->head;
+    }
+    for (;;) {  // file by file
+      bool file_done = false;
+      while (!file_done) {
+        GS::Piece pc{-1, 0};
+        {
+          std::unique_lock<std::mutex> lk(h->m);
+          GS::FileQ* q = nullptr;
+          h->cv.wait(lk, [&] {
+            if (h->stop) return true;
+            auto it = h->active.find(h->head);
+            if (it == h->active.end()) return false;
+            q = &it->second;
+            return !q->pieces.empty() || q->done;
+          });
+          if (h->stop) return;
+          if (!q->pieces.empty()) { pc = q->pieces.front(); q->pieces.pop_front(); }
+          else file_done = true;
+        }
+        if (file_done) break;
+        const Clock::time_point t0 = Clock::now();
+        if (fill + pc.bytes + 16 > h->cap[buf]) {  // (a file that outgrows the batch's room: rare, and paid with a device-wide wait)
+          uint64_t ncap = h->cap[buf] * 2;
+          if (ncap < fill + pc.bytes + 16) ncap = fill + pc.bytes + 16;
+          uint8_t* nt = nullptr;
+          if ((e = hipMalloc(reinterpret_cast<void**>(&nt), ncap)) != hipSuccess) { hip_fail("hipMalloc of a text buffer", e); return; }
+          if (fill) e = hipMemcpyAsync(nt, h->dtext[buf], fill, hipMemcpyDeviceToDevice, r.copy);
+          if (e == hipSuccess) e = hipStreamSynchronize(r.copy);
+          if (e != hipSuccess) { (void)hipFree(nt); hip_fail("growing a text buffer", e); return; }
+          (void)hipFree(h->dtext[buf]);
+          h->dtext[buf] = nt;
+          h->cap[buf] = ncap;
+        }
+        e = hipMemcpyAsync(h->dtext[buf] + fill, r.slots[pc.slab], pc.bytes, hipMemcpyHostToDevice, r.copy);
+        if (e == hipSuccess) e = hipEventRecord(r.ev_slot[pc.slab], r.copy);
+        if (e != hipSuccess) { hip_fail("the copy of a slab", e); return; }
+        fill += pc.bytes;
+        {
+          std::lock_guard<std::mutex> lk(h->m);
+          h->slab_used[pc.slab] = 1;
+          h->free_slabs.push_back(pc.slab);
+          h->upload_s += secs_since(t0);
+          h->text_bytes += pc.bytes;
+          h->cv.notify_all();
+        }
+      }
+      batch.ext.push_back(fill);
+      bool close_batch;
+      {
+        std::lock_guard<std::mutex> lk(h->m);
+        h->active.erase(h->head);
+        ++h->head;
+        close_batch = h->head >= nfiles || fill >= h->batch_bases;
+        h->cv.notify_all();  // (the reader of the new head may take the last free slab)
+      }
+      if (close_batch) break;
+    }
+    if ((e = hipEventRecord(r.ev_h2d[buf], r.copy)) != hipSuccess) { hip_fail("hipEventRecord", e); return; }
+    batch.text = h->dtext[buf];
+    {
+      std::lock_guard<std::mutex> lk(h->m);
+      h->ready.push_back(std::move(batch));
+      h->cv.notify_all();
+    }
+  }
+}
+
+}  // namespace mg
+
+extern "C" {
+
+void mg_genomes_stream_close(mg_genomes_stream* h) {
+  if (!h) return;
+  {
+    std::lock_guard<std::mutex> lk(h->m);
+    h->stop = true;
+    h->cv.notify_all();
+  }
+  for (auto& t : h->readers) if (t.joinable()) t.join();
+  if (h->uploader.joinable()) h->uploader.join();
+  if (g_res.copy) (void)hipStreamSynchronize(g_res.copy);
+  if (ctx().ready) (void)hipStreamSynchronize(ctx().stream);  // (a parse may still read the text)
+  for (int b = 0; b < 2; ++b) if (h->dtext[b]) (void)hipFree(h->dtext[b]);
+  delete h;
+}
+
+int mg_genomes_stream_open(const char* const* paths, uint64_t nfiles, uint64_t batch_bases, int nthreads, mg_genomes_stream** out) {
+  MG_REQUIRE_READY();
+  if (!out) return fail(MG_ERR_ARG, "null out handle");
+  *out = nullptr;
+  if (nfiles && !paths) return fail(MG_ERR_ARG, "null paths");
+  for (uint64_t i = 0; i < nfiles; ++i) if (!paths[i]) return fail(MG_ERR_ARG, "null path");
+  if (nthreads <= 0 || nthreads > 16) nthreads = 16;  // (never by the machine's core count)
+  if ((uint64_t)nthreads > nfiles) nthreads = nfiles ? (int)nfiles : 1;
+  uint64_t slab = dbg("genome_slab_bytes") > 0 ? (uint64_t)dbg("genome_slab_bytes") : (8ull << 20);
+  if (slab < 4096) slab = 4096;
+  slab = (slab + 4095) & ~4095ull;
+  std::unique_ptr<mg_genomes_stream, void (*)(mg_genomes_stream*)> h(new mg_genomes_stream(), mg_genomes_stream_close);
+  h->paths.assign(paths, paths + nfiles);
+  h->batch_bases = batch_bases ? batch_bases : (1ull << 27);
+  h->slab_bytes = slab;
+  h->nslots = (size_t)nthreads + 2;
+  h->device = ctx().device;
+  MG_TRY(ensure_res(slab, h->nslots));
+  MG_HIP(hipStreamSynchronize(g_res.copy));  // (slots and events of an earlier streaming call)
+  h->slab_used.assign(h->nslots, 0);
+  for (size_t s = 0; s < h->nslots; ++s) h->free_slabs.push_back((int)s);
+  for (int b = 0; b < 2; ++b) {
+    h->cap[b] = h->batch_bases + slab + 16;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->dtext[b]), h->cap[b]);
+    if (e != hipSuccess) return fail(MG_ERR_NOMEM, "hipMalloc(%llu) of a text buffer failed: %s", (unsigned long long)h->cap[b], hipGetErrorString(e));
+  }
+  mg_genomes_stream* raw = h.get();
+  for (int t = 0; t < nthreads; ++t) raw->readers.emplace_back(gs_reader, raw);
+  raw->uploader = std::thread(gs_uploader, raw);
+  *out = h.release();
+  return MG_OK;
+}
+
+int mg_genomes_stream_next(mg_genomes_stream* h, mg_genomes** batch, uint64_t* first_file, uint64_t* nfiles_in_batch,
+                           uint8_t* undecided_flags) {
+  MG_REQUIRE_READY();
+  if (!h || !batch || !first_file || !nfiles_in_batch) return fail(MG_ERR_ARG, "null argument");
+  *batch = nullptr;
+  *nfiles_in_batch = 0;
+  *first_file = h->paths.size();
+  mg_genomes_stream::Batch b;
+  {
+    const Clock::time_point t0 = Clock::now();
+    std::unique_lock<std::mutex> lk(h->m);
+    h->cv.wait(lk, [&] { return h->failed || !h->ready.empty() || h->end; });
+    h->wait_s += secs_since(t0);
+    if (h->failed) return fail(MG_ERR_ARG, "%s", h->error.c_str());
+    if (h->ready.empty()) return MG_OK;  // after the last file
+    b = std::move(h->ready.front());
+    h->ready.pop_front();
+  }
+  const Clock::time_point t0 = Clock::now();
+  hipStream_t st = ctx().stream;
+  int rc = hipStreamWaitEvent(st, g_res.ev_h2d[b.buf], 0) == hipSuccess ? MG_OK : fail(MG_ERR_HIP, "hipStreamWaitEvent failed");
+  const uint64_t nf = b.ext.size() - 1;
+  if (rc == MG_OK) rc = mg_genomes_parse_dev(b.text, b.ext.data(), nf, batch, undecided_flags);
+  if (hipEventRecord(g_res.ev_parsed[b.buf], st) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "hipEventRecord failed");
+  {
+    std::lock_guard<std::mutex> lk(h->m);
+    ++h->parsed;
+    h->parse_s += secs_since(t0);
+    h->cv.notify_all();
+  }
+  if (rc != MG_OK) { mg_genomes_free(*batch); *batch = nullptr; return rc; }
+  *first_file = b.first;
+  *nfiles_in_batch = nf;
+  return MG_OK;
+}
+
+int mg_genomes_stream_stats(const mg_genomes_stream* h, double out[5]) {
+  if (!h || !out) return fail(MG_ERR_ARG, "null argument");
+  mg_genomes_stream* w = const_cast<mg_genomes_stream*>(h);
+  std::lock_guard<std::mutex> lk(w->m);
+  out[0] = h->read_s; out[1] = h->upload_s; out[2] = h->wait_s; out[3] = h->parse_s; out[4] = (double)h->text_bytes;
+  return MG_OK;
 }
 
 }  // extern "C"
