@@ -761,6 +761,18 @@ int mg_profile_commit_reset_dev(mg_profile* p, int incoming_dropped, int first_s
                                 uint64_t group_base, uint64_t* d_count,
                                 uint64_t* d_bases, uint64_t* d_first_seen,
                                 uint64_t* d_scalars);
+/* mg_profile_commit_dev that also writes every read's verdict (--read_assignments; metalign_amd/assignments.py is the definition):
+ * d_assign is u64[2 * mg_profile_ngroups(p)], two words for read group_base + i of the shard at [2 i]:
+ *   w0 = kind in the low 2 bits — 0 ambiguous, 1 unique, 2 multimapped, 3 not counted (the shard's last read when no line closes it:
+ *        with has_lookahead = 0, scripts/map_and_profile.py:259-264) — and, for kind 1, the dense taxon id above them;
+ *   w1 = hitlen (kind 1), the read's row in the multimapped CSR of this shard (kind 2: mg_profile_multimapped), else 0.
+ * The array is prefilled with kind 3 by the launch that prepares the pass.  The sums and the CSR are those of mg_profile_commit_dev,
+ * by the same code (a compile-time variant of the commit pass).  The read count comes from the map-only pass, which runs first if it
+ * has not. */
+int mg_profile_commit_assign_dev(mg_profile* p, int incoming_dropped, int first_shard,
+                                 uint64_t group_base, uint64_t* d_count,
+                                 uint64_t* d_bases, uint64_t* d_first_seen,
+                                 uint64_t* d_scalars, uint64_t* d_assign);
 /* Sizes of the multimapped CSR after commit. */
 int mg_profile_multimapped_size(const mg_profile* p, uint64_t* nreads,
                                 uint64_t* nentries);
@@ -864,6 +876,26 @@ int mg_sam_stream_file_collated(const char* path, int paf, const mg_acc_index* i
                                 uint64_t chunk_bytes, int nthreads, mg_sam_batch** out, int* err_kind, uint64_t* err_line);
 int mg_bam_stream_file_collated(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,
                                 int* err_kind, uint64_t* err_rec);
+/* NAMING THE READS (--read_assignments; metalign_amd/csrc/mg_ingest.hip).  The NAMED tokenisers are mg_sam_tokenize_dev /
+ * mg_paf_tokenize_dev (paf = 0 / 1), mg_sam_tokenize (host text), mg_bam_tokenize_dev and the two file streams with a batch that
+ * also carries the QNAME of every record whose new-read bit is set, in record order: one name per read of stage C, the same
+ * bytes from SAM text, PAF and BAM.  Same arguments and error contract as the calls they mirror.  A read that goes on from the piece
+ * before (prev_qname) opens no read in this piece and has no name in it.  The names cost their bytes + 8 per read beside the batch. */
+int mg_sam_tokenize_named_dev(const uint8_t* d_text, uint64_t nbytes, int paf, const mg_acc_index* ix, const char* prev_qname,
+                              mg_sam_batch** out, int* err_kind, uint64_t* err_line);
+int mg_sam_tokenize_named(const uint8_t* text, uint64_t nbytes, int paf, const mg_acc_index* ix, const char* prev_qname,
+                          mg_sam_batch** out, int* err_kind, uint64_t* err_line);
+int mg_bam_tokenize_named_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* refmap, uint32_t nref, const mg_acc_index* ix,
+                              const char* prev_qname, int final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec);
+int mg_sam_stream_file_named(const char* path, int paf, const mg_acc_index* ix, uint64_t offset, uint64_t length,
+                             uint64_t chunk_bytes, int nthreads, mg_sam_batch** out, int* err_kind, uint64_t* err_line);
+int mg_bam_stream_file_named(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,
+                             int* err_kind, uint64_t* err_rec);
+/* The names of a named batch: their number and bytes; off (u64[nreads + 1]) and the bytes themselves (read r's name is
+ * bytes[off[r] .. off[r + 1])).  MG_ERR_STATE for a batch without names.  A named batch is not collated (mg_sam_batch_collate_dev:
+ * MG_ERR_STATE): its names are in the order the reads came in. */
+int mg_sam_batch_names_size(const mg_sam_batch* b, uint64_t* nreads, uint64_t* nbytes);
+int mg_sam_batch_names_download(const mg_sam_batch* b, uint64_t* off, uint8_t* bytes);
 uint64_t mg_sam_batch_count(const mg_sam_batch* b);
 const char* mg_sam_batch_last_qname(const mg_sam_batch* b);
 int mg_sam_batch_device_ptr(const mg_sam_batch* b, const mg_aln_rec** d_recs);

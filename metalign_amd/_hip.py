@@ -44,6 +44,8 @@ EXPORTS = [
     "mg_sam_batch_last_qname", "mg_sam_batch_device_ptr", "mg_sam_batch_download", "mg_sam_batch_free",
     "mg_sam_tokenize_keyed_dev", "mg_bam_tokenize_keyed_dev", "mg_sam_batch_keys_download", "mg_collate_order_dev", "mg_sam_batch_collate_dev",
     "mg_sam_stream_file_collated", "mg_bam_stream_file_collated",
+    "mg_sam_tokenize_named_dev", "mg_sam_tokenize_named", "mg_bam_tokenize_named_dev", "mg_sam_stream_file_named", "mg_bam_stream_file_named",
+    "mg_sam_batch_names_size", "mg_sam_batch_names_download", "mg_profile_commit_assign_dev",
     "mg_gunzip_open", "mg_gunzip_read", "mg_gunzip_close", "mg_zcat_files", "mg_stream_thin_file",
     "mg_inflate_dev", "mg_inflated_bytes", "mg_inflated_download", "mg_inflated_free", "mg_inflate_config", "mg_inflate_stats",
     "mg_sketch_genomes", "mg_sketch_genomes_prefix", "mg_db_upload", "mg_db_upload_sorted", "mg_db_ngenomes", "mg_db_max_hash", "mg_db_free",
@@ -870,6 +872,12 @@ class ProfileShard:
             self.handle, ctypes.c_int(int(incoming_dropped)), ctypes.c_int(int(first_shard)),
             ctypes.c_uint64(group_base), _vp(d_count), _vp(d_bases), _vp(d_first_seen), _vp(d_scalars)))
 
+    def commit_assign(self, incoming_dropped, first_shard, group_base, d_count, d_bases, d_first_seen, d_scalars, d_assign):
+        """commit that also writes two verdict words per read of the shard to d_assign (uint64[2 * ngroups]; mg_profile_commit_assign_dev)."""
+        self.hip._chk(self.hip.lib.mg_profile_commit_assign_dev(
+            self.handle, ctypes.c_int(int(incoming_dropped)), ctypes.c_int(int(first_shard)),
+            ctypes.c_uint64(group_base), _vp(d_count), _vp(d_bases), _vp(d_first_seen), _vp(d_scalars), _vp(d_assign)))
+
     def multimapped(self):
         nr, ne = ctypes.c_uint64(0), ctypes.c_uint64(0)
         self.hip._chk(self.hip.lib.mg_profile_multimapped_size(self.handle, ctypes.byref(nr), ctypes.byref(ne)))
@@ -943,6 +951,16 @@ class SamBatch:
         k = np.zeros((self.count, 2), dtype=np.uint64)
         self.hip._chk(self.hip.lib.mg_sam_batch_keys_download(self.handle, _vp(k.ctypes.data)))
         return k
+
+    def names(self):
+        """A named batch's read names: (bytes, uint64[reads + 1] offsets into them), one per record with the new-read bit
+        (mg_sam_batch_names_download)."""
+        nr, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.hip._chk(self.hip.lib.mg_sam_batch_names_size(self.handle, ctypes.byref(nr), ctypes.byref(nb)))
+        off = np.zeros(nr.value + 1, dtype=np.uint64)
+        blob = np.zeros(max(nb.value, 1), dtype=np.uint8)
+        self.hip._chk(self.hip.lib.mg_sam_batch_names_download(self.handle, _np(off, ctypes.c_uint64), _np(blob, ctypes.c_uint8)))
+        return blob[: nb.value].tobytes(), off
 
     def collate(self, want_perm=False):
         """A keyed batch regrouped by read in place, its keys freed (mg_sam_batch_collate_dev; metalign_amd/collate.py is the
@@ -1404,13 +1422,17 @@ class Hip:
         self.lib.mg_sam_batch_free(h)
         return n
 
-    def sam_tokenize_dev_batch(self, d_text, nbytes, acc_index, prev_qname="", paf=False):
+    def sam_tokenize_dev_batch(self, d_text, nbytes, acc_index, prev_qname="", paf=False, named=False):
         """SAM (or, paf=True, PAF) text resident in HBM -> SamBatch (records stay on the device).  SamParseError as
-        sam_tokenize."""
+        sam_tokenize.  named: the batch also carries the reads' names (mg_sam_tokenize_named_dev; SamBatch.names)."""
         h = _vp()
         kind, line = ctypes.c_int(0), ctypes.c_uint64(0)
-        fn = self.lib.mg_paf_tokenize_dev if paf else self.lib.mg_sam_tokenize_dev
-        rc = fn(_vp(d_text), ctypes.c_uint64(nbytes), acc_index.handle,
+        if named:
+            rc = self.lib.mg_sam_tokenize_named_dev(_vp(d_text), ctypes.c_uint64(nbytes), ctypes.c_int(1 if paf else 0), acc_index.handle,
+                                                    ctypes.c_char_p(prev_qname.encode()), ctypes.byref(h), ctypes.byref(kind), ctypes.byref(line))
+        else:
+            fn = self.lib.mg_paf_tokenize_dev if paf else self.lib.mg_sam_tokenize_dev
+            rc = fn(_vp(d_text), ctypes.c_uint64(nbytes), acc_index.handle,
                                           ctypes.c_char_p(prev_qname.encode()), ctypes.byref(h), ctypes.byref(kind),
                                           ctypes.byref(line))
         if rc != 0 and kind.value:
@@ -1446,13 +1468,16 @@ class Hip:
             d_r.free()
             d_p.free()
 
-    def sam_stream_file(self, path, acc_index, paf=False, offset=0, length=0, chunk_bytes=0, nthreads=0, collate=False):
+    def sam_stream_file(self, path, acc_index, paf=False, offset=0, length=0, chunk_bytes=0, nthreads=0, collate=False, named=False):
         """The alignment file (SAM; paf=True: PAF; plain, gzip or BGZF) -> SamBatch, streamed through page-locked chunks
         inside the library (mg_sam_stream_file): the file read, the upload and the tokeniser overlap, and the text never
         exists as a host array.  SamParseError for a line the reference cannot parse."""
         h = _vp()
         kind, line = ctypes.c_int(0), ctypes.c_uint64(0)
         fn = self.lib.mg_sam_stream_file_collated if collate else self.lib.mg_sam_stream_file  # (collate: regrouped by read)
+        if named:  # (the batch also carries the reads' names; never together with collate)
+            assert not collate
+            fn = self.lib.mg_sam_stream_file_named
         rc = fn(os.fsencode(path), ctypes.c_int(1 if paf else 0), acc_index.handle,
                                          ctypes.c_uint64(int(offset)), ctypes.c_uint64(int(length)), ctypes.c_uint64(int(chunk_bytes)),
                                          ctypes.c_int(int(nthreads)), ctypes.byref(h), ctypes.byref(kind), ctypes.byref(line))
@@ -1461,13 +1486,16 @@ class Hip:
         self._chk(rc)
         return SamBatch(self, h)
 
-    def bam_stream_file(self, path, acc_index, chunk_bytes=0, nthreads=0, collate=False):
+    def bam_stream_file(self, path, acc_index, chunk_bytes=0, nthreads=0, collate=False, named=False):
         """A BAM file -> SamBatch: the records its SAM rendering gives through sam_stream_file (mg_bam_stream_file).  SamParseError
         for a record whose rendering the reference cannot parse, that the device does not decide (kind 6) or that is not a BAM
         record the package takes (kind 7); `line` is the record's number within its piece."""
         h = _vp()
         kind, rec = ctypes.c_int(0), ctypes.c_uint64(0)
         fn = self.lib.mg_bam_stream_file_collated if collate else self.lib.mg_bam_stream_file  # (collate: regrouped by read)
+        if named:  # (the batch also carries the reads' names; never together with collate)
+            assert not collate
+            fn = self.lib.mg_bam_stream_file_named
         rc = fn(os.fsencode(path), acc_index.handle, ctypes.c_uint64(int(chunk_bytes)), ctypes.c_int(int(nthreads)),
                                          ctypes.byref(h), ctypes.byref(kind), ctypes.byref(rec))
         if rc != 0 and kind.value:
@@ -1475,13 +1503,16 @@ class Hip:
         self._chk(rc)
         return SamBatch(self, h)
 
-    def bam_tokenize_dev(self, d_bytes, nbytes, refmap, acc_index, prev_qname="", final=True, keyed=False):
+    def bam_tokenize_dev(self, d_bytes, nbytes, refmap, acc_index, prev_qname="", final=True, keyed=False, named=False):
         """BAM record bytes resident in HBM (behind the header) -> (SamBatch, consumed) (mg_bam_tokenize_dev); refmap: the accession row
         of every header reference (-1: none, -2: not one SAM field).  SamParseError as bam_stream_file."""
         rm = np.ascontiguousarray(refmap, dtype=np.int32)
         h = _vp()
         kind, rec, used = ctypes.c_int(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
         fn = self.lib.mg_bam_tokenize_keyed_dev if keyed else self.lib.mg_bam_tokenize_dev  # (keyed: the batch carries QNAME keys)
+        if named:
+            assert not keyed
+            fn = self.lib.mg_bam_tokenize_named_dev
         rc = fn(_vp(d_bytes), ctypes.c_uint64(nbytes), _np(rm if rm.size else np.zeros(1, np.int32), ctypes.c_int32),
                                           ctypes.c_uint32(rm.size), acc_index.handle, ctypes.c_char_p(prev_qname.encode()),
                                           ctypes.c_int(1 if final else 0), ctypes.byref(used), ctypes.byref(h), ctypes.byref(kind),
@@ -1501,15 +1532,21 @@ class Hip:
                                               ctypes.c_uint32(len(names)), ctypes.byref(h)))
         return AccIndex(self, h)
 
-    def sam_tokenize(self, text, acc_index, prev_qname="", paf=False):
+    def sam_tokenize(self, text, acc_index, prev_qname="", paf=False, named=False):
         """One chunk of SAM (paf=True: PAF) text (ending on a line boundary) -> (records REC_DTYPE[], QNAME of its last
-        retained line).  Raises SamParseError for a line the reference cannot parse."""
+        retained line).  Raises SamParseError for a line the reference cannot parse.  named: -> (records, last QNAME, (name bytes,
+        offsets)) — the names of the reads that open in this chunk (mg_sam_tokenize_named)."""
         buf = np.frombuffer(text, dtype=np.uint8)  # bytes or a memoryview slice: no copy
         h = _vp()
         kind, line = ctypes.c_int(0), ctypes.c_uint64(0)
         src = buf if buf.size else np.zeros(1, np.uint8)
-        fn = self.lib.mg_paf_tokenize if paf else self.lib.mg_sam_tokenize
-        rc = fn(_np(src, ctypes.c_uint8), ctypes.c_uint64(buf.size), acc_index.handle,
+        if named:
+            rc = self.lib.mg_sam_tokenize_named(_np(src, ctypes.c_uint8), ctypes.c_uint64(buf.size), ctypes.c_int(1 if paf else 0),
+                                                acc_index.handle, ctypes.c_char_p(prev_qname.encode()), ctypes.byref(h),
+                                                ctypes.byref(kind), ctypes.byref(line))
+        else:
+            fn = self.lib.mg_paf_tokenize if paf else self.lib.mg_sam_tokenize
+            rc = fn(_np(src, ctypes.c_uint8), ctypes.c_uint64(buf.size), acc_index.handle,
                                       ctypes.c_char_p(prev_qname.encode()), ctypes.byref(h), ctypes.byref(kind),
                                       ctypes.byref(line))
         if rc != 0 and kind.value:
@@ -1521,6 +1558,13 @@ class Hip:
             if n:
                 self._chk(self.lib.mg_sam_batch_download(h, _vp(recs.ctypes.data)))
             last = self.lib.mg_sam_batch_last_qname(h).decode("utf-8", "replace")
+            if named:
+                nr, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+                self._chk(self.lib.mg_sam_batch_names_size(h, ctypes.byref(nr), ctypes.byref(nb)))
+                off = np.zeros(nr.value + 1, dtype=np.uint64)
+                blob = np.zeros(max(nb.value, 1), dtype=np.uint8)
+                self._chk(self.lib.mg_sam_batch_names_download(h, _np(off, ctypes.c_uint64), _np(blob, ctypes.c_uint8)))
+                return recs, last, (blob[: nb.value].tobytes(), off)
             return recs, last
         finally:
             self.lib.mg_sam_batch_free(h)
@@ -1783,10 +1827,13 @@ class Hip:
         res['resident'] = ResidentProfile(shard, [d_recs, d_r2t, d_acc])
         return res
 
-    def profile_assign_dev_records(self, d_recs_ptr, n, ref2tax, ntax, pct_id, owners, resident=False):
+    def profile_assign_dev_records(self, d_recs_ptr, n, ref2tax, ntax, pct_id, owners, resident=False, assign=False):
         """Stage C over records ALREADY in HBM (the device tokeniser's batch).  owners: objects to free with the
         result (they hold the records).  resident=False: the multimapped CSR is downloaded (same dict as
-        profile_assign); True: it stays on the device (same dict as profile_assign_resident)."""
+        profile_assign); True: it stays on the device (same dict as profile_assign_resident).
+        assign=True (--read_assignments): also res['assign'] = uint64[2 * reads], every read's verdict words
+        (mg_profile_commit_assign_dev), res['names'] = (bytes, offsets) when the first owner is a named SamBatch, and the
+        multimapped CSR downloaded whatever `resident` says (the rows of the multimapped reads are read from it)."""
         ref2tax = np.ascontiguousarray(ref2tax, dtype=np.uint32)
         T = max(int(ntax), 1)
         d_r2t = self.array(ref2tax if ref2tax.size else np.zeros(1, np.uint32))
@@ -1797,14 +1844,35 @@ class Hip:
             d_recs_ptr = pad.ptr
         shard = self.profile_begin_dev(d_recs_ptr, n, False, d_r2t.ptr, len(ref2tax), ntax, pct_id)
         base = d_acc.ptr
-        shard.commit(True, True, 0, base, base + 8 * T, base + 16 * T, base + 24 * T, reset=True)
-        acc = d_acc.download()
+        words = None
+        if assign:
+            nreads = shard.ngroups if n else 0  # (the map-only pass; the array is sized by it)
+            d_words = self.empty(max(2 * nreads, 2), np.uint64)
+            try:
+                self._chk(self.lib.mg_profile_acc_reset(_vp(base), _vp(base + 8 * T), _vp(base + 16 * T), _vp(base + 24 * T),
+                                                        ctypes.c_uint32(ntax)))
+                shard.commit_assign(True, True, 0, base, base + 8 * T, base + 16 * T, base + 24 * T, d_words.ptr)
+                acc = d_acc.download()
+                words = d_words.download()[: 2 * nreads]
+            finally:
+                d_words.free()
+        else:
+            shard.commit(True, True, 0, base, base + 8 * T, base + 16 * T, base + 24 * T, reset=True)
+            acc = d_acc.download()
         res = dict(count=acc[:ntax].copy(), bases=acc[T:T + ntax].copy(), first_seen=acc[2 * T:2 * T + ntax].copy(),
                    tot_rds=int(acc[3 * T]), n_ambig=int(acc[3 * T + 1]))
+        if assign:
+            res['assign'] = words
+            if owners and isinstance(owners[0], SamBatch):
+                res['names'] = owners[0].names()
         keep = list(owners) + [d_r2t, d_acc] + ([pad] if pad is not None else [])
         if resident:
             nr, ne = shard.multimapped_size() if n else (0, 0)
             res.update(mm_nreads=nr, mm_nentries=ne, resident=ResidentProfile(shard, keep))
+            if assign:
+                off, tax, hl, rd = shard.multimapped() if n else (np.zeros(1, np.uint64), np.zeros(0, np.uint32),
+                                                                 np.zeros(0, np.uint64), np.zeros(0, np.uint64))
+                res.update(mm_offsets=off, mm_tax=tax, mm_hitlen=hl, mm_read=rd)
             return res
         try:
             off, tax, hl, rd = shard.multimapped() if n else (np.zeros(1, np.uint64), np.zeros(0, np.uint32),

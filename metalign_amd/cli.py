@@ -47,6 +47,9 @@ _OPTIONS = {
                     help='Regroup the alignments of a SAM / BAM file by read before profiling, on the GPU: "auto" when the @HD line '
                          'says SO:coordinate, "always", or "never" (default: a read\'s alignments are expected next to each other). '
                          'An aligner\'s own output is never regrouped.'),
+    'read_assignments': dict(default='NONE', help='Also write every read\'s verdict here, one TSV line per read in file order: '
+                             'read, class (U unique / M multimapped / A ambiguous / N not counted: the last read), taxids, hit bases '
+                             '(metalign_amd/assignments.py is the definition). One process only.'),
     'device_multimap': dict(action='store_true', help='Resolve multimapped reads on the GPU (their lists never leave '
                             'the device; abundances equal the default path to ~1e-15 relative, not byte for byte).'),
 }
@@ -62,7 +65,7 @@ _TOOLS = {
         options=['cutoff', 'db_dir', 'dbinfo_in', 'keep_temp_files', ('input_type', _READ_TYPES), 'length_normalize',
                  'low_mem', 'min_abundance', 'no_quantify_unmapped', 'output', 'pct_id', 'precise', 'rank_renormalize',
                  'read_cutoff', 'sampleID', 'sensitive', 'strain_level', 'temp_dir', 'threads', 'verbose',
-                 'sketch_table', 'min_count', 'sketch_size', 'kmer_match', 'device_multimap', 'collate']),
+                 'sketch_table', 'min_count', 'sketch_size', 'kmer_match', 'device_multimap', 'collate', 'read_assignments']),
     'select_db': dict(
         description='Run CMash and select a subset of the whole database to align to.',
         positionals=[('reads', dict(help='Reads file (FASTA / FASTQ, optionally .gz, or a BAM of reads).')),
@@ -77,7 +80,7 @@ _TOOLS = {
         options=[('db', 'NONE', 'Database FASTA from select_db (needed unless the inputs are SAM files).'), 'dbinfo',
                  ('input_type', ['fastq', 'fasta', 'sam', 'AUTO']), 'length_normalize', 'low_mem', 'min_abundance',
                  'rank_renormalize', 'output', 'pct_id', 'no_quantify_unmapped', 'read_cutoff', 'sampleID', 'threads',
-                 'verbose', 'device_multimap', 'collate']),
+                 'verbose', 'device_multimap', 'collate', 'read_assignments']),
 }
 
 

@@ -223,7 +223,7 @@ static int bam_chain_dev(const uint8_t* d_bytes, uint64_t nbytes, int32_t n_ref,
 }
 
 int bam_tokenize_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* d_refmap, int32_t n_ref, const char* prev_qname,
-                            bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec, bool keyed) {
+                            bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec, bool keyed, bool named) {
   MG_REQUIRE_READY();
   if (!out || !d_refmap) return fail(MG_ERR_ARG, "null argument");
   *out = nullptr;
@@ -239,6 +239,7 @@ int bam_tokenize_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32
   if (keyed) MG_TRY(sb->keys.alloc(16));  // (replaced by aln_emit_retained's when there are records)
   if (nbytes == 0) {
     MG_TRY(sb->recs.alloc(16));
+    if (named) MG_TRY(names_empty(sb.get()));
     *out = sb.release();
     return MG_OK;
   }
@@ -282,9 +283,10 @@ int bam_tokenize_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32
       return fail(MG_ERR_ARG, "BAM record %llu of the piece: %s (kind %u)", (unsigned long long)h_err,
                   kind == mgb::kCorrupt ? "corrupt, or a CIGAR kept in a CG tag (not supported)" : "not decided on the device", kind);
     }
-    MG_TRY(aln_emit_retained(d_bytes, d_lines, d_ret, d_rank, nrec, nret, d_prev, (uint32_t)plen, sb.get(), keyed));
+    MG_TRY(aln_emit_retained(d_bytes, d_lines, d_ret, d_rank, nrec, nret, d_prev, (uint32_t)plen, sb.get(), keyed, named));
   } else {
     MG_TRY(sb->recs.alloc(16));
+    if (named) MG_TRY(names_empty(sb.get()));
   }
   sb->nrecs = nret;
   *out = sb.release();
@@ -442,7 +444,7 @@ extern "C" {
 
 static int bam_tokenize_dev_impl(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* refmap, uint32_t nref, const mg_acc_index* ix,
                                 const char* prev_qname, int final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec,
-                                bool keyed) {
+                                bool keyed, bool named = false) {
   MG_REQUIRE_READY();
   if (!out || !ix || (nref && !refmap) || nref > 0x7fffffffu) return fail(MG_ERR_ARG, "null argument");
   std::vector<int32_t> m(nref + 1ull);
@@ -453,7 +455,7 @@ static int bam_tokenize_dev_impl(const uint8_t* d_bytes, uint64_t nbytes, const 
   MG_TRY(d_map.alloc(m.size() * sizeof(int32_t)));
   MG_TRY(mg_memcpy_h2d(d_map.p, m.data(), m.size() * sizeof(int32_t)));
   const int rc = bam_tokenize_prefix_dev(d_bytes, nbytes, d_map.as<int32_t>(), (int32_t)nref, prev_qname, final != 0, consumed, out,
-                                         err_kind, err_rec, keyed);
+                                         err_kind, err_rec, keyed, named);
   (void)hipStreamSynchronize(ctx().stream);  // (d_map is released here)
   return rc;
 }
@@ -466,6 +468,11 @@ int mg_bam_tokenize_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* 
 int mg_bam_tokenize_keyed_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* refmap, uint32_t nref, const mg_acc_index* ix,
                               const char* prev_qname, int final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec) {
   return bam_tokenize_dev_impl(d_bytes, nbytes, refmap, nref, ix, prev_qname, final, consumed, out, err_kind, err_rec, true);
+}
+
+int mg_bam_tokenize_named_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* refmap, uint32_t nref, const mg_acc_index* ix,
+                              const char* prev_qname, int final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec) {
+  return bam_tokenize_dev_impl(d_bytes, nbytes, refmap, nref, ix, prev_qname, final, consumed, out, err_kind, err_rec, false, true);
 }
 
 int mg_reads_parse_bam_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, int32_t n_ref, int final, uint64_t* consumed, mg_reads** out,

@@ -114,6 +114,7 @@ static int collate_order(const uint64_t* d_keys2, const mg_aln_rec* d_recs, uint
 
 int collate_batch(mg_sam_batch* b, uint64_t* d_perm_or_null) {
   if (!b->keyed) return fail(MG_ERR_STATE, "the batch carries no keys (tokenise it with a keyed call; a batch is collated once)");
+  if (b->named) return fail(MG_ERR_STATE, "a named batch is not collated (its names are in the order the reads came in)");
   hipStream_t st = ctx().stream;
   const uint64_t n = b->nrecs;
   if (n) {

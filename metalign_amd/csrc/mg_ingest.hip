@@ -532,6 +532,47 @@ __global__ void k_sam_emit(const uint8_t* __restrict__ text, const LineOut* __re
   }
 }
 
+// NAMED (--read_assignments): the QNAMEs of the records that open a read, in three steps over the emitted records.
+// 1. len[r] = the QNAME's length where record r carries the new-read bit, else 0; flag[r] = that bit
+__global__ void k_name_len(const mg_aln_rec* __restrict__ recs, const LineOut* __restrict__ lines, const uint64_t* __restrict__ ret_line,
+                           uint64_t nret, uint32_t* __restrict__ len, uint32_t* __restrict__ flag) {
+  uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (; r < nret; r += stride) {
+    const bool opens = (recs[r].ref_new & MG_REC_NEW_BIT) != 0;
+    flag[r] = opens ? 1u : 0u;
+    len[r] = opens ? lines[ret_line[r]].qlen : 0u;
+  }
+}
+// 2. the scans of both (exclusive_sum_u32_to_u64) give every opening record its read's rank and its name's place:
+//    name_off[rank] = that place, src[rank] = where the QNAME lies in the text; name_off[nreads] = nbytes
+__global__ void k_name_place(const uint32_t* __restrict__ flag, const LineOut* __restrict__ lines, const uint64_t* __restrict__ ret_line,
+                             uint64_t nret, const uint64_t* __restrict__ byte_off, const uint64_t* __restrict__ read_rank, uint64_t nreads,
+                             uint64_t nbytes, uint64_t* __restrict__ name_off, uint64_t* __restrict__ src) {
+  uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  if (r == 0) name_off[nreads] = nbytes;
+  for (; r < nret; r += stride) {
+    if (!flag[r]) continue;
+    const uint64_t k = read_rank[r];  // < nreads: the exclusive count of flags in front of a set one
+    name_off[k] = byte_off[r];
+    src[k] = lines[ret_line[r]].qbeg;
+  }
+}
+// 3. the bytes: kNameLanes lanes per name (a QNAME is 20 to 60 bytes in practice, at most 254 by the format: two to four rounds
+//    of 16 neighbouring bytes, where one lane per name would walk them alone and 64 would mostly idle)
+constexpr uint32_t kNameLanes = 16;
+__global__ __launch_bounds__(256) void k_name_gather(const uint8_t* __restrict__ text, const uint64_t* __restrict__ name_off,
+                                                     const uint64_t* __restrict__ src, uint64_t nreads, uint8_t* __restrict__ out) {
+  const uint32_t sub = threadIdx.x % kNameLanes;
+  uint64_t g = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kNameLanes;
+  const uint64_t ngroups = (uint64_t)gridDim.x * blockDim.x / kNameLanes;
+  for (; g < nreads; g += ngroups) {
+    const uint64_t o0 = name_off[g], n = name_off[g + 1] - o0, s = src[g];
+    for (uint64_t i = sub; i < n; i += kNameLanes) out[o0 + i] = text[s + i];
+  }
+}
+
 // Shared: build the line index of a text buffer.  If the text does not end in '\n' the last partial
 // line is terminated virtually.  -> d_line_end (scratch "ing_lines"), *nlines.
 // last_end (optional): the end of the last line, brought back in the same round trip as the marks' completion (a piece of a
@@ -832,7 +873,7 @@ __global__ void k_sam_last_qname(const uint8_t* __restrict__ text, const LineOut
 // the byte after the last newline (what follows is carried to the next piece by the caller, mg_stream.hip).
 int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg_acc_index* ix, const char* prev_qname,
                                 bool paf, bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_line,
-                                bool thin, bool keyed) {
+                                bool thin, bool keyed, bool named) {
   MG_REQUIRE_READY();
   if (!out || !ix) return fail(MG_ERR_ARG, "null argument");
   *out = nullptr;
@@ -852,6 +893,7 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
   if (nlines == 0) {
     MG_TRY(sb->recs.alloc(16));
     if (keyed) MG_TRY(sb->keys.alloc(16));
+    if (named) MG_TRY(names_empty(sb.get()));
     *out = sb.release();
     return MG_OK;
   }
@@ -890,7 +932,7 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
       if (err_line) *err_line = h_err;
       return fail(MG_ERR_ARG, "%s line %llu: parse error kind %u", paf ? "PAF" : "SAM", h_err, kind);
     }
-    MG_TRY(aln_emit_retained(d_text, d_lines, d_ret, d_rank, nlines, nret, d_prev, (uint32_t)plen, sb.get(), keyed));
+    MG_TRY(aln_emit_retained(d_text, d_lines, d_ret, d_rank, nlines, nret, d_prev, (uint32_t)plen, sb.get(), keyed, named));
   }
   sb->nrecs = nret;
   *out = sb.release();
@@ -900,7 +942,7 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
 // The retained lines (d_ret[l] = 1, d_rank = its exclusive prefix, nret of them) -> sb->recs with the new-read bit, and
 // sb->last_qname.  The SAM / PAF tokeniser above and the BAM decoder (mg_bam.hip) end here.
 int mg::aln_emit_retained(const uint8_t* d_text, const LineOut* d_lines, const uint32_t* d_ret, const uint64_t* d_rank, uint64_t nlines,
-                          uint64_t nret, const uint8_t* d_prev, uint32_t plen, mg_sam_batch* sb, bool keyed) {
+                          uint64_t nret, const uint8_t* d_prev, uint32_t plen, mg_sam_batch* sb, bool keyed, bool named) {
   Context& c = ctx();
   hipStream_t st = c.stream;
   MG_TRY(sb->recs.alloc((nret + 1) * sizeof(mg_aln_rec)));
@@ -937,11 +979,84 @@ int mg::aln_emit_retained(const uint8_t* d_text, const LineOut* d_lines, const u
       MG_HIP(hipMemcpyAsync(&sb->last_qname[0], d_text + qbeg, qlen, hipMemcpyDeviceToHost, st));
       MG_HIP(hipStreamSynchronize(st));
     }
+    if (named) {
+      ProfScope ps("ingest_names");
+      const unsigned grid = grid_for(nret, 256, (unsigned)c.num_cus * 16);
+      uint32_t* d_len = (uint32_t*)scratch("nm_len", nret * sizeof(uint32_t));
+      uint32_t* d_flag = (uint32_t*)scratch("nm_flag", nret * sizeof(uint32_t));
+      uint64_t* d_boff = (uint64_t*)scratch("nm_boff", (nret + 1) * sizeof(uint64_t));
+      uint64_t* d_rrank = (uint64_t*)scratch("nm_rrank", (nret + 1) * sizeof(uint64_t));
+      if (!d_len || !d_flag || !d_boff || !d_rrank) return MG_ERR_NOMEM;
+      hipLaunchKernelGGL(k_name_len, dim3(grid), dim3(256), 0, st, sb->recs.as<mg_aln_rec>(), d_lines, d_list, nret, d_len, d_flag);
+      MG_HIP(hipGetLastError());
+      uint64_t nbytes = 0, nreads = 0;
+      MG_TRY(exclusive_sum_u32_to_u64(d_len, d_boff, nret, &nbytes));
+      MG_TRY(exclusive_sum_u32_to_u64(d_flag, d_rrank, nret, &nreads));
+      uint64_t* d_src = (uint64_t*)scratch("nm_src", (nreads + 1) * sizeof(uint64_t));
+      if (!d_src) return MG_ERR_NOMEM;
+      MG_TRY(sb->name_off.alloc((nreads + 2) * sizeof(uint64_t)));
+      MG_TRY(sb->name_bytes.alloc(nbytes + 16));
+      hipLaunchKernelGGL(k_name_place, dim3(grid), dim3(256), 0, st, d_flag, d_lines, d_list, nret, d_boff, d_rrank, nreads, nbytes,
+                         sb->name_off.as<uint64_t>(), d_src);
+      MG_HIP(hipGetLastError());
+      if (nreads) {
+        hipLaunchKernelGGL(k_name_gather, dim3(grid_for(nreads * kNameLanes, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_text,
+                           sb->name_off.as<uint64_t>(), d_src, nreads, sb->name_bytes.as<uint8_t>());
+        MG_HIP(hipGetLastError());
+      }
+      MG_HIP(hipStreamSynchronize(st));  // (the text and the scratch arrays are the caller's to reuse from here)
+      sb->nreads = nreads;
+      sb->nname_bytes = nbytes;
+      sb->named = true;
+    }
+  } else if (named) {
+    MG_TRY(names_empty(sb));
   }
   return MG_OK;
 }
 
+int mg::names_empty(mg_sam_batch* sb) {
+  MG_TRY(sb->name_off.alloc(2 * sizeof(uint64_t)));
+  MG_TRY(sb->name_bytes.alloc(16));
+  MG_HIP(hipMemsetAsync(sb->name_off.p, 0, 2 * sizeof(uint64_t), ctx().stream));
+  MG_HIP(hipStreamSynchronize(ctx().stream));
+  sb->nreads = sb->nname_bytes = 0;
+  sb->named = true;
+  return MG_OK;
+}
+
 extern "C" {
+
+int mg_sam_tokenize_named_dev(const uint8_t* d_text, uint64_t nbytes, int paf, const mg_acc_index* ix, const char* prev_qname,
+                              mg_sam_batch** out, int* err_kind, uint64_t* err_line) {
+  return mg::aln_tokenize_prefix_dev(d_text, nbytes, ix, prev_qname, paf != 0, true, nullptr, out, err_kind, err_line, false, false, true);
+}
+
+int mg_sam_tokenize_named(const uint8_t* text, uint64_t nbytes, int paf, const mg_acc_index* ix, const char* prev_qname,
+                          mg_sam_batch** out, int* err_kind, uint64_t* err_line) {
+  MG_REQUIRE_READY();
+  DevBuf d_text;
+  MG_TRY(d_text.alloc(nbytes + 16));
+  MG_TRY(mg_memcpy_h2d(d_text.p, text, nbytes));
+  return mg_sam_tokenize_named_dev(d_text.as<uint8_t>(), nbytes, paf, ix, prev_qname, out, err_kind, err_line);
+}
+
+int mg_sam_batch_names_size(const mg_sam_batch* b, uint64_t* nreads, uint64_t* nbytes) {
+  if (!b || !nreads || !nbytes) return fail(MG_ERR_ARG, "null argument");
+  if (!b->named) return fail(MG_ERR_STATE, "the batch carries no names (tokenise it with a named call)");
+  *nreads = b->nreads;
+  *nbytes = b->nname_bytes;
+  return MG_OK;
+}
+
+int mg_sam_batch_names_download(const mg_sam_batch* b, uint64_t* off, uint8_t* bytes) {
+  MG_REQUIRE_READY();
+  if (!b || !off || (b->named && b->nname_bytes && !bytes)) return fail(MG_ERR_ARG, "null argument");
+  if (!b->named) return fail(MG_ERR_STATE, "the batch carries no names (tokenise it with a named call)");
+  MG_TRY(mg_memcpy_d2h(off, b->name_off.p, (b->nreads + 1) * sizeof(uint64_t)));
+  if (b->nname_bytes) MG_TRY(mg_memcpy_d2h(bytes, b->name_bytes.p, b->nname_bytes));
+  return MG_OK;
+}
 
 int mg_sam_tokenize_dev(const uint8_t* d_text, uint64_t nbytes, const mg_acc_index* ix, const char* prev_qname,
                         mg_sam_batch** out, int* err_kind, uint64_t* err_line) {

@@ -326,6 +326,11 @@ struct mg_sam_batch {
   // the keyed tokenisers (mg_collate.hip): u64[2 nrecs], record r's QNAME key (mg_collate_core.h: lo, hi) — until the batch is collated
   mg::DevBuf keys;
   bool keyed = false;
+  // the named tokenisers (mg_ingest.hip): the QNAME of every record that carries the new-read bit, in record order — name_off
+  // u64[nreads + 1] into name_bytes.  A read that goes on from the piece before has no name here: its first piece has it.
+  mg::DevBuf name_off, name_bytes;
+  uint64_t nreads = 0, nname_bytes = 0;
+  bool named = false;
 };
 
 namespace mg {
@@ -338,7 +343,9 @@ struct LineOut {
   uint32_t retained;
 };
 int aln_emit_retained(const uint8_t* d_text, const LineOut* d_lines, const uint32_t* d_ret, const uint64_t* d_rank, uint64_t nlines,
-                      uint64_t nret, const uint8_t* d_prev, uint32_t plen, mg_sam_batch* sb, bool keyed = false);
+                      uint64_t nret, const uint8_t* d_prev, uint32_t plen, mg_sam_batch* sb, bool keyed = false, bool named = false);
+// a named batch without records: no names
+int names_empty(mg_sam_batch* sb);
 // BAM (mg_bam.hip): the header as zlib reads it from the file; a piece of the records behind it -> the batch, as
 // aln_tokenize_prefix_dev for text (d_refmap: int32[1 + n_ref], bam_refmap's); *consumed = the end of its last complete record.
 struct BamHeader {
@@ -349,7 +356,8 @@ struct BamHeader {
 int bam_read_header(const char* path, BamHeader* h);
 std::vector<int32_t> bam_refmap(const std::vector<std::string>& names, const mg_acc_index* ix);
 int bam_tokenize_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* d_refmap, int32_t n_ref, const char* prev_qname,
-                            bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec, bool keyed = false);
+                            bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec, bool keyed = false,
+                            bool named = false);
 // The reads of a piece of BAM records (`samtools fastq -F 0x900`, mg_bam_core.h) -> *out, as mg_reads_parse_prefix_dev for text;
 // a break in the chain: MG_ERR_ARG, *err_at = its byte in the piece.
 int bam_reads_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, int32_t n_ref, bool final, uint64_t* consumed, mg_reads** out,
@@ -357,7 +365,7 @@ int bam_reads_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, int32_t n_ref,
 // thin: the piece comes from the file reader's thinning (mg_stream.hip: a SEQ field is MG_THIN_MARK + its length in decimal).
 int aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg_acc_index* ix, const char* prev_qname, bool paf,
                             bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_line, bool thin = false,
-                            bool keyed = false);
+                            bool keyed = false, bool named = false);
 // mg_collate.hip: a keyed batch -> its records regrouped by read (metalign_amd/collate.py is the definition), the keys freed.
 int collate_batch(mg_sam_batch* b, uint64_t* d_perm_or_null);
 }

@@ -545,8 +545,12 @@ extern "C" int mg_debug_k3_phases(unsigned long long* out, int reset) {
 #define PH(i)
 #define PH_FLUSH(c)
 #endif
-template <bool COMMIT>
-__device__ __forceinline__ void profile_pass_body(const PassArgs& A) {
+// ASSIGN (a commit pass only; --read_assignments): every committed read's verdict also goes to assign[2 (read - group_base)] —
+// w0 = kind (0 ambiguous, 1 unique, 2 multimapped) | dense taxon << 2 (unique), w1 = hitlen (unique) or the read's row in the
+// multimapped CSR.  A compile-time variant: the two instantiations without it are the code they were.
+template <bool COMMIT, bool ASSIGN = false>
+__device__ __forceinline__ void profile_pass_body(const PassArgs& A, uint64_t* __restrict__ assign = nullptr) {
+  static_assert(COMMIT || !ASSIGN, "verdicts exist in the commit pass only");
   PH_DECL;
   extern __shared__ __attribute__((aligned(16))) unsigned long long hist[];
   __shared__ uint2 s_desc[kSlots];
@@ -805,6 +809,11 @@ __device__ __forceinline__ void profile_pass_body(const PassArgs& A) {
             out = A.mm_tax + eo;
           }
         }
+        if constexpr (ASSIGN) {  // (fast and slow path alike end here; `so` is still this read's row)
+          uint64_t* const aw = assign + 2 * (my_gidx - A.group_base);
+          aw[0] = kind == 1u ? 1ull | ((uint64_t)tax << 2) : (uint64_t)kind;
+          aw[1] = kind == 1u ? hitlen : kind == 2u ? so : 0ull;
+        }
         if (kind == 0) {
           ++ambig;
         } else if (kind == 1) {
@@ -958,6 +967,10 @@ template <>
 __global__ __launch_bounds__(kPB) __attribute__((amdgpu_waves_per_eu(MG_K3_COMMIT_WAVES))) void k_profile_pass<true>(const PassArgs A) {
   profile_pass_body<true>(A);
 }
+// ... and the commit pass that also writes every read's verdict (mg_profile_commit_assign_dev): the same body, the same limits
+__global__ __launch_bounds__(kPB) __attribute__((amdgpu_waves_per_eu(MG_K3_COMMIT_WAVES))) void k_profile_pass_assign(const PassArgs A, uint64_t* __restrict__ assign) {
+  profile_pass_body<true, true>(A, assign);
+}
 
 // k_bins_reduce's view of the dumped tables: a block takes kRedSlots consecutive slots x kRedSlices shares of a quarter of the tables
 constexpr uint32_t kRedSlots = 32, kRedSlices = 8, kRedCache = 4, kRedY = 4;
@@ -1101,12 +1114,17 @@ __global__ __launch_bounds__(256) void k_bins_reduce(unsigned long long* __restr
 
 // Before a pass: tile descriptors + ticket = 0 and, when asked, the accumulators of a fresh batch (one launch).
 // flags: the hashed bins' overflow flags of the pass before (read by its k_bins_reduce, which ran ahead of this on the stream).
+// assign (optional): u64[2 nassign], the verdict words of mg_profile_commit_assign_dev.
 __global__ void k_pass_prepare(uint64_t* __restrict__ desc, uint64_t ndesc, uint64_t* __restrict__ count,
                                uint64_t* __restrict__ bases, uint64_t* __restrict__ first, uint64_t* __restrict__ scalars,
-                               uint32_t ntax, uint32_t* __restrict__ flags, uint32_t nflags) {
+                               uint32_t ntax, uint32_t* __restrict__ flags, uint32_t nflags, uint64_t* __restrict__ assign,
+                               uint64_t nassign) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   const uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (uint64_t i = i0; i < ndesc; i += stride) desc[i] = 0;
+  // the verdict words of a pass that writes them: every read "not counted" (kind 3) until the pass says otherwise — the shard's last
+  // read without a closing line never is
+  for (uint64_t i = i0; i < 2 * nassign; i += stride) assign[i] = (i & 1) ? 0ull : 3ull;
   for (uint64_t i = i0; i < nflags; i += stride) flags[i] = 0;
   if (count) {
     for (uint64_t t = i0; t < ntax; t += stride) { count[t] = 0; bases[t] = 0; first[t] = ~0ull; }
@@ -1201,7 +1219,8 @@ namespace {
 
 // One chained-scan pass over the shard.  commit == false: composed state map + read count only.
 int launch_pass(mg_profile* p, bool commit, uint32_t incoming, uint32_t first_shard, uint64_t group_base,
-                uint64_t* d_count, uint64_t* d_bases, uint64_t* d_first_seen, uint64_t* d_scalars, bool reset_acc = false) {
+                uint64_t* d_count, uint64_t* d_bases, uint64_t* d_first_seen, uint64_t* d_scalars, bool reset_acc = false,
+                uint64_t* d_assign = nullptr, uint64_t nassign = 0) {
   Context& c = ctx();
   hipStream_t st = stage_c_stream();
   const uint64_t desc_bytes = (p->ntiles * kDescWords + (uint64_t)kTicketLanes * kTicketStride) * sizeof(uint64_t);
@@ -1210,10 +1229,11 @@ int launch_pass(mg_profile* p, bool commit, uint32_t incoming, uint32_t first_sh
   if (!p->tot.p) MG_TRY(p->tot.alloc(4 * sizeof(uint64_t)));
   {
     const uint64_t ndesc = desc_bytes / sizeof(uint64_t);
-    const uint64_t work = ndesc > p->ntax ? ndesc : p->ntax;
+    uint64_t work = ndesc > p->ntax ? ndesc : p->ntax;
+    if (2 * nassign > work) work = 2 * nassign;
     hipLaunchKernelGGL(k_pass_prepare, dim3(grid_for(work, 256, (unsigned)c.num_cus * 4)), dim3(256), 0, st,
                        p->desc.as<uint64_t>(), ndesc, reset_acc ? d_count : (uint64_t*)nullptr, d_bases, d_first_seen, d_scalars,
-                       p->ntax, c.k3_flags, c.k3_flags ? c.k3_nflags : 0u);
+                       p->ntax, c.k3_flags, c.k3_flags ? c.k3_nflags : 0u, d_assign, d_assign ? nassign : 0ull);
     MG_HIP(hipGetLastError());
   }
   PassArgs a{};
@@ -1283,7 +1303,8 @@ int launch_pass(mg_profile* p, bool commit, uint32_t incoming, uint32_t first_sh
       c.k3_nflags = (uint32_t)nflags;
     }
   }
-  hipLaunchKernelGGL(k_profile_pass<true>, dim3(grid), dim3(kPB), lds, st, a);
+  if (d_assign) hipLaunchKernelGGL(k_profile_pass_assign, dim3(grid), dim3(kPB), lds, st, a, d_assign);
+  else hipLaunchKernelGGL(k_profile_pass<true>, dim3(grid), dim3(kPB), lds, st, a);
   MG_HIP(hipGetLastError());
   if (a.use_lds_hist == 2) {
     const unsigned rx = (p->ntax + 255) / 256 > kHashSlots / kRedSlots ? (p->ntax + 255) / 256 : kHashSlots / kRedSlots;
@@ -1404,10 +1425,12 @@ uint64_t mg_profile_ngroups(const mg_profile* p) {
 }
 
 static int commit_impl(mg_profile* p, int incoming_dropped, int first_shard, uint64_t group_base, uint64_t* d_count,
-                       uint64_t* d_bases, uint64_t* d_first_seen, uint64_t* d_scalars, bool reset_acc) {
+                       uint64_t* d_bases, uint64_t* d_first_seen, uint64_t* d_scalars, bool reset_acc, uint64_t* d_assign = nullptr) {
   MG_REQUIRE_READY();
   if (!p || !d_count || !d_bases || !d_first_seen || !d_scalars) return fail(MG_ERR_ARG, "null argument");
   if (p->committed) return fail(MG_ERR_STATE, "profile shard already committed");
+  // (the verdict array is sized by the shard's read count: known from the map-only pass, which runs now if it has not)
+  if (d_assign) MG_TRY(fetch_map(p));
   p->committed = true;
   if (p->nrecs == 0) {  // the phantom boundary never happens without a first line: nothing to add
     if (reset_acc) return mg_profile_acc_reset(d_count, d_bases, d_first_seen, d_scalars, p->ntax);
@@ -1420,7 +1443,13 @@ static int commit_impl(mg_profile* p, int incoming_dropped, int first_shard, uin
   MG_TRY(p->mm_hitlen.alloc((p->nrecs + 1) * sizeof(uint64_t)));
   MG_TRY(p->mm_read.alloc((p->nrecs + 1) * sizeof(uint64_t)));
   return launch_pass(p, true, incoming_dropped ? 1u : 0u, first_shard ? 1u : 0u, group_base, d_count, d_bases,
-                     d_first_seen, d_scalars, reset_acc);
+                     d_first_seen, d_scalars, reset_acc, d_assign, d_assign ? p->ngroups : 0ull);
+}
+
+int mg_profile_commit_assign_dev(mg_profile* p, int incoming_dropped, int first_shard, uint64_t group_base, uint64_t* d_count,
+                                 uint64_t* d_bases, uint64_t* d_first_seen, uint64_t* d_scalars, uint64_t* d_assign) {
+  if (!d_assign) return fail(MG_ERR_ARG, "null argument");
+  return commit_impl(p, incoming_dropped, first_shard, group_base, d_count, d_bases, d_first_seen, d_scalars, false, d_assign);
 }
 
 int mg_profile_commit_dev(mg_profile* p, int incoming_dropped, int first_shard, uint64_t group_base, uint64_t* d_count,

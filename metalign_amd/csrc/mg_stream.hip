@@ -1020,15 +1020,23 @@ int mg_reads_from_bam_file(const char* path, uint64_t chunk_bytes, int nthreads,
 }
 
 // The batches of a file's pieces -> one (a single piece's records are taken over as they are); keyed pieces: their keys likewise
+// named pieces: their names appended, their offsets moved up by the bytes in front of them (a read that goes on into the next
+// piece opens no read there, so it is named once)
 static int concat_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uint64_t total, const std::string& prev, bool keyed,
-                          mg_sam_batch** out) {
+                          mg_sam_batch** out, bool named = false) {
   std::unique_ptr<mg_sam_batch> all(new mg_sam_batch());
   all->last_qname = prev;
   all->nrecs = total;
   all->keyed = keyed;
+  if (named && parts.empty()) MG_TRY(names_empty(all.get()));
   if (parts.size() == 1) {
     all->recs = std::move(parts[0]->recs);
     all->keys = std::move(parts[0]->keys);
+    all->name_off = std::move(parts[0]->name_off);
+    all->name_bytes = std::move(parts[0]->name_bytes);
+    all->nreads = parts[0]->nreads;
+    all->nname_bytes = parts[0]->nname_bytes;
+    all->named = parts[0]->named;
   } else {
     MG_TRY(all->recs.alloc((total + 1) * sizeof(mg_aln_rec)));
     if (keyed) MG_TRY(all->keys.alloc((total + 1) * 2 * sizeof(uint64_t)));
@@ -1041,6 +1049,27 @@ static int concat_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uin
         MG_HIP(hipMemcpyAsync(all->keys.as<uint64_t>() + 2 * at, p->keys.p, p->nrecs * 2 * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
       at += p->nrecs;
     }
+    if (named && !parts.empty()) {
+      uint64_t nreads = 0, nbytes = 0;
+      for (auto& p : parts) { nreads += p->nreads; nbytes += p->nname_bytes; }
+      MG_TRY(all->name_off.alloc((nreads + 2) * sizeof(uint64_t)));
+      MG_TRY(all->name_bytes.alloc(nbytes + 16));
+      MG_HIP(hipMemsetAsync(all->name_off.p, 0, sizeof(uint64_t), st));
+      uint64_t r = 0, b = 0;
+      for (auto& p : parts) {
+        if (p->nname_bytes)
+          MG_HIP(hipMemcpyAsync(all->name_bytes.as<uint8_t>() + b, p->name_bytes.p, p->nname_bytes, hipMemcpyDeviceToDevice, st));
+        if (p->nreads)
+          hipLaunchKernelGGL(k_shift_offsets, dim3(grid_for(p->nreads, 256, 1024)), dim3(256), 0, st, p->name_off.as<uint64_t>() + 1,
+                             p->nreads, b, all->name_off.as<uint64_t>() + r + 1);
+        MG_HIP(hipGetLastError());
+        r += p->nreads;
+        b += p->nname_bytes;
+      }
+      all->nreads = nreads;
+      all->nname_bytes = nbytes;
+      all->named = true;
+    }
     MG_HIP(hipStreamSynchronize(st));
   }
   *out = all.release();
@@ -1050,9 +1079,9 @@ static int concat_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uin
 // ... and, for the collated entry points, regrouped by read (mg_collate.hip).  The knob collate_defer (a test hook) leaves the
 // batch as it was tokenised, keys and all, for the caller to look at and collate (mg_sam_batch_collate_dev).
 static int finish_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uint64_t total, const std::string& prev, bool collate,
-                          mg_sam_batch** out) {
+                          mg_sam_batch** out, bool named = false) {
   mg_sam_batch* all = nullptr;
-  MG_TRY(concat_batches(parts, total, prev, collate, &all));
+  MG_TRY(concat_batches(parts, total, prev, collate, &all, named));
   if (collate && !dbg("collate_defer")) {
     parts.clear();  // (the pieces' buffers go back to the pool before the sort asks for its own)
     const int rc = collate_batch(all, nullptr);
@@ -1068,7 +1097,8 @@ static int finish_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uin
 // scripts/map_and_profile.py:201-217.  A line the reference cannot parse: MG_ERR_ARG with err_kind (the caller streams
 // the file through the host tokeniser, which raises what the reference raises).
 static int sam_stream_file_impl(const char* path, int paf, const mg_acc_index* ix, uint64_t offset, uint64_t length,
-                                uint64_t chunk_bytes, int nthreads, mg_sam_batch** out, int* err_kind, uint64_t* err_line, bool collate) {
+                                uint64_t chunk_bytes, int nthreads, mg_sam_batch** out, int* err_kind, uint64_t* err_line, bool collate,
+                                bool named = false) {
   MG_REQUIRE_READY();
   if (!path || !ix || !out) return fail(MG_ERR_ARG, "null argument");
   *out = nullptr;
@@ -1083,13 +1113,18 @@ static int sam_stream_file_impl(const char* path, int paf, const mg_acc_index* i
   uint64_t total = 0;
   MG_TRY(stream_file(path, plan, [&](const uint8_t* d_text, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
     mg_sam_batch* b = nullptr;
-    MG_TRY(aln_tokenize_prefix_dev(d_text, nbytes, ix, prev.c_str(), paf != 0, final, consumed, &b, err_kind, err_line, thinned, collate));
+    MG_TRY(aln_tokenize_prefix_dev(d_text, nbytes, ix, prev.c_str(), paf != 0, final, consumed, &b, err_kind, err_line, thinned, collate, named));
     prev = b->last_qname;
     total += b->nrecs;
     parts.emplace_back(b);
     return MG_OK;
   }, &thinned));
-  return finish_batches(parts, total, prev, collate, out);
+  return finish_batches(parts, total, prev, collate, out, named);
+}
+
+int mg_sam_stream_file_named(const char* path, int paf, const mg_acc_index* ix, uint64_t offset, uint64_t length,
+                             uint64_t chunk_bytes, int nthreads, mg_sam_batch** out, int* err_kind, uint64_t* err_line) {
+  return sam_stream_file_impl(path, paf, ix, offset, length, chunk_bytes, nthreads, out, err_kind, err_line, false, true);
 }
 
 int mg_sam_stream_file(const char* path, int paf, const mg_acc_index* ix, uint64_t offset, uint64_t length,
@@ -1106,7 +1141,7 @@ int mg_sam_stream_file_collated(const char* path, int paf, const mg_acc_index* i
 // the header read here with zlib and stepped over in the first piece(s), every piece cut after its last complete record
 // (mg_bam.hip).
 static int bam_stream_file_impl(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,
-                                int* err_kind, uint64_t* err_rec, bool collate) {
+                                int* err_kind, uint64_t* err_rec, bool collate, bool named = false) {
   MG_REQUIRE_READY();
   if (!path || !ix || !out) return fail(MG_ERR_ARG, "null argument");
   *out = nullptr;
@@ -1126,13 +1161,18 @@ static int bam_stream_file_impl(const char* path, const mg_acc_index* ix, uint64
   MG_TRY(stream_file(path, plan, skip_bam_header(hdr.bytes, path, [&](const uint8_t* d_recs, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
     mg_sam_batch* b = nullptr;
     MG_TRY(bam_tokenize_prefix_dev(d_recs, nbytes, d_map.as<int32_t>(), (int32_t)hdr.names.size(), prev.c_str(), final, consumed, &b,
-                                   err_kind, err_rec, collate));
+                                   err_kind, err_rec, collate, named));
     prev = b->last_qname;
     total += b->nrecs;
     parts.emplace_back(b);
     return MG_OK;
   })));
-  return finish_batches(parts, total, prev, collate, out);
+  return finish_batches(parts, total, prev, collate, out, named);
+}
+
+int mg_bam_stream_file_named(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,
+                             int* err_kind, uint64_t* err_rec) {
+  return bam_stream_file_impl(path, ix, chunk_bytes, nthreads, out, err_kind, err_rec, false, true);
 }
 
 int mg_bam_stream_file(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,

@@ -29,7 +29,7 @@ import time
 
 import numpy as np
 
-from . import _hip, bam, cli, collate
+from . import _hip, assignments, bam, cli, collate
 
 start = time.time()
 RANKS = ['superkingdom', 'phylum', 'class', 'order', 'family', 'genus', 'species', 'strain']
@@ -96,6 +96,7 @@ class _Tokeniser:
         self.acc_index = acc_index
         self.prev = ''
         self.rows = []
+        self.names = []  # the QNAME of every record that opens a read (--read_assignments)
 
     def feed(self, line):
         if line.startswith('@'):
@@ -125,6 +126,8 @@ class _Tokeniser:
             raise OverflowError('alignment longer than the record format allows')
         new = f[0] != self.prev
         self.prev = f[0]
+        if new:
+            self.names.append(f[0])
         self.rows.append((ref | (_hip.NEW_BIT if new else 0), matched, total,
                           (flag & 0xFFF) | (seqlen << _hip.LEN_SHIFT)))
 
@@ -159,8 +162,9 @@ def tokenise_paf(lines, acc_index, decode=False):
     return _tokenise_paf_from(lines, acc_index, '', decode)[0]
 
 
-def _tokenise_paf_from(lines, acc_index, prev, decode=False):
-    """tokenise_paf with the previous retained QNAME handed in and out: (records, last retained QNAME)."""
+def _tokenise_paf_from(lines, acc_index, prev, decode=False, names=None):
+    """tokenise_paf with the previous retained QNAME handed in and out: (records, last retained QNAME).  names: a list that takes
+    the QNAME of every record that opens a read."""
     rows = []
     for line in lines:
         if isinstance(line, (bytes, bytearray)):  # a file opened in binary mode (map_main does), or the aligner's pipe
@@ -194,6 +198,8 @@ def _tokenise_paf_from(lines, acc_index, prev, decode=False):
         seqlen = 0 if secondary else qlen
         new = f[0] != prev
         prev = f[0]
+        if new and names is not None:
+            names.append(f[0])
         rows.append((acc_index[f[5]] | (_hip.NEW_BIT if new else 0), matched, total,
                      flag | (seqlen << _hip.LEN_SHIFT)))
     return (np.array(rows, dtype=_hip.REC_DTYPE) if rows else np.zeros(0, dtype=_hip.REC_DTYPE)), prev
@@ -249,9 +255,30 @@ def _line_chunks(instream, decode):
         yield b''.join(buf)
 
 
-def tokenise_sam_device(instream, acc_index, decode=False, paf=False):
+def _pack_names(names):
+    """A list of QNAMEs -> (bytes, uint64 offsets), the form the named tokenisers give."""
+    enc = [n.encode('utf-8') for n in names]
+    off = np.zeros(len(enc) + 1, dtype=np.uint64)
+    if enc:
+        off[1:] = np.cumsum([len(e) for e in enc])
+    return b''.join(enc), off
+
+
+def _join_names(parts):
+    """The (bytes, offsets) of consecutive chunks -> those of the whole stream."""
+    blobs, offs, at = [], [np.zeros(1, dtype=np.uint64)], 0
+    for blob, off in parts:
+        blobs.append(blob)
+        offs.append(off[1:] + np.uint64(at))
+        at += len(blob)
+    return b''.join(blobs), np.concatenate(offs)
+
+
+def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names=None):
     """SAM (paf=True: PAF) stream -> records on the MI355X (mg_sam_tokenize / mg_paf_tokenize).  A line the reference
-    cannot parse is re-run through the host tokeniser so that the very same exception (type and message) surfaces."""
+    cannot parse is re-run through the host tokeniser so that the very same exception (type and message) surfaces.
+    read_names (--read_assignments): a list that takes every chunk's read names, (bytes, offsets) from mg_sam_tokenize_named — a read that
+    goes on from the chunk before is named there."""
     hip = _hip.Hip.get()
     names = [None] * len(acc_index)
     for a, i in acc_index.items():
@@ -261,7 +288,11 @@ def tokenise_sam_device(instream, acc_index, decode=False, paf=False):
     try:
         for chunk in _line_chunks(instream, decode):
             try:
-                recs, prev = hip.sam_tokenize(chunk, index, prev, paf=paf)
+                if read_names is not None:
+                    recs, prev, nm = hip.sam_tokenize(chunk, index, prev, paf=paf, named=True)
+                    read_names.append(nm)
+                else:
+                    recs, prev = hip.sam_tokenize(chunk, index, prev, paf=paf)
             except _hip.SamParseError as e:
                 lines = bytes(chunk).split(b'\n')
                 bad = lines[e.line].decode('utf-8', 'replace')
@@ -274,14 +305,17 @@ def tokenise_sam_device(instream, acc_index, decode=False, paf=False):
                 # tokeniser is the definition — this chunk goes through it, carrying the previous QNAME in and out.
                 if lines and not lines[-1]:
                     lines.pop()  # (the chunk ends in a newline)
+                host_names = []
                 if paf:
-                    recs, prev = _tokenise_paf_from(lines, acc_index, prev)
+                    recs, prev = _tokenise_paf_from(lines, acc_index, prev, names=host_names)
                 else:
                     tk = _Tokeniser(acc_index)
                     tk.prev = prev
                     for ln in lines:
                         tk.feed(ln.decode('utf-8'))
-                    recs, prev = tk.records(), tk.prev
+                    recs, prev, host_names = tk.records(), tk.prev, tk.names
+                if read_names is not None:
+                    read_names.append(_pack_names(host_names))
             parts.append(recs)
     finally:
         index.free()
@@ -293,9 +327,9 @@ def tokenise_sam_device(instream, acc_index, decode=False, paf=False):
 _device_tokenise = tokenise_sam_device
 
 
-def tokenise_paf_device(instream, acc_index, decode=False):
+def tokenise_paf_device(instream, acc_index, decode=False, read_names=None):
     """PAF replay on the device (mg_paf_tokenize): the same records as tokenise_paf."""
-    return tokenise_sam_device(instream, acc_index, decode=decode, paf=True)
+    return tokenise_sam_device(instream, acc_index, decode=decode, paf=True, read_names=read_names)
 
 
 _device_tokenise_paf = tokenise_paf_device
@@ -363,6 +397,18 @@ def multimapped_lists(res, taxids):
     return out
 
 
+def assignment_rows(res, taxids):
+    """Stage C's verdict words (res['assign']), the reads' names (res['names']) and the multimapped CSR -> the rows
+    assignments.read_assignments gives for the same stream."""
+    blob, off = res['names']
+    return assignments.rows_from_words(res['assign'], blob, off, taxids, res['mm_offsets'], res['mm_tax'], res['mm_hitlen'])
+
+
+def _append_assignments(args, rows):
+    """One input file's rows behind those of the files before it (map_main wrote the header)."""
+    assignments.write_assignments(args.read_assignments, rows, append=True)
+
+
 def assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=True):
     """Kernel outputs -> the (taxids2abs, multimapped, low_mem_mmap) triple of the reference (:193-264).
     want_lists=False leaves `multimapped` as the CSR dict for the vectorised tail (compute_abundances)."""
@@ -392,14 +438,18 @@ def assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=True):
     return taxids2abs, multimapped, {}
 
 
-def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _resident=False, _paf=False, _bam=False, _collate=False):
+def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _resident=False, _paf=False, _bam=False, _collate=False,
+                         _assignments=False):
     """map_and_process for a plain SAM FILE, without the text or the records ever being host arrays: the file goes up
     through page-locked chunks (Hip.upload_file), is tokenised where it lands and stage C runs on the records the
     tokeniser left in HBM.  A line the reference cannot parse makes this return None: the caller then takes the
     streaming path, which reproduces the reference's exception for that line.  _bam: a BAM file (mg_bam_stream_file), None
     likewise for a record the device does not decide — the caller then streams the file's SAM rendering (bam.sam_lines).
     _collate: the file's records regrouped by read on the device before stage C (mg_*_stream_file_collated; the definition is
-    collate.collated_lines, which the caller falls back to on None)."""
+    collate.collated_lines, which the caller falls back to on None).
+    _assignments (--read_assignments): the tokeniser also keeps the reads' names, stage C also writes every read's verdict and the rows
+    are appended to args.read_assignments; never together with _collate (a named batch is not collated)."""
+    assert not (_assignments and _collate)
     acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
     _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
     hip = _hip.Hip.get()
@@ -420,19 +470,24 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
             # 16 B of the regrouped copy = 80 B; a record is at least ~50 B of BAM / compressed text, ~100 B of plain text
             compressed = _bam or _is_gzip(path)
             need += 80 * (os.path.getsize(path) // (50 if compressed else 100))
+        if _assignments:
+            # per read 16 B of verdict words, 8 B of name offset and the name itself (~40 B); a read is at least one record
+            need += 64 * (os.path.getsize(path) // (50 if _bam or _is_gzip(path) else 100))
         if need > free + pooled:
             return None
         try:
             if _bam:  # (a BAM is always streamed: ~16 B of records per ~60 B of the compressed file stay resident)
-                batch = hip.bam_stream_file(path, index, chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)), collate=_collate)
+                batch = hip.bam_stream_file(path, index, chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)), collate=_collate,
+                                            named=_assignments)
             elif _collate:  # (always streamed: the keys ride on the stream's batches)
                 batch = hip.sam_stream_file(path, index, paf=_paf, chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)), collate=True)
             elif not streamed:  # the whole text up, then one tokeniser call (round 2's path)
                 d_text, size = hip.upload_file(path)
-                batch = hip.sam_tokenize_dev_batch(d_text.ptr, size, index, '', paf=_paf)
+                batch = hip.sam_tokenize_dev_batch(d_text.ptr, size, index, '', paf=_paf, named=_assignments)
             else:
                 # reader threads -> page-locked chunks -> HBM -> tokeniser, chunk i + 1 in flight while chunk i is tokenised
-                batch = hip.sam_stream_file(path, index, paf=_paf, chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)))
+                batch = hip.sam_stream_file(path, index, paf=_paf, chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)),
+                                            named=_assignments)
         except _hip.SamParseError:
             return None
         except _hip.HipError as e:
@@ -445,12 +500,14 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
             if d_text is not None:
                 d_text.free()
         res = hip.profile_assign_dev_records(batch.ptr, batch.count, ref2tax, len(taxids), float(args.pct_id), [batch],
-                                             resident=_resident)
+                                             resident=_resident, assign=_assignments)
         batch = None  # owned by the result now
     finally:
         index.free()
         if batch is not None:
             batch.free()
+    if _assignments:
+        _append_assignments(args, assignment_rows(res, taxids))
     if not _want_lists:
         res = dict(res, taxids=taxids)
     return assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=_want_lists)
@@ -640,14 +697,30 @@ class _CudaWords:
         self.__cuda_array_interface__ = {'shape': (int(n),), 'typestr': '<i4', 'data': (int(ptr), False), 'version': 2}
 
 
-def map_and_process(args, instream, acc2info, taxid2info, _assign=None, _want_lists=True, _resident=False):
-    """Reference signature (:193).  `_assign` is a test seam; product code never passes it."""
+def map_and_process(args, instream, acc2info, taxid2info, _assign=None, _want_lists=True, _resident=False, _assignments=False):
+    """Reference signature (:193).  `_assign` is a test seam; product code never passes it.
+    _assignments (--read_assignments): every chunk's read names are collected beside its records, stage C runs over the records
+    uploaded as one array with the verdict words written, and the rows are appended to args.read_assignments."""
     acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
     _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
     # test seam: an injected record-level backend is fed by the host tokeniser; product code never passes one
     tokenise = _device_tokenise if _assign is None else tokenise_sam
     if getattr(args, 'paf_input', False):
         tokenise = _device_tokenise_paf if _assign is None else tokenise_paf
+    if _assignments:
+        if _assign is not None:
+            raise ValueError('--read_assignments needs the device path')
+        parts = []
+        recs = tokenise(instream, acc_index, decode=(args.input_type != 'sam'), read_names=parts)
+        hip = _hip.Hip.get()
+        d_recs = hip.array(recs if len(recs) else np.zeros(1, _hip.REC_DTYPE))
+        res = hip.profile_assign_dev_records(d_recs.ptr, len(recs), ref2tax, len(taxids), float(args.pct_id), [d_recs],
+                                             resident=_resident, assign=True)
+        res['names'] = _join_names(parts)
+        _append_assignments(args, assignment_rows(res, taxids))
+        if not _want_lists:
+            res = dict(res, taxids=taxids)
+        return assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=_want_lists)
     recs = tokenise(instream, acc_index, decode=(args.input_type != 'sam'))
     res = (_assign or (_device_assign_resident if _resident else _device_assign))(recs, ref2tax, len(taxids),
                                                                                   float(args.pct_id))
@@ -838,13 +911,14 @@ def compute_abundances(args, infile, acc2info, tax2info):
     seams_untouched = (_device_tokenise is tokenise_sam_device and _device_tokenise_paf is tokenise_paf_device
                        and _device_assign is _DEVICE_ASSIGN)  # (tests reroute them)
     paf = bool(getattr(args, 'paf_input', False))
+    want_rows = _wants_assignments(args)
     if args.input_type == 'sam' and not paf and bam.is_bam(infile):  # decided per file: a BAM is never SAM text
         instream.close()
         return _compute_abundances_bam(args, infile, acc2info, tax2info, on_device, seams_untouched)
     if args.input_type == 'sam' and not paf and _wants_collation(args, lambda: _sam_header_lines(infile)):
         instream.close()
         return _compute_abundances_collated(args, infile, acc2info, tax2info, on_device, seams_untouched)
-    if args.input_type == 'sam' and seams_untouched and not paf:
+    if args.input_type == 'sam' and seams_untouched and not paf and not want_rows:
         from .select_db import dist_context
         ctx = dist_context()
         if ctx is not None:  # one process per GPU: the ranks tokenise the text between them, rank 0 does the rest
@@ -855,9 +929,11 @@ def compute_abundances(args, infile, acc2info, tax2info):
             seams_untouched = seams_untouched and done is not None  # (None: rank 0 streams the file, alone)
     if args.input_type == 'sam' and seams_untouched and done is None:
         # a plain file (SAM, or a PAF replay): all the way on the device
-        done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _paf=paf)
+        done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _paf=paf,
+                                    _assignments=want_rows)
     if done is None:
-        done = map_and_process(args, instream, acc2info, tax2info, _want_lists=False, _resident=on_device)
+        done = map_and_process(args, instream, acc2info, tax2info, _want_lists=False, _resident=on_device,
+                               _assignments=want_rows and seams_untouched)
     taxids2abs, mm, low_mem_mmap = done
     if args.input_type == 'sam':
         instream.close()
@@ -865,6 +941,10 @@ def compute_abundances(args, infile, acc2info, tax2info):
         mapper.stdout.close()
         mapper.wait()
     return _abundances_tail(args, taxids2abs, mm, tax2info, on_device)
+
+
+def _wants_assignments(args):
+    return getattr(args, 'read_assignments', 'NONE') not in (None, 'NONE')  # (callers build Namespaces without it)
 
 
 def _is_gzip(path):
@@ -911,6 +991,8 @@ def _compute_abundances_collated(args, infile, acc2info, tax2info, on_device, se
     if done is None:
         done = map_and_process(args, collate.collated_lines(_sam_file_lines(infile)), acc2info, tax2info, _want_lists=False,
                                _resident=on_device)
+    if _wants_assignments(args):  # (a named batch is not collated: the rows of a collated input come from the definition)
+        _append_assignments(args, assignments.read_assignments(collate.collated_lines(_sam_file_lines(infile)), acc2info, args.pct_id))
     taxids2abs, mm, _ = done
     return _abundances_tail(args, taxids2abs, mm, tax2info, on_device)
 
@@ -924,13 +1006,16 @@ def _compute_abundances_bam(args, infile, acc2info, tax2info, on_device, seams_u
     collating = _wants_collation(args, lambda: _bam_header_lines(infile))
     bam.warn_about(infile, collating=collating)
     done = None
+    want_rows = _wants_assignments(args)
     if seams_untouched:
         done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _bam=True,
-                                    _collate=collating)
+                                    _collate=collating, _assignments=want_rows and not collating)
     if done is None:
         lines = bam.sam_lines(infile)
         done = map_and_process(args, collate.collated_lines(lines) if collating else lines, acc2info, tax2info, _want_lists=False,
-                               _resident=on_device)
+                               _resident=on_device, _assignments=want_rows and not collating and seams_untouched)
+    if want_rows and collating:  # (as a collated SAM file: the definition over the regrouped lines)
+        _append_assignments(args, assignments.read_assignments(collate.collated_lines(bam.sam_lines(infile)), acc2info, args.pct_id))
     taxids2abs, mm, _ = done
     return _abundances_tail(args, taxids2abs, mm, tax2info, on_device)
 
@@ -1007,6 +1092,9 @@ def map_main(args=None):
         sys.exit('Error: --pct_id must be between 0.0 and 1.0, inclusive.')
     if args.db == 'NONE' and not args.infiles[0].endswith(('sam', 'paf', 'bam')):
         sys.exit('Error: --db must be specified unless sam files are provided.')
+    if _wants_assignments(args) and int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        # (the records the ranks gather on rank 0 carry no names: refused before the process group or a GPU is touched)
+        sys.exit('Error: --read_assignments runs in one process on one GPU; start it without torch.distributed.run.')
     args.data = cli.with_slash(args.data)
     if args.dbinfo == 'AUTO':
         args.dbinfo = args.data + 'db_info.txt'
@@ -1024,6 +1112,8 @@ def map_main(args=None):
         return  # a multi-GPU launch shares only SAM files between the ranks; anything else is rank 0's alone
     if int(os.environ.get('RANK', '0')) == 0:
         open(args.output, 'w').close()
+        if _wants_assignments(args):
+            assignments.write_assignments(args.read_assignments, [])  # the header; every input file appends its rows
     acc2info, taxid2info = get_acc2info(args)
     rank_results = gather_results(args, acc2info, taxid2info)
     if not getattr(args, '_not_root', False):

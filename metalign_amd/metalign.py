@@ -52,6 +52,9 @@ def _bam_for_the_aligner(args):
 
 def main(argv=None):
     args = metalign_parseargs(argv)
+    import os
+    if args.read_assignments != 'NONE' and int(os.environ.get('WORLD_SIZE', '1')) > 1:  # (as map_main, before stages A and B run)
+        sys.exit('Error: --read_assignments runs in one process on one GPU; start it without torch.distributed.run.')
     args.data = cli.with_slash(args.data)
     own_temp = args.temp_dir == 'AUTO/'  # a directory of this process's own making (one per rank in a multi-GPU launch)
     if own_temp:
@@ -65,7 +68,6 @@ def main(argv=None):
     _apply_modes(args)
     _wire_stages(args)
     select.select_main(args)
-    import os
     if int(os.environ.get('WORLD_SIZE', '1')) > 1 and int(os.environ.get('RANK', '0')) != 0:
         # a multi-GPU launch (torch.distributed.run): the ranks share stages A + B; rank 0 aligns and profiles.
         # An explicit --temp_dir is ONE directory for all ranks: rank 0 is still reading the CSV from it, writing the
