@@ -63,6 +63,14 @@ typedef struct mg_aln_rec {
 #define MG_REC_LEN_SHIFT 12
 #define MG_REC_MAX_SEQLEN ((1u << 20) - 1u)
 
+/* Where a record lies on its reference (--coverage; metalign_amd/coverage.py): pos0 = POS - 1, span = the sum of the CIGAR's
+ * M, D, N and X lengths (at most 2^32 - 1).  span == 0: not placed (POS not 1 to 10 digits in [1, 2^31 - 1], or no such op);
+ * pos0 is then 0. */
+typedef struct mg_aln_place {
+  uint32_t pos0;
+  uint32_t span;
+} mg_aln_place;
+
 /* ------------------------------------------------------------------------ *
  * Lifecycle, errors, raw device memory
  * ------------------------------------------------------------------------ */
@@ -85,7 +93,8 @@ int mg_device_count(void);
  *   k_refpipe_count — few workgroups, so that each loops over many tiles); collate_defer (test hook: the collated stream calls
  *   return their batch keyed and not yet collated); genome_slab_bytes (mg_genomes_stream_open: the size of a page-locked slab,
  *   default 8 MiB, at least 4 KiB), genome_guard (test hook: mg_genomes_parse_dev fills the 16 bytes behind its bases and the
- *   word behind its offsets with 0xa5 before its kernels run).
+ *   word behind its offsets with 0xa5 before its kernels run); cov_grid (test hook, k3_grid's meaning for k_cov_add /
+ *   k_cov_count, mg_coverage.hip).
  * Needs no device and no mg_init.  MG_ERR_ARG for a key that does not exist. */
 int mg_debug_set(const char* key, int64_t value);
 int64_t mg_debug_get(const char* key);
@@ -896,11 +905,51 @@ int mg_bam_stream_file_named(const char* path, const mg_acc_index* ix, uint64_t 
  * MG_ERR_STATE): its names are in the order the reads came in. */
 int mg_sam_batch_names_size(const mg_sam_batch* b, uint64_t* nreads, uint64_t* nbytes);
 int mg_sam_batch_names_download(const mg_sam_batch* b, uint64_t* off, uint8_t* bytes);
+/* ONE FLAG-TAKING FAMILY (mg_sam_tokenize_dev_ex, ...): the arguments of its namesake plus `want`, a mask of what the batch
+ * carries beside its records.  KEYS / NAMES / COLLATE are what the keyed, named and collated calls above give (COLLATE on a
+ * tokeniser: the batch is keyed and then collated; the knob collate_defer holds for the streams only).  NAMES with COLLATE:
+ * MG_ERR_STATE, as mg_sam_batch_collate_dev says.  PLACES (--coverage): mg_aln_place[count] in record order, the same from SAM
+ * text and from BAM (pos < 0: not placed), 8 bytes per record; it combines with each of the others — a placed batch that is
+ * collated has its places permuted with its records.  PLACES with paf = 1: MG_ERR_ARG (a PAF line has no POS / CIGAR columns).  A file stream keeps keys only to collate
+ * by them: KEYS without COLLATE is MG_ERR_ARG there. */
+#define MG_BATCH_KEYS 1u
+#define MG_BATCH_NAMES 2u
+#define MG_BATCH_PLACES 4u
+#define MG_BATCH_COLLATE 8u
+int mg_sam_tokenize_dev_ex(const uint8_t* d_text, uint64_t nbytes, int paf, const mg_acc_index* ix, const char* prev_qname,
+                           mg_sam_batch** out, int* err_kind, uint64_t* err_line, unsigned want);
+int mg_sam_tokenize_ex(const uint8_t* text, uint64_t nbytes, int paf, const mg_acc_index* ix, const char* prev_qname,
+                       mg_sam_batch** out, int* err_kind, uint64_t* err_line, unsigned want);
+int mg_bam_tokenize_dev_ex(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* refmap, uint32_t nref, const mg_acc_index* ix,
+                           const char* prev_qname, int final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec,
+                           unsigned want);
+int mg_sam_stream_file_ex(const char* path, int paf, const mg_acc_index* ix, uint64_t offset, uint64_t length,
+                          uint64_t chunk_bytes, int nthreads, mg_sam_batch** out, int* err_kind, uint64_t* err_line, unsigned want);
+int mg_bam_stream_file_ex(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,
+                          int* err_kind, uint64_t* err_rec, unsigned want);
+/* The places of a placed batch.  MG_ERR_STATE for a batch without places. */
+int mg_sam_batch_places_download(const mg_sam_batch* b, mg_aln_place* places);
+int mg_sam_batch_places_device_ptr(const mg_sam_batch* b, const mg_aln_place** d_places);
 uint64_t mg_sam_batch_count(const mg_sam_batch* b);
 const char* mg_sam_batch_last_qname(const mg_sam_batch* b);
 int mg_sam_batch_device_ptr(const mg_sam_batch* b, const mg_aln_rec** d_recs);
 int mg_sam_batch_download(const mg_sam_batch* b, mg_aln_rec* recs);
 void mg_sam_batch_free(mg_sam_batch* b);
+
+/* BREADTH AND DEPTH OF COVERAGE (--coverage; metalign_amd/csrc/mg_coverage.hip; the definition is metalign_amd/coverage.py).
+ * create: one bit per reference base, zeroed; accession a (length lengths[a]) starts on a 32-bit word boundary at a word offset
+ *   held in 64 bits.  nacc = 0 and lengths of 0 are legal.  MG_ERR_NOMEM when the bitmap does not fit.
+ * add_dev: records and their places (device pointers, n of each; any number of calls).  A record counts when FLAG has no 2048 and
+ *   (double)matched / (double)total >= pct_id (stage C's own expression); a counting record with span 0, pos0 >= its accession's
+ *   length or an accession row >= nacc is unplaced; every other one sets bits [pos0, min(pos0 + span, length)) of its accession
+ *   and adds 1 and that length to the accession's alignments and aligned_bases.  Asynchronous on the library stream.
+ * result: counts the set bits per accession and downloads alignments, aligned_bases, covered_bases (u64[nacc] each) and
+ *   *unplaced.  Synchronises.  May be called again after further add_dev calls. */
+typedef struct mg_coverage mg_coverage;
+int mg_coverage_create(const uint64_t* lengths, uint32_t nacc, mg_coverage** out);
+int mg_coverage_add_dev(mg_coverage* c, const mg_aln_rec* d_recs, const mg_aln_place* d_place, uint64_t n, double pct_id);
+int mg_coverage_result(mg_coverage* c, uint64_t* alignments, uint64_t* aligned_bases, uint64_t* covered_bases, uint64_t* unplaced);
+void mg_coverage_free(mg_coverage* c);
 
 /* Host-buffer convenience, single shard = whole stream. Capacities: mm_* as
  * above with mm_cap_reads / mm_cap_entries entries available. */

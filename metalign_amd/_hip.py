@@ -46,6 +46,9 @@ EXPORTS = [
     "mg_sam_stream_file_collated", "mg_bam_stream_file_collated",
     "mg_sam_tokenize_named_dev", "mg_sam_tokenize_named", "mg_bam_tokenize_named_dev", "mg_sam_stream_file_named", "mg_bam_stream_file_named",
     "mg_sam_batch_names_size", "mg_sam_batch_names_download", "mg_profile_commit_assign_dev",
+    "mg_sam_tokenize_dev_ex", "mg_sam_tokenize_ex", "mg_bam_tokenize_dev_ex", "mg_sam_stream_file_ex", "mg_bam_stream_file_ex",
+    "mg_sam_batch_places_download", "mg_sam_batch_places_device_ptr",
+    "mg_coverage_create", "mg_coverage_add_dev", "mg_coverage_result", "mg_coverage_free",
     "mg_gunzip_open", "mg_gunzip_read", "mg_gunzip_close", "mg_zcat_files", "mg_stream_thin_file",
     "mg_inflate_dev", "mg_inflated_bytes", "mg_inflated_download", "mg_inflated_free", "mg_inflate_config", "mg_inflate_stats",
     "mg_sketch_genomes", "mg_sketch_genomes_prefix", "mg_db_upload", "mg_db_upload_sorted", "mg_db_ngenomes", "mg_db_max_hash", "mg_db_free",
@@ -71,6 +74,14 @@ class HipError(RuntimeError):
 
 
 ERR_HIP, ERR_ARG, ERR_CAPACITY, ERR_STATE, ERR_NOMEM = -1, -2, -3, -4, -5
+# what a batch carries beside its records (include/metalign_hip.h: MG_BATCH_*), and a record's place (mg_aln_place)
+BATCH_KEYS, BATCH_NAMES, BATCH_PLACES, BATCH_COLLATE = 1, 2, 4, 8
+PLACE_DTYPE = np.dtype([("pos0", np.uint32), ("span", np.uint32)])
+
+
+def _want(keyed=False, named=False, placed=False, collate=False):
+    return ctypes.c_uint((BATCH_KEYS if keyed else 0) | (BATCH_NAMES if named else 0) | (BATCH_PLACES if placed else 0)
+                         | (BATCH_COLLATE if collate else 0))
 
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -116,6 +127,7 @@ def load_library(path=LIB_PATH):
     lib.mg_refdb_distinct_kmers.restype = ctypes.c_uint64
     lib.mg_kcounts_free.restype = None
     lib.mg_profile_free.restype = None
+    lib.mg_coverage_free.restype = None
     lib.mg_shutdown.restype = None
     return lib
 
@@ -962,6 +974,18 @@ class SamBatch:
         self.hip._chk(self.hip.lib.mg_sam_batch_names_download(self.handle, _np(off, ctypes.c_uint64), _np(blob, ctypes.c_uint8)))
         return blob[: nb.value].tobytes(), off
 
+    def places(self):
+        """A placed batch's places, PLACE_DTYPE[count] in record order (mg_sam_batch_places_download); ERR_STATE without them."""
+        pl = np.zeros(self.count, dtype=PLACE_DTYPE)
+        self.hip._chk(self.hip.lib.mg_sam_batch_places_download(self.handle, _vp(pl.ctypes.data if self.count else None)))
+        return pl
+
+    @property
+    def places_ptr(self):
+        p = _vp()
+        self.hip._chk(self.hip.lib.mg_sam_batch_places_device_ptr(self.handle, ctypes.byref(p)))
+        return p.value or 0
+
     def collate(self, want_perm=False):
         """A keyed batch regrouped by read in place, its keys freed (mg_sam_batch_collate_dev; metalign_amd/collate.py is the
         definition).  want_perm: -> uint64[count], the index of the record that now comes t-th."""
@@ -979,6 +1003,58 @@ class SamBatch:
     def free(self):
         if self.handle:
             self.hip.lib.mg_sam_batch_free(self.handle)
+            self.handle = None
+
+
+class Coverage:
+    """One bit per reference base on the device and the per-accession sums (mg_coverage_*; metalign_amd/coverage.py is the
+    definition).  lengths: one per accession row.  HipError with code ERR_NOMEM when the bitmap does not fit."""
+
+    def __init__(self, hip, lengths):
+        self.hip = hip
+        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
+        self.nacc = int(ln.size)
+        h = _vp()
+        hip._chk(hip.lib.mg_coverage_create(_np(ln if ln.size else np.zeros(1, np.uint64), ctypes.c_uint64), ctypes.c_uint32(self.nacc),
+                                            ctypes.byref(h)))
+        self.handle = h
+
+    def add_ptr(self, d_recs, d_places, n, pct_id):
+        """n records and their places at device pointers (asynchronous; the arrays must outlive the next synchronisation)."""
+        self.hip._chk(self.hip.lib.mg_coverage_add_dev(self.handle, _vp(d_recs), _vp(d_places), ctypes.c_uint64(int(n)),
+                                                       ctypes.c_double(float(pct_id))))
+
+    def add_batch(self, batch, pct_id):
+        """A placed SamBatch."""
+        if batch.count:
+            self.add_ptr(batch.ptr, batch.places_ptr, batch.count, pct_id)
+            self.hip.sync()
+
+    def add(self, recs, places, pct_id):
+        """Host arrays REC_DTYPE[n], PLACE_DTYPE[n]."""
+        recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
+        places = np.ascontiguousarray(places, dtype=PLACE_DTYPE)
+        assert len(recs) == len(places)
+        if not len(recs):
+            return
+        d_r, d_p = self.hip.array(recs.view(np.uint8)), self.hip.array(places.view(np.uint8))
+        try:
+            self.add_ptr(d_r.ptr, d_p.ptr, len(recs), pct_id)
+            self.hip.sync()
+        finally:
+            d_r.free()
+            d_p.free()
+
+    def result(self):
+        """-> (alignments, aligned_bases, covered_bases) uint64[nacc] each, unplaced."""
+        out = [np.zeros(max(self.nacc, 1), dtype=np.uint64) for _ in range(3)]
+        unplaced = ctypes.c_uint64(0)
+        self.hip._chk(self.hip.lib.mg_coverage_result(self.handle, *[_np(a, ctypes.c_uint64) for a in out], ctypes.byref(unplaced)))
+        return tuple(a[:self.nacc] for a in out) + (int(unplaced.value),)
+
+    def free(self):
+        if self.handle:
+            self.hip.lib.mg_coverage_free(self.handle)
             self.handle = None
 
 
@@ -1070,6 +1146,10 @@ class Hip:
 
     def sync(self):
         self._chk(self.lib.mg_sync())
+
+    def coverage(self, lengths):
+        """A Coverage over accessions of these lengths (mg_coverage_create)."""
+        return Coverage(self, lengths)
 
     def array(self, host, dtype=None):
         host = np.ascontiguousarray(host, dtype=dtype)
@@ -1422,12 +1502,18 @@ class Hip:
         self.lib.mg_sam_batch_free(h)
         return n
 
-    def sam_tokenize_dev_batch(self, d_text, nbytes, acc_index, prev_qname="", paf=False, named=False):
+    def sam_tokenize_dev_batch(self, d_text, nbytes, acc_index, prev_qname="", paf=False, named=False, placed=False, keyed=False,
+                               collate=False):
         """SAM (or, paf=True, PAF) text resident in HBM -> SamBatch (records stay on the device).  SamParseError as
-        sam_tokenize.  named: the batch also carries the reads' names (mg_sam_tokenize_named_dev; SamBatch.names)."""
+        sam_tokenize.  named: the batch also carries the reads' names (mg_sam_tokenize_named_dev; SamBatch.names).  placed (with
+        any of named / keyed / collate): their places too (mg_sam_tokenize_dev_ex; SamBatch.places)."""
         h = _vp()
         kind, line = ctypes.c_int(0), ctypes.c_uint64(0)
-        if named:
+        if placed or keyed or collate:
+            rc = self.lib.mg_sam_tokenize_dev_ex(_vp(d_text), ctypes.c_uint64(nbytes), ctypes.c_int(1 if paf else 0), acc_index.handle,
+                                                 ctypes.c_char_p(prev_qname.encode()), ctypes.byref(h), ctypes.byref(kind), ctypes.byref(line),
+                                                 _want(keyed, named, placed, collate))
+        elif named:
             rc = self.lib.mg_sam_tokenize_named_dev(_vp(d_text), ctypes.c_uint64(nbytes), ctypes.c_int(1 if paf else 0), acc_index.handle,
                                                     ctypes.c_char_p(prev_qname.encode()), ctypes.byref(h), ctypes.byref(kind), ctypes.byref(line))
         else:
@@ -1468,12 +1554,22 @@ class Hip:
             d_r.free()
             d_p.free()
 
-    def sam_stream_file(self, path, acc_index, paf=False, offset=0, length=0, chunk_bytes=0, nthreads=0, collate=False, named=False):
+    def sam_stream_file(self, path, acc_index, paf=False, offset=0, length=0, chunk_bytes=0, nthreads=0, collate=False, named=False,
+                        placed=False):
         """The alignment file (SAM; paf=True: PAF; plain, gzip or BGZF) -> SamBatch, streamed through page-locked chunks
         inside the library (mg_sam_stream_file): the file read, the upload and the tokeniser overlap, and the text never
-        exists as a host array.  SamParseError for a line the reference cannot parse."""
+        exists as a host array.  SamParseError for a line the reference cannot parse.  placed: the batch carries the records'
+        places (mg_sam_stream_file_ex), with collate or named where those are on."""
         h = _vp()
         kind, line = ctypes.c_int(0), ctypes.c_uint64(0)
+        if placed:
+            rc = self.lib.mg_sam_stream_file_ex(os.fsencode(path), ctypes.c_int(1 if paf else 0), acc_index.handle, ctypes.c_uint64(int(offset)),
+                                                ctypes.c_uint64(int(length)), ctypes.c_uint64(int(chunk_bytes)), ctypes.c_int(int(nthreads)),
+                                                ctypes.byref(h), ctypes.byref(kind), ctypes.byref(line), _want(False, named, True, collate))
+            if rc != 0 and kind.value:
+                raise SamParseError(kind.value, line.value)
+            self._chk(rc)
+            return SamBatch(self, h)
         fn = self.lib.mg_sam_stream_file_collated if collate else self.lib.mg_sam_stream_file  # (collate: regrouped by read)
         if named:  # (the batch also carries the reads' names; never together with collate)
             assert not collate
@@ -1486,12 +1582,19 @@ class Hip:
         self._chk(rc)
         return SamBatch(self, h)
 
-    def bam_stream_file(self, path, acc_index, chunk_bytes=0, nthreads=0, collate=False, named=False):
+    def bam_stream_file(self, path, acc_index, chunk_bytes=0, nthreads=0, collate=False, named=False, placed=False):
         """A BAM file -> SamBatch: the records its SAM rendering gives through sam_stream_file (mg_bam_stream_file).  SamParseError
         for a record whose rendering the reference cannot parse, that the device does not decide (kind 6) or that is not a BAM
         record the package takes (kind 7); `line` is the record's number within its piece."""
         h = _vp()
         kind, rec = ctypes.c_int(0), ctypes.c_uint64(0)
+        if placed:  # (the batch carries the records' places: mg_bam_stream_file_ex)
+            rc = self.lib.mg_bam_stream_file_ex(os.fsencode(path), acc_index.handle, ctypes.c_uint64(int(chunk_bytes)), ctypes.c_int(int(nthreads)),
+                                                ctypes.byref(h), ctypes.byref(kind), ctypes.byref(rec), _want(False, named, True, collate))
+            if rc != 0 and kind.value:
+                raise SamParseError(kind.value, rec.value)
+            self._chk(rc)
+            return SamBatch(self, h)
         fn = self.lib.mg_bam_stream_file_collated if collate else self.lib.mg_bam_stream_file  # (collate: regrouped by read)
         if named:  # (the batch also carries the reads' names; never together with collate)
             assert not collate
@@ -1503,7 +1606,7 @@ class Hip:
         self._chk(rc)
         return SamBatch(self, h)
 
-    def bam_tokenize_dev(self, d_bytes, nbytes, refmap, acc_index, prev_qname="", final=True, keyed=False, named=False):
+    def bam_tokenize_dev(self, d_bytes, nbytes, refmap, acc_index, prev_qname="", final=True, keyed=False, named=False, placed=False):
         """BAM record bytes resident in HBM (behind the header) -> (SamBatch, consumed) (mg_bam_tokenize_dev); refmap: the accession row
         of every header reference (-1: none, -2: not one SAM field).  SamParseError as bam_stream_file."""
         rm = np.ascontiguousarray(refmap, dtype=np.int32)
@@ -1513,10 +1616,13 @@ class Hip:
         if named:
             assert not keyed
             fn = self.lib.mg_bam_tokenize_named_dev
+        extra = ()
+        if placed:  # (the batch carries the records' places)
+            fn, extra = self.lib.mg_bam_tokenize_dev_ex, (_want(keyed, named, True),)
         rc = fn(_vp(d_bytes), ctypes.c_uint64(nbytes), _np(rm if rm.size else np.zeros(1, np.int32), ctypes.c_int32),
                                           ctypes.c_uint32(rm.size), acc_index.handle, ctypes.c_char_p(prev_qname.encode()),
                                           ctypes.c_int(1 if final else 0), ctypes.byref(used), ctypes.byref(h), ctypes.byref(kind),
-                                          ctypes.byref(rec))
+                                          ctypes.byref(rec), *extra)
         if rc != 0 and kind.value:
             raise SamParseError(kind.value, rec.value)
         self._chk(rc)
@@ -1532,7 +1638,7 @@ class Hip:
                                               ctypes.c_uint32(len(names)), ctypes.byref(h)))
         return AccIndex(self, h)
 
-    def sam_tokenize(self, text, acc_index, prev_qname="", paf=False, named=False):
+    def sam_tokenize(self, text, acc_index, prev_qname="", paf=False, named=False, placed=False):
         """One chunk of SAM (paf=True: PAF) text (ending on a line boundary) -> (records REC_DTYPE[], QNAME of its last
         retained line).  Raises SamParseError for a line the reference cannot parse.  named: -> (records, last QNAME, (name bytes,
         offsets)) — the names of the reads that open in this chunk (mg_sam_tokenize_named)."""
@@ -1540,7 +1646,11 @@ class Hip:
         h = _vp()
         kind, line = ctypes.c_int(0), ctypes.c_uint64(0)
         src = buf if buf.size else np.zeros(1, np.uint8)
-        if named:
+        if placed:  # (one more element at the end of what is returned: the records' places, PLACE_DTYPE[])
+            rc = self.lib.mg_sam_tokenize_ex(_np(src, ctypes.c_uint8), ctypes.c_uint64(buf.size), ctypes.c_int(1 if paf else 0),
+                                             acc_index.handle, ctypes.c_char_p(prev_qname.encode()), ctypes.byref(h),
+                                             ctypes.byref(kind), ctypes.byref(line), _want(False, named, True))
+        elif named:
             rc = self.lib.mg_sam_tokenize_named(_np(src, ctypes.c_uint8), ctypes.c_uint64(buf.size), ctypes.c_int(1 if paf else 0),
                                                 acc_index.handle, ctypes.c_char_p(prev_qname.encode()), ctypes.byref(h),
                                                 ctypes.byref(kind), ctypes.byref(line))
@@ -1558,14 +1668,19 @@ class Hip:
             if n:
                 self._chk(self.lib.mg_sam_batch_download(h, _vp(recs.ctypes.data)))
             last = self.lib.mg_sam_batch_last_qname(h).decode("utf-8", "replace")
+            tail = ()
+            if placed:
+                pl = np.zeros(n, dtype=PLACE_DTYPE)
+                self._chk(self.lib.mg_sam_batch_places_download(h, _vp(pl.ctypes.data if n else None)))
+                tail = (pl,)
             if named:
                 nr, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
                 self._chk(self.lib.mg_sam_batch_names_size(h, ctypes.byref(nr), ctypes.byref(nb)))
                 off = np.zeros(nr.value + 1, dtype=np.uint64)
                 blob = np.zeros(max(nb.value, 1), dtype=np.uint8)
                 self._chk(self.lib.mg_sam_batch_names_download(h, _np(off, ctypes.c_uint64), _np(blob, ctypes.c_uint8)))
-                return recs, last, (blob[: nb.value].tobytes(), off)
-            return recs, last
+                return (recs, last, (blob[: nb.value].tobytes(), off)) + tail
+            return (recs, last) + tail
         finally:
             self.lib.mg_sam_batch_free(h)
 

@@ -50,6 +50,10 @@ _OPTIONS = {
     'read_assignments': dict(default='NONE', help='Also write every read\'s verdict here, one TSV line per read in file order: '
                              'read, class (U unique / M multimapped / A ambiguous / N not counted: the last read), taxids, hit bases '
                              '(metalign_amd/assignments.py is the definition). One process only.'),
+    'coverage': dict(default='NONE', help='Also write breadth and depth of coverage here (TSV): per accession (S rows) and per '
+                     'genome (G rows) the placed alignments, aligned bases, covered bases, breadth, mean depth and the breadth that '
+                     'depth predicts, from the alignments stage C keeps (metalign_amd/coverage.py is the definition). SAM / BAM '
+                     'input, one process only.'),
     'device_multimap': dict(action='store_true', help='Resolve multimapped reads on the GPU (their lists never leave '
                             'the device; abundances equal the default path to ~1e-15 relative, not byte for byte).'),
 }
@@ -65,7 +69,7 @@ _TOOLS = {
         options=['cutoff', 'db_dir', 'dbinfo_in', 'keep_temp_files', ('input_type', _READ_TYPES), 'length_normalize',
                  'low_mem', 'min_abundance', 'no_quantify_unmapped', 'output', 'pct_id', 'precise', 'rank_renormalize',
                  'read_cutoff', 'sampleID', 'sensitive', 'strain_level', 'temp_dir', 'threads', 'verbose',
-                 'sketch_table', 'min_count', 'sketch_size', 'kmer_match', 'device_multimap', 'collate', 'read_assignments']),
+                 'sketch_table', 'min_count', 'sketch_size', 'kmer_match', 'device_multimap', 'collate', 'read_assignments', 'coverage']),
     'select_db': dict(
         description='Run CMash and select a subset of the whole database to align to.',
         positionals=[('reads', dict(help='Reads file (FASTA / FASTQ, optionally .gz, or a BAM of reads).')),
@@ -80,7 +84,7 @@ _TOOLS = {
         options=[('db', 'NONE', 'Database FASTA from select_db (needed unless the inputs are SAM files).'), 'dbinfo',
                  ('input_type', ['fastq', 'fasta', 'sam', 'AUTO']), 'length_normalize', 'low_mem', 'min_abundance',
                  'rank_renormalize', 'output', 'pct_id', 'no_quantify_unmapped', 'read_cutoff', 'sampleID', 'threads',
-                 'verbose', 'device_multimap', 'collate', 'read_assignments']),
+                 'verbose', 'device_multimap', 'collate', 'read_assignments', 'coverage']),
 }
 
 

@@ -79,6 +79,13 @@ __global__ __launch_bounds__(256) void k_collate_gather(const mg_aln_rec* __rest
   }
 }
 
+// ... and a placed batch's places the same way: out[t] = place[perm[t]]
+__global__ __launch_bounds__(256) void k_collate_gather_places(const mg_aln_place* __restrict__ place, const uint64_t* __restrict__ perm,
+                                                               uint64_t n, mg_aln_place* __restrict__ out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += stride) out[t] = place[perm[t]];
+}
+
 // keys and flags -> d_perm[t] = the index of the record that comes t-th; *d_fkey (optional) = the sorted final keys (scratch:
 // valid until the next collation).  n > 0.
 static int collate_order(const uint64_t* d_keys2, const mg_aln_rec* d_recs, uint64_t n, uint64_t* d_perm, const uint64_t** d_fkey) {
@@ -124,11 +131,19 @@ int collate_batch(mg_sam_batch* b, uint64_t* d_perm_or_null) {
     MG_TRY(collate_order(b->keys.as<uint64_t>(), b->recs.as<mg_aln_rec>(), n, d_perm, &d_fkey));
     DevBuf out;  // (until here a failure leaves the batch as it was)
     MG_TRY(out.alloc((n + 1) * sizeof(mg_aln_rec)));
+    DevBuf out_places;
+    if (b->placed) {
+      MG_TRY(out_places.alloc((n + 1) * sizeof(mg_aln_place)));
+      hipLaunchKernelGGL(k_collate_gather_places, dim3(grid_for(n, 256, (unsigned)ctx().num_cus * 16)), dim3(256), 0, st,
+                         b->places.as<mg_aln_place>(), d_perm, n, out_places.as<mg_aln_place>());
+      MG_HIP(hipGetLastError());
+    }
     hipLaunchKernelGGL(k_collate_gather, dim3(grid_for(n, 256, (unsigned)ctx().num_cus * 16)), dim3(256), 0, st, b->recs.as<mg_aln_rec>(),
                        d_perm, d_fkey, n, out.as<mg_aln_rec>());
     MG_HIP(hipGetLastError());
     MG_HIP(hipStreamSynchronize(st));
     b->recs = std::move(out);
+    if (b->placed) b->places = std::move(out_places);
   }
   b->keys.release();
   b->keyed = false;

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "mg_collate_core.h"
+#include "mg_coverage_core.h"
 #include "mg_internal.h"
 
 namespace mg {
@@ -573,6 +574,28 @@ __global__ __launch_bounds__(256) void k_name_gather(const uint8_t* __restrict__
   }
 }
 
+// PLACED (--coverage): record r is retained line ret_line[r]; its POS (field 4) and CIGAR (field 6) -> place[r] (mg_coverage_core.h).
+// The line is split again from its start (line_end[l - 1] + 1) on the parser's white space; on thinned text fields 1 to 9 are as
+// they were.  One thread per record: ~40 bytes of the line's front, which the parse has just pulled through the caches — read a
+// byte at a time, which makes this the dearest step of --coverage; the follow-up is the parser's own remedy, 8-byte
+// loads, or several lanes per line.
+__global__ __launch_bounds__(256) void k_sam_place(const uint8_t* __restrict__ text, const uint64_t* __restrict__ line_end, const uint64_t* __restrict__ ret_line,
+                            uint64_t nret, mg_aln_place* __restrict__ place) {
+  uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (; r < nret; r += stride) {
+    const uint64_t l = ret_line[r];
+    place[r] = mgv::place_of_line(text, l == 0 ? 0 : line_end[l - 1] + 1, line_end[l]);
+  }
+}
+// ... of a BAM record (mg_bam.hip's decode left the QNAME's offset in the line: the fixed part lies in front of it, the ops behind)
+__global__ __launch_bounds__(256) void k_bam_place(const uint8_t* __restrict__ bytes, const LineOut* __restrict__ lines, const uint64_t* __restrict__ ret_line,
+                            uint64_t nret, mg_aln_place* __restrict__ place) {
+  uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (; r < nret; r += stride) place[r] = mgv::place_of_bam(bytes, lines[ret_line[r]].qbeg);
+}
+
 // Shared: build the line index of a text buffer.  If the text does not end in '\n' the last partial
 // line is terminated virtually.  -> d_line_end (scratch "ing_lines"), *nlines.
 // last_end (optional): the end of the last line, brought back in the same round trip as the marks' completion (a piece of a
@@ -873,9 +896,10 @@ __global__ void k_sam_last_qname(const uint8_t* __restrict__ text, const LineOut
 // the byte after the last newline (what follows is carried to the next piece by the caller, mg_stream.hip).
 int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg_acc_index* ix, const char* prev_qname,
                                 bool paf, bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_line,
-                                bool thin, bool keyed, bool named) {
+                                bool thin, bool keyed, bool named, bool placed) {
   MG_REQUIRE_READY();
   if (!out || !ix) return fail(MG_ERR_ARG, "null argument");
+  if (placed && paf) return fail(MG_ERR_ARG, "a PAF line has no POS and CIGAR columns: no places from PAF");
   *out = nullptr;
   if (err_kind) *err_kind = 0;
   if (err_line) *err_line = 0;
@@ -894,6 +918,7 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
     MG_TRY(sb->recs.alloc(16));
     if (keyed) MG_TRY(sb->keys.alloc(16));
     if (named) MG_TRY(names_empty(sb.get()));
+    if (placed) MG_TRY(places_empty(sb.get()));
     *out = sb.release();
     return MG_OK;
   }
@@ -932,7 +957,8 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
       if (err_line) *err_line = h_err;
       return fail(MG_ERR_ARG, "%s line %llu: parse error kind %u", paf ? "PAF" : "SAM", h_err, kind);
     }
-    MG_TRY(aln_emit_retained(d_text, d_lines, d_ret, d_rank, nlines, nret, d_prev, (uint32_t)plen, sb.get(), keyed, named));
+    MG_TRY(aln_emit_retained(d_text, d_lines, d_ret, d_rank, nlines, nret, d_prev, (uint32_t)plen, sb.get(), keyed, named,
+                             placed ? kPlaceSam : kPlaceNone, d_le));
   }
   sb->nrecs = nret;
   *out = sb.release();
@@ -942,12 +968,18 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
 // The retained lines (d_ret[l] = 1, d_rank = its exclusive prefix, nret of them) -> sb->recs with the new-read bit, and
 // sb->last_qname.  The SAM / PAF tokeniser above and the BAM decoder (mg_bam.hip) end here.
 int mg::aln_emit_retained(const uint8_t* d_text, const LineOut* d_lines, const uint32_t* d_ret, const uint64_t* d_rank, uint64_t nlines,
-                          uint64_t nret, const uint8_t* d_prev, uint32_t plen, mg_sam_batch* sb, bool keyed, bool named) {
+                          uint64_t nret, const uint8_t* d_prev, uint32_t plen, mg_sam_batch* sb, bool keyed, bool named, int placed,
+                          const uint64_t* d_line_end) {
   Context& c = ctx();
   hipStream_t st = c.stream;
   MG_TRY(sb->recs.alloc((nret + 1) * sizeof(mg_aln_rec)));
   sb->keyed = keyed;
   if (keyed) MG_TRY(sb->keys.alloc((nret + 1) * 2 * sizeof(uint64_t)));
+  if (placed) {
+    if (placed == kPlaceSam && !d_line_end) return fail(MG_ERR_ARG, "places from text need its line index");
+    MG_TRY(sb->places.alloc((nret + 1) * sizeof(mg_aln_place)));
+    sb->placed = true;
+  }
   if (nret) {
     uint64_t* d_list = (uint64_t*)scratch("sam_list", nret * sizeof(uint64_t));
     if (!d_list) return MG_ERR_NOMEM;
@@ -960,6 +992,15 @@ int mg::aln_emit_retained(const uint8_t* d_text, const LineOut* d_lines, const u
       hipLaunchKernelGGL(k_sam_emit<false>, dim3(grid_for(nret, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_text, d_lines,
                          d_list, nret, d_prev, plen, sb->recs.as<mg_aln_rec>(), (uint64_t*)nullptr);
     MG_HIP(hipGetLastError());
+    if (placed) {  // (before the round trip below: its synchronisation covers this launch too)
+      ProfScope ps("ingest_places");
+      const unsigned grid = grid_for(nret, 256, (unsigned)c.num_cus * 16);
+      if (placed == kPlaceSam)
+        hipLaunchKernelGGL(k_sam_place, dim3(grid), dim3(256), 0, st, d_text, d_line_end, d_list, nret, sb->places.as<mg_aln_place>());
+      else
+        hipLaunchKernelGGL(k_bam_place, dim3(grid), dim3(256), 0, st, d_text, d_lines, d_list, nret, sb->places.as<mg_aln_place>());
+      MG_HIP(hipGetLastError());
+    }
     // QNAME of the last retained line, for the next chunk: its span and its first kQnameInline bytes in ONE round trip
     // (three dependent ones — line number, span, bytes — were a quarter of a streamed piece's host time)
     uint8_t* d_q = (uint8_t*)scratch("sam_lastq", 16 + kQnameInline);
@@ -1015,6 +1056,12 @@ int mg::aln_emit_retained(const uint8_t* d_text, const LineOut* d_lines, const u
   return MG_OK;
 }
 
+int mg::places_empty(mg_sam_batch* sb) {
+  MG_TRY(sb->places.alloc(16));
+  sb->placed = true;
+  return MG_OK;
+}
+
 int mg::names_empty(mg_sam_batch* sb) {
   MG_TRY(sb->name_off.alloc(2 * sizeof(uint64_t)));
   MG_TRY(sb->name_bytes.alloc(16));
@@ -1039,6 +1086,48 @@ int mg_sam_tokenize_named(const uint8_t* text, uint64_t nbytes, int paf, const m
   MG_TRY(d_text.alloc(nbytes + 16));
   MG_TRY(mg_memcpy_h2d(d_text.p, text, nbytes));
   return mg_sam_tokenize_named_dev(d_text.as<uint8_t>(), nbytes, paf, ix, prev_qname, out, err_kind, err_line);
+}
+
+// The flag-taking family: what the plain, keyed, named and collated calls give, and the places, by one mask.
+int mg_sam_tokenize_dev_ex(const uint8_t* d_text, uint64_t nbytes, int paf, const mg_acc_index* ix, const char* prev_qname,
+                           mg_sam_batch** out, int* err_kind, uint64_t* err_line, unsigned want) {
+  if (want & ~(MG_BATCH_KEYS | MG_BATCH_NAMES | MG_BATCH_PLACES | MG_BATCH_COLLATE)) return fail(MG_ERR_ARG, "unknown bits in want");
+  if ((want & MG_BATCH_PLACES) && paf) return fail(MG_ERR_ARG, "a PAF line has no POS and CIGAR columns: no places from PAF");
+  if ((want & MG_BATCH_NAMES) && (want & MG_BATCH_COLLATE))
+    return fail(MG_ERR_STATE, "a named batch is not collated (its names are in the order the reads came in)");
+  const bool collate = (want & MG_BATCH_COLLATE) != 0;
+  MG_TRY(mg::aln_tokenize_prefix_dev(d_text, nbytes, ix, prev_qname, paf != 0, true, nullptr, out, err_kind, err_line, false,
+                                     collate || (want & MG_BATCH_KEYS), (want & MG_BATCH_NAMES) != 0, (want & MG_BATCH_PLACES) != 0));
+  if (collate) {
+    const int rc = mg::collate_batch(*out, nullptr);
+    if (rc != MG_OK) { delete *out; *out = nullptr; return rc; }
+  }
+  return MG_OK;
+}
+
+int mg_sam_tokenize_ex(const uint8_t* text, uint64_t nbytes, int paf, const mg_acc_index* ix, const char* prev_qname,
+                       mg_sam_batch** out, int* err_kind, uint64_t* err_line, unsigned want) {
+  MG_REQUIRE_READY();
+  DevBuf d_text;
+  MG_TRY(d_text.alloc(nbytes + 16));
+  MG_TRY(mg_memcpy_h2d(d_text.p, text, nbytes));
+  return mg_sam_tokenize_dev_ex(d_text.as<uint8_t>(), nbytes, paf, ix, prev_qname, out, err_kind, err_line, want);
+}
+
+int mg_sam_batch_places_download(const mg_sam_batch* b, mg_aln_place* places) {
+  MG_REQUIRE_READY();
+  if (!b) return fail(MG_ERR_ARG, "null batch");
+  if (!b->placed) return fail(MG_ERR_STATE, "the batch carries no places (tokenise it with MG_BATCH_PLACES)");
+  if (b->nrecs && !places) return fail(MG_ERR_ARG, "null argument");
+  if (b->nrecs) MG_TRY(mg_memcpy_d2h(places, b->places.p, b->nrecs * sizeof(mg_aln_place)));
+  return MG_OK;
+}
+
+int mg_sam_batch_places_device_ptr(const mg_sam_batch* b, const mg_aln_place** d_places) {
+  if (!b || !d_places) return fail(MG_ERR_ARG, "null argument");
+  if (!b->placed) return fail(MG_ERR_STATE, "the batch carries no places (tokenise it with MG_BATCH_PLACES)");
+  *d_places = b->places.as<mg_aln_place>();
+  return MG_OK;
 }
 
 int mg_sam_batch_names_size(const mg_sam_batch* b, uint64_t* nreads, uint64_t* nbytes) {

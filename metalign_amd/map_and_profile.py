@@ -29,7 +29,7 @@ import time
 
 import numpy as np
 
-from . import _hip, assignments, bam, cli, collate
+from . import _hip, assignments, bam, cli, collate, coverage
 
 start = time.time()
 RANKS = ['superkingdom', 'phylum', 'class', 'order', 'family', 'genus', 'species', 'strain']
@@ -274,12 +274,47 @@ def _join_names(parts):
     return b''.join(blobs), np.concatenate(offs)
 
 
-def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names=None):
+def _host_places(lines):
+    """The places of the lines the host tokeniser retains (coverage.placement), PLACE_DTYPE[] in record order."""
+    out = []
+    for ln in lines:
+        f = coverage.retained_fields(ln)
+        if f is not None:
+            out.append(coverage.placement(f))
+    return np.array(out, dtype=_hip.PLACE_DTYPE) if out else np.zeros(0, dtype=_hip.PLACE_DTYPE)
+
+
+def _leading_header(chunk, header, state):
+    """--coverage on the chunked path: the stream's leading '@' lines -> header, scanned only while lines start with '@'."""
+    if not state['leading']:
+        return
+    view = memoryview(chunk)
+    pos, n = 0, len(view)
+    while pos < n:
+        if view[pos] != 0x40:
+            state['leading'] = False
+            return
+        end = pos
+        while end < n:
+            seg = bytes(view[end:end + (1 << 16)])
+            k = seg.find(b'\n')
+            if k >= 0:
+                end += k + 1
+                break
+            end += len(seg)
+        header.append(bytes(view[pos:end]))
+        pos = end
+
+
+def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names=None, places=None, header=None):
     """SAM (paf=True: PAF) stream -> records on the MI355X (mg_sam_tokenize / mg_paf_tokenize).  A line the reference
     cannot parse is re-run through the host tokeniser so that the very same exception (type and message) surfaces.
     read_names (--read_assignments): a list that takes every chunk's read names, (bytes, offsets) from mg_sam_tokenize_named — a read that
-    goes on from the chunk before is named there."""
+    goes on from the chunk before is named there.
+    places (--coverage): a list that takes every chunk's places (PLACE_DTYPE[], beside its records); header: a list that takes the
+    stream's leading '@' lines as the chunks pass."""
     hip = _hip.Hip.get()
+    hstate = {'leading': True}
     names = [None] * len(acc_index)
     for a, i in acc_index.items():
         names[i] = a
@@ -287,8 +322,16 @@ def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names
     parts, prev = [], ''
     try:
         for chunk in _line_chunks(instream, decode):
+            if header is not None:
+                _leading_header(chunk, header, hstate)
             try:
-                if read_names is not None:
+                if places is not None:
+                    got = hip.sam_tokenize(chunk, index, prev, paf=paf, named=read_names is not None, placed=True)
+                    recs, prev = got[0], got[1]
+                    if read_names is not None:
+                        read_names.append(got[2])
+                    places.append(got[-1])
+                elif read_names is not None:
                     recs, prev, nm = hip.sam_tokenize(chunk, index, prev, paf=paf, named=True)
                     read_names.append(nm)
                 else:
@@ -316,6 +359,8 @@ def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names
                     recs, prev, host_names = tk.records(), tk.prev, tk.names
                 if read_names is not None:
                     read_names.append(_pack_names(host_names))
+                if places is not None:
+                    places.append(_host_places(ln.decode('utf-8') for ln in lines))
             parts.append(recs)
     finally:
         index.free()
@@ -409,6 +454,40 @@ def _append_assignments(args, rows):
     assignments.write_assignments(args.read_assignments, rows, append=True)
 
 
+def _wants_coverage(args):
+    return getattr(args, 'coverage', 'NONE') not in (None, 'NONE')  # (callers build Namespaces without it)
+
+
+def _coverage_open(hip, lengths, acc_index):
+    """--coverage for one input file: the device's bitmap over its lengths (coverage.lengths_of: the file's @SQ lines over db_info's)."""
+    arr = np.zeros(len(acc_index), dtype=np.uint64)
+    for a, i in acc_index.items():
+        arr[i] = lengths[a]
+    try:
+        return hip.coverage(arr)
+    except _hip.HipError as e:
+        if e.code != _hip.ERR_NOMEM:
+            raise
+        sys.exit('Error: --coverage keeps one bit per reference base on the GPU; %d MB for this database do not fit.'
+                 % (int(arr.sum()) >> 23))
+
+
+def _append_coverage(args, path, cov, acc2info, taxid2info):
+    """One input file's block behind those of the files before it (map_main wrote the column header)."""
+    source = path if len(getattr(args, 'infiles', [])) > 1 else None
+    coverage.write_coverage(args.coverage, coverage.rows(cov, acc2info, taxid2info), cov.unplaced, source=source, append=True)
+
+
+def _coverage_close(args, path, lengths, dev, acc_index, acc2info, taxid2info):
+    """The device's sums -> the file's block."""
+    try:
+        aln, bases, covered, unplaced = dev.result()
+    finally:
+        dev.free()
+    per = {a: [int(aln[i]), int(bases[i]), int(covered[i])] for a, i in acc_index.items() if aln[i]}
+    _append_coverage(args, path, coverage.Coverage(lengths, per, unplaced), acc2info, taxid2info)
+
+
 def assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=True):
     """Kernel outputs -> the (taxids2abs, multimapped, low_mem_mmap) triple of the reference (:193-264).
     want_lists=False leaves `multimapped` as the CSR dict for the vectorised tail (compute_abundances)."""
@@ -439,7 +518,7 @@ def assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=True):
 
 
 def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _resident=False, _paf=False, _bam=False, _collate=False,
-                         _assignments=False):
+                         _assignments=False, _coverage=None):
     """map_and_process for a plain SAM FILE, without the text or the records ever being host arrays: the file goes up
     through page-locked chunks (Hip.upload_file), is tokenised where it lands and stage C runs on the records the
     tokeniser left in HBM.  A line the reference cannot parse makes this return None: the caller then takes the
@@ -448,8 +527,11 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
     _collate: the file's records regrouped by read on the device before stage C (mg_*_stream_file_collated; the definition is
     collate.collated_lines, which the caller falls back to on None).
     _assignments (--read_assignments): the tokeniser also keeps the reads' names, stage C also writes every read's verdict and the rows
-    are appended to args.read_assignments; never together with _collate (a named batch is not collated)."""
+    are appended to args.read_assignments; never together with _collate (a named batch is not collated).
+    _coverage (--coverage): the file's header lines — the batch also carries the records' places, which feed the coverage bitmap
+    before stage C takes the batch, and the file's block is appended to args.coverage."""
     assert not (_assignments and _collate)
+    placed = _coverage is not None
     acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
     _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
     hip = _hip.Hip.get()
@@ -457,12 +539,14 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
     for a, i in acc_index.items():
         names[i] = a
     index = hip.acc_index(names)
-    d_text = batch = None
+    d_text = batch = cov_lengths = cov_dev = None
     try:
         # the text plus ~60 B per line of line index and tokeniser output must fit beside what is resident already:
         # otherwise straight to the streaming path (256 MB chunks), without first filling the device and failing
         free, _, pooled = hip.mem_info()
         streamed = os.environ.get('MG_NO_STREAM') != '1'
+        if placed and not streamed and _is_gzip(path):
+            streamed = True  # (the whole-text call has no inflater in front of it: a compressed file's places come from the stream)
         # (streamed: only the 16-byte records — ~1/20 of the text — and three chunks of text are ever resident)
         need = os.path.getsize(path) // 8 if streamed or _collate else 2 * os.path.getsize(path)
         if _collate:
@@ -473,10 +557,22 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
         if _assignments:
             # per read 16 B of verdict words, 8 B of name offset and the name itself (~40 B); a read is at least one record
             need += 64 * (os.path.getsize(path) // (50 if _bam or _is_gzip(path) else 100))
+        if placed:
+            # 8 B of place per record (and as much again where a collation permutes them) and one bit per reference base
+            need += 16 * (os.path.getsize(path) // (50 if _bam or _is_gzip(path) else 100))
+            cov_lengths = coverage.lengths_of(_coverage, acc2info)
+            need += sum(cov_lengths.values()) // 8
         if need > free + pooled:
             return None
         try:
-            if _bam:  # (a BAM is always streamed: ~16 B of records per ~60 B of the compressed file stay resident)
+            if placed and not streamed and not _bam and not _collate:  # (one call over the whole text: the flag-taking tokeniser)
+                d_text, size = hip.upload_file(path)
+                batch = hip.sam_tokenize_dev_batch(d_text.ptr, size, index, '', named=_assignments, placed=True)
+            elif placed:
+                stream = hip.bam_stream_file if _bam else hip.sam_stream_file
+                batch = stream(path, index, chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)), collate=_collate,
+                               named=_assignments, placed=True)
+            elif _bam:  # (a BAM is always streamed: ~16 B of records per ~60 B of the compressed file stay resident)
                 batch = hip.bam_stream_file(path, index, chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)), collate=_collate,
                                             named=_assignments)
             elif _collate:  # (always streamed: the keys ride on the stream's batches)
@@ -499,13 +595,22 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
         finally:
             if d_text is not None:
                 d_text.free()
+        if placed:  # (before stage C takes the batch over)
+            cov_dev = _coverage_open(hip, cov_lengths, acc_index)
+            cov_dev.add_batch(batch, float(args.pct_id))
         res = hip.profile_assign_dev_records(batch.ptr, batch.count, ref2tax, len(taxids), float(args.pct_id), [batch],
                                              resident=_resident, assign=_assignments)
         batch = None  # owned by the result now
+    except BaseException:
+        if cov_dev is not None:
+            cov_dev.free()
+        raise
     finally:
         index.free()
         if batch is not None:
             batch.free()
+    if placed:
+        _coverage_close(args, path, cov_lengths, cov_dev, acc_index, acc2info, taxid2info)
     if _assignments:
         _append_assignments(args, assignment_rows(res, taxids))
     if not _want_lists:
@@ -697,11 +802,18 @@ class _CudaWords:
         self.__cuda_array_interface__ = {'shape': (int(n),), 'typestr': '<i4', 'data': (int(ptr), False), 'version': 2}
 
 
-def map_and_process(args, instream, acc2info, taxid2info, _assign=None, _want_lists=True, _resident=False, _assignments=False):
+def map_and_process(args, instream, acc2info, taxid2info, _assign=None, _want_lists=True, _resident=False, _assignments=False,
+                    _coverage=None):
     """Reference signature (:193).  `_assign` is a test seam; product code never passes it.
     _assignments (--read_assignments): every chunk's read names are collected beside its records, stage C runs over the records
-    uploaded as one array with the verdict words written, and the rows are appended to args.read_assignments."""
+    uploaded as one array with the verdict words written, and the rows are appended to args.read_assignments.
+    _coverage (--coverage): the name the block is written under — every chunk's places are collected beside its records, the
+    lengths come from the leading '@' lines of the stream, and places and records go up together for the coverage kernels."""
     acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
+    if _coverage is not None:
+        if _assign is not None:
+            raise ValueError('--coverage needs the device path')
+        return _map_and_process_covered(args, instream, acc2info, taxid2info, _want_lists, _resident, _assignments, _coverage)
     _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
     # test seam: an injected record-level backend is fed by the host tokeniser; product code never passes one
     tokenise = _device_tokenise if _assign is None else tokenise_sam
@@ -724,6 +836,44 @@ def map_and_process(args, instream, acc2info, taxid2info, _assign=None, _want_li
     recs = tokenise(instream, acc_index, decode=(args.input_type != 'sam'))
     res = (_assign or (_device_assign_resident if _resident else _device_assign))(recs, ref2tax, len(taxids),
                                                                                   float(args.pct_id))
+    if not _want_lists:
+        res = dict(res, taxids=taxids)
+    return assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=_want_lists)
+
+
+def _map_and_process_covered(args, instream, acc2info, taxid2info, _want_lists, _resident, _assignments, source):
+    """map_and_process with --coverage (and --read_assignments where that is on)."""
+    acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
+    _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
+    names, places, header = ([] if _assignments else None), [], []
+    recs = _device_tokenise(instream, acc_index, decode=(args.input_type != 'sam'), read_names=names, places=places, header=header)
+    place = np.concatenate(places) if places else np.zeros(0, dtype=_hip.PLACE_DTYPE)
+    assert len(place) == len(recs)
+    hip = _hip.Hip.get()
+    d_recs = hip.array(recs if len(recs) else np.zeros(1, _hip.REC_DTYPE))
+    try:
+        lengths = coverage.lengths_of(header, acc2info)
+        dev = _coverage_open(hip, lengths, acc_index)
+        try:
+            if len(recs):
+                d_place = hip.array(place.view(np.uint8))
+                try:
+                    dev.add_ptr(d_recs.ptr, d_place.ptr, len(recs), float(args.pct_id))
+                    hip.sync()
+                finally:
+                    d_place.free()
+        except BaseException:
+            dev.free()
+            raise
+        _coverage_close(args, source, lengths, dev, acc_index, acc2info, taxid2info)
+    except BaseException:
+        d_recs.free()  # (stage C has not taken the records over yet)
+        raise
+    res = hip.profile_assign_dev_records(d_recs.ptr, len(recs), ref2tax, len(taxids), float(args.pct_id), [d_recs],
+                                         resident=_resident, assign=_assignments)
+    if _assignments:
+        res['names'] = _join_names(names)
+        _append_assignments(args, assignment_rows(res, taxids))
     if not _want_lists:
         res = dict(res, taxids=taxids)
     return assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=_want_lists)
@@ -912,13 +1062,16 @@ def compute_abundances(args, infile, acc2info, tax2info):
                        and _device_assign is _DEVICE_ASSIGN)  # (tests reroute them)
     paf = bool(getattr(args, 'paf_input', False))
     want_rows = _wants_assignments(args)
+    want_cov = _wants_coverage(args)
+    if want_cov and not seams_untouched:
+        raise ValueError('--coverage needs the device path')
     if args.input_type == 'sam' and not paf and bam.is_bam(infile):  # decided per file: a BAM is never SAM text
         instream.close()
         return _compute_abundances_bam(args, infile, acc2info, tax2info, on_device, seams_untouched)
     if args.input_type == 'sam' and not paf and _wants_collation(args, lambda: _sam_header_lines(infile)):
         instream.close()
         return _compute_abundances_collated(args, infile, acc2info, tax2info, on_device, seams_untouched)
-    if args.input_type == 'sam' and seams_untouched and not paf and not want_rows:
+    if args.input_type == 'sam' and seams_untouched and not paf and not want_rows and not want_cov:
         from .select_db import dist_context
         ctx = dist_context()
         if ctx is not None:  # one process per GPU: the ranks tokenise the text between them, rank 0 does the rest
@@ -930,10 +1083,10 @@ def compute_abundances(args, infile, acc2info, tax2info):
     if args.input_type == 'sam' and seams_untouched and done is None:
         # a plain file (SAM, or a PAF replay): all the way on the device
         done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _paf=paf,
-                                    _assignments=want_rows)
+                                    _assignments=want_rows, _coverage=_sam_header_lines(infile) if want_cov else None)
     if done is None:
         done = map_and_process(args, instream, acc2info, tax2info, _want_lists=False, _resident=on_device,
-                               _assignments=want_rows and seams_untouched)
+                               _assignments=want_rows and seams_untouched, _coverage=infile if want_cov else None)
     taxids2abs, mm, low_mem_mmap = done
     if args.input_type == 'sam':
         instream.close()
@@ -986,11 +1139,15 @@ def _compute_abundances_collated(args, infile, acc2info, tax2info, on_device, se
     if int(os.environ.get('RANK', '0')) != 0:
         return None
     done = None
+    want_cov = _wants_coverage(args) and seams_untouched
     if seams_untouched:
-        done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _collate=True)
+        done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _collate=True,
+                                    _coverage=_sam_header_lines(infile) if want_cov else None)
     if done is None:
         done = map_and_process(args, collate.collated_lines(_sam_file_lines(infile)), acc2info, tax2info, _want_lists=False,
                                _resident=on_device)
+        if want_cov:  # (the definition over the file's lines: coverage does not depend on their order)
+            _append_coverage(args, infile, coverage.coverage(_sam_file_lines(infile), acc2info, args.pct_id), acc2info, tax2info)
     if _wants_assignments(args):  # (a named batch is not collated: the rows of a collated input come from the definition)
         _append_assignments(args, assignments.read_assignments(collate.collated_lines(_sam_file_lines(infile)), acc2info, args.pct_id))
     taxids2abs, mm, _ = done
@@ -1007,13 +1164,19 @@ def _compute_abundances_bam(args, infile, acc2info, tax2info, on_device, seams_u
     bam.warn_about(infile, collating=collating)
     done = None
     want_rows = _wants_assignments(args)
+    want_cov = _wants_coverage(args) and seams_untouched
     if seams_untouched:
+        # (the reference list's l_ref equals the header's @SQ text: the text is what gives the lengths)
         done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _bam=True,
-                                    _collate=collating, _assignments=want_rows and not collating)
+                                    _collate=collating, _assignments=want_rows and not collating,
+                                    _coverage=_bam_header_lines(infile) if want_cov else None)
     if done is None:
         lines = bam.sam_lines(infile)
         done = map_and_process(args, collate.collated_lines(lines) if collating else lines, acc2info, tax2info, _want_lists=False,
-                               _resident=on_device, _assignments=want_rows and not collating and seams_untouched)
+                               _resident=on_device, _assignments=want_rows and not collating and seams_untouched,
+                               _coverage=infile if want_cov and not collating else None)
+        if want_cov and collating:
+            _append_coverage(args, infile, coverage.coverage(bam.sam_lines(infile), acc2info, args.pct_id), acc2info, tax2info)
     if want_rows and collating:  # (as a collated SAM file: the definition over the regrouped lines)
         _append_assignments(args, assignments.read_assignments(collate.collated_lines(bam.sam_lines(infile)), acc2info, args.pct_id))
     taxids2abs, mm, _ = done
@@ -1095,6 +1258,10 @@ def map_main(args=None):
     if _wants_assignments(args) and int(os.environ.get('WORLD_SIZE', '1')) > 1:
         # (the records the ranks gather on rank 0 carry no names: refused before the process group or a GPU is touched)
         sys.exit('Error: --read_assignments runs in one process on one GPU; start it without torch.distributed.run.')
+    if _wants_coverage(args) and int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        sys.exit('Error: --coverage runs in one process on one GPU; start it without torch.distributed.run.')
+    if _wants_coverage(args) and (getattr(args, 'paf_input', False) or any(f.endswith('.paf') for f in args.infiles)):
+        sys.exit('Error: --coverage needs SAM or BAM alignments: a PAF line has no POS and CIGAR columns.')
     args.data = cli.with_slash(args.data)
     if args.dbinfo == 'AUTO':
         args.dbinfo = args.data + 'db_info.txt'
@@ -1114,6 +1281,8 @@ def map_main(args=None):
         open(args.output, 'w').close()
         if _wants_assignments(args):
             assignments.write_assignments(args.read_assignments, [])  # the header; every input file appends its rows
+        if _wants_coverage(args):
+            coverage.write_coverage(args.coverage)  # the column header; every input file appends its block
     acc2info, taxid2info = get_acc2info(args)
     rank_results = gather_results(args, acc2info, taxid2info)
     if not getattr(args, '_not_root', False):
