@@ -94,7 +94,8 @@ int mg_device_count(void);
  *   return their batch keyed and not yet collated); genome_slab_bytes (mg_genomes_stream_open: the size of a page-locked slab,
  *   default 8 MiB, at least 4 KiB), genome_guard (test hook: mg_genomes_parse_dev fills the 16 bytes behind its bases and the
  *   word behind its offsets with 0xa5 before its kernels run); cov_grid (test hook, k3_grid's meaning for k_cov_add /
- *   k_cov_count, mg_coverage.hip).
+ *   k_cov_count, mg_coverage.hip); mm_hash_bits (test hook, mg_profile_mm_iterate_dev: only this many low bits of a list's hash
+ *   are kept, so that different lists collide).
  * Needs no device and no mg_init.  MG_ERR_ARG for a key that does not exist. */
 int mg_debug_set(const char* key, int64_t value);
 int64_t mg_debug_get(const char* key);
@@ -805,6 +806,25 @@ int mg_profile_resolve_multimapped_dev(const mg_profile* p, const double* d_weig
  * extra[ntax] and touched[ntax] are overwritten.  Plain host code: needs no device and no mg_init. */
 int mg_multimapped_shares(const uint64_t* mm_offsets, uint64_t nreads, const uint32_t* mm_tax, const uint64_t* mm_hitlen,
                           const double* weight, uint32_t ntax, const double* genome_len, double* extra, uint8_t* touched);
+/* The reassignment run as a fixed-point iteration (--multimap_iterations; metalign_amd/multimap.py is the definition): iteration
+ * i = 1, 2, ... is the step above taken with the weights w_{i-1} (w_0 = weight), then w_i[t] = weight[t] + extra_i[t] and
+ * change_i = max over the taxa with an entry of |w_i - w_{i-1}| / w_i (0 where w_i == 0); it stops after iteration i when
+ * i == max_iter (>= 1), or when tol > 0 and change_i <= tol (tol >= 0).  extra / touched are the last iteration's, so that
+ * max_iter = 1 is mg_multimapped_shares.  Every iteration is that routine's own loop (its threads and the shares_threads knob
+ * included): bit for bit the definition.  Plain host code. */
+int mg_multimapped_shares_iter(const uint64_t* mm_offsets, uint64_t nreads, const uint32_t* mm_tax, const uint64_t* mm_hitlen,
+                               const double* weight, uint32_t ntax, const double* genome_len, uint32_t max_iter, double tol,
+                               double* extra, uint8_t* touched, uint32_t* iterations_run, double* last_change);
+/* The same on the device, over the multimapped CSR of a committed shard (the contract of mg_profile_resolve_multimapped_dev:
+ * d_weight0[t] NaN = no entry, d_genome_len NULL unless --length_normalize, d_extra[ntax] overwritten with the LAST iteration's
+ * additions).  Built once per call: every read's sorted list of distinct taxa that have a weight, and the classes of reads with
+ * the same list (equal lists only: a collision of the 64-bit hash they are sorted by can split a class, never merge two), each
+ * with the exact u64 sum of its reads' hitlen.  An iteration then costs one thread per class.  *nclasses (may be NULL) = the
+ * classes of non-empty lists.  When tol == 0 nothing is read back before the last iteration.  Sums are floating point and
+ * order-dependent: equal to the host routine to a few 1e-15 relative per iteration, not bit for bit.  The call returns with
+ * its work done (it synchronises stage C's stream). */
+int mg_profile_mm_iterate_dev(const mg_profile* p, const double* d_weight0, const double* d_genome_len, uint32_t max_iter,
+                              double tol, double* d_extra, uint32_t* iterations_run, double* last_change, uint64_t* nclasses);
 void mg_profile_free(mg_profile* p);
 
 /* SAM text in HBM -> alignment records (mg_aln_rec), one per retained line, in file order.

@@ -58,6 +58,7 @@ EXPORTS = [
     "mg_refpipe_count_dev", "mg_refdb_marks",
     "mg_profile_begin_dev", "mg_profile_acc_reset", "mg_profile_map_launch", "mg_profile_state_map", "mg_profile_map_words_dev", "mg_profile_ngroups", "mg_profile_commit_dev", "mg_profile_commit_reset_dev",
     "mg_profile_multimapped_size", "mg_profile_multimapped", "mg_profile_resolve_multimapped_dev", "mg_multimapped_shares", "mg_profile_free", "mg_profile_assign",
+    "mg_multimapped_shares_iter", "mg_profile_mm_iterate_dev",
 ]
 
 
@@ -177,6 +178,35 @@ def multimapped_shares(mm_offsets, mm_tax, mm_hitlen, weight, genome_len=None):
     if rc != 0:
         raise HipError("libmetalign_hip rc=%d: %s" % (rc, _host_lib.mg_last_error().decode("utf-8", "replace")), rc)
     return extra, touched.astype(bool)
+
+
+def multimapped_shares_iter(mm_offsets, mm_tax, mm_hitlen, weight, genome_len=None, max_iter=1, tol=0.0):
+    """mg_multimapped_shares_iter: the reassignment iterated (metalign_amd/multimap.py is the definition; host code of the library:
+    no device involved).  -> (extra float64[ntax], touched bool[ntax], iterations_run, last_change), extra the last iteration's."""
+    global _host_lib
+    if _host_lib is None:
+        _host_lib = load_library()
+    off = np.ascontiguousarray(mm_offsets, dtype=np.uint64)
+    tax = np.ascontiguousarray(mm_tax, dtype=np.uint32)
+    hl = np.ascontiguousarray(mm_hitlen, dtype=np.uint64)
+    w = np.ascontiguousarray(weight, dtype=np.float64)
+    gl = np.ascontiguousarray(genome_len, dtype=np.float64) if genome_len is not None else None
+    extra = np.zeros(len(w), dtype=np.float64)
+    touched = np.zeros(len(w), dtype=np.uint8)
+    one = np.zeros(1, dtype=np.uint64)
+    n_run, change = ctypes.c_uint32(0), ctypes.c_double(0.0)
+    if not 1 <= int(max_iter) <= 0xffffffff:
+        raise HipError("max_iter must be at least 1", ERR_ARG)
+    rc = _host_lib.mg_multimapped_shares_iter(_np(off if off.size else one, ctypes.c_uint64), ctypes.c_uint64(len(hl)),
+                                              _np(tax if tax.size else np.zeros(1, np.uint32), ctypes.c_uint32),
+                                              _np(hl if hl.size else one, ctypes.c_uint64), _np(w, ctypes.c_double),
+                                              ctypes.c_uint32(len(w)), _np(gl, ctypes.c_double) if gl is not None else None,
+                                              ctypes.c_uint32(int(max_iter)), ctypes.c_double(float(tol)),
+                                              _np(extra, ctypes.c_double), _np(touched, ctypes.c_uint8), ctypes.byref(n_run),
+                                              ctypes.byref(change))
+    if rc != 0:
+        raise HipError("libmetalign_hip rc=%d: %s" % (rc, _host_lib.mg_last_error().decode("utf-8", "replace")), rc)
+    return extra, touched.astype(bool), int(n_run.value), float(change.value)
 
 
 def hash_mode1_ks():
@@ -924,6 +954,28 @@ class ProfileShard:
             if d_l:
                 d_l.free()
 
+    def iterate_multimapped(self, weight, genome_len=None, max_iter=1, tol=0.0):
+        """mg_profile_mm_iterate_dev: the reassignment iterated over classes of reads on the device.
+        -> (extra[t] of the last iteration (host float64 array), iterations_run, last_change, nclasses)."""
+        hip = self.hip
+        if not 1 <= int(max_iter) <= 0xffffffff:
+            raise HipError("max_iter must be at least 1", ERR_ARG)
+        weight = np.ascontiguousarray(weight, dtype=np.float64)
+        d_w = hip.array(weight)
+        d_l = hip.array(np.ascontiguousarray(genome_len, dtype=np.float64)) if genome_len is not None else None
+        d_x = hip.empty(len(weight), np.float64)
+        n_run, change, ncls = ctypes.c_uint32(0), ctypes.c_double(0.0), ctypes.c_uint64(0)
+        try:
+            hip._chk(hip.lib.mg_profile_mm_iterate_dev(self.handle, _vp(d_w.ptr), _vp(d_l.ptr if d_l else None),
+                                                       ctypes.c_uint32(int(max_iter)), ctypes.c_double(float(tol)), _vp(d_x.ptr),
+                                                       ctypes.byref(n_run), ctypes.byref(change), ctypes.byref(ncls)))
+            return d_x.download(), int(n_run.value), float(change.value), int(ncls.value)
+        finally:
+            d_w.free()
+            d_x.free()
+            if d_l:
+                d_l.free()
+
     def free(self):
         if self.handle:
             self.hip.lib.mg_profile_free(self.handle)
@@ -1066,6 +1118,9 @@ class ResidentProfile:
 
     def resolve_multimapped(self, weight, genome_len=None):
         return self.shard.resolve_multimapped(weight, genome_len)
+
+    def iterate_multimapped(self, weight, genome_len=None, max_iter=1, tol=0.0):
+        return self.shard.iterate_multimapped(weight, genome_len, max_iter, tol)
 
     def free(self):
         if self.shard is not None:

@@ -54,6 +54,11 @@ _OPTIONS = {
                      'genome (G rows) the placed alignments, aligned bases, covered bases, breadth, mean depth and the breadth that '
                      'depth predicts, from the alignments stage C keeps (metalign_amd/coverage.py is the definition). SAM / BAM '
                      'input, one process only.'),
+    'multimap_iterations': dict(type=int, default=1, help='Iterate the reassignment of multimapped reads up to this many times: every '
+                                'iteration shares them in proportion to the bases the one before gave (metalign_amd/multimap.py is '
+                                'the definition). Default 1: the single step, in proportion to uniquely mapped bases.'),
+    'multimap_tol': dict(type=float, default=1e-8, help='Stop iterating once no genome\'s bases change by more than this fraction '
+                         '(default 1e-8, a tenth of the last digit the profile prints); 0 runs all --multimap_iterations.'),
     'device_multimap': dict(action='store_true', help='Resolve multimapped reads on the GPU (their lists never leave '
                             'the device; abundances equal the default path to ~1e-15 relative, not byte for byte).'),
 }
@@ -69,7 +74,8 @@ _TOOLS = {
         options=['cutoff', 'db_dir', 'dbinfo_in', 'keep_temp_files', ('input_type', _READ_TYPES), 'length_normalize',
                  'low_mem', 'min_abundance', 'no_quantify_unmapped', 'output', 'pct_id', 'precise', 'rank_renormalize',
                  'read_cutoff', 'sampleID', 'sensitive', 'strain_level', 'temp_dir', 'threads', 'verbose',
-                 'sketch_table', 'min_count', 'sketch_size', 'kmer_match', 'device_multimap', 'collate', 'read_assignments', 'coverage']),
+                 'sketch_table', 'min_count', 'sketch_size', 'kmer_match', 'device_multimap', 'collate', 'read_assignments', 'coverage',
+                 'multimap_iterations', 'multimap_tol']),
     'select_db': dict(
         description='Run CMash and select a subset of the whole database to align to.',
         positionals=[('reads', dict(help='Reads file (FASTA / FASTQ, optionally .gz, or a BAM of reads).')),
@@ -84,7 +90,8 @@ _TOOLS = {
         options=[('db', 'NONE', 'Database FASTA from select_db (needed unless the inputs are SAM files).'), 'dbinfo',
                  ('input_type', ['fastq', 'fasta', 'sam', 'AUTO']), 'length_normalize', 'low_mem', 'min_abundance',
                  'rank_renormalize', 'output', 'pct_id', 'no_quantify_unmapped', 'read_cutoff', 'sampleID', 'threads',
-                 'verbose', 'device_multimap', 'collate', 'read_assignments', 'coverage']),
+                 'verbose', 'device_multimap', 'collate', 'read_assignments', 'coverage',
+                 'multimap_iterations', 'multimap_tol']),
 }
 
 

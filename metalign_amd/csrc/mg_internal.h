@@ -125,8 +125,16 @@ inline uint32_t stage_a_cs_word() {
 void* pool_alloc(uint64_t bytes, uint64_t* got);
 void pool_free(void* p, uint64_t bytes);
 void pool_release_all();
-// Pinned host words for small read-backs (index < 64).
+// Pinned host words for small read-backs (index < 64).  Who owns which (a new user takes free words and adds itself here):
+//   [0, 16)   the sort and scan services and the passes of mg_sketch, mg_refpipe, mg_contain and mg_ingest; each synchronises
+//             and reads its words before it returns
+//   [16, 20)  stage C's pass totals (mg_profile.hip: fetch_map, fetch_mm)
+//   20        mg_contain.hip: the pair bound of a query that counts sizes
+//   [24, 26)  the multimapped iteration (mg_multimap.hip): kHostWordMmChange, kHostWordMmLastLen
+//   [40, 44)  mg_bam.hip: the words that ride on a scan's synchronisation
 uint64_t* host_words();
+constexpr unsigned kHostWordMmChange = 24;   // change_i, a double
+constexpr unsigned kHostWordMmLastLen = 25;  // the last class's list length, a uint32_t
 
 // RAII device buffer on the library stream's device.
 struct DevBuf {
@@ -198,6 +206,11 @@ inline unsigned grid_cap(unsigned grid, const char* key) {
   const int64_t v = dbg(key);
   return v > 0 && (uint64_t)v < grid ? (unsigned)v : grid;
 }
+
+// mg_multimap.hip: the iterated multimapped-read reassignment over a multimapped CSR in device memory (mg_profile_mm_iterate_dev).
+int mm_iterate_dev(const uint64_t* mm_offsets, const uint32_t* mm_tax, const uint64_t* mm_hitlen, uint64_t nreads, uint64_t nent,
+                   uint32_t ntax, const double* d_weight0, const double* d_genome_len, uint32_t max_iter, double tol,
+                   double* d_extra, uint32_t* iterations_run, double* last_change, uint64_t* nclasses);
 
 // ---- internal services implemented in mg_sort.hip (rocPRIM-backed plain library ops) ----
 // Sorts n u64 keys ascending using bits [0,end_bit). out may not alias in.

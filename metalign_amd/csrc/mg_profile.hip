@@ -1560,6 +1560,19 @@ int mg_profile_resolve_multimapped_dev(const mg_profile* p, const double* d_weig
   return MG_OK;
 }
 
+int mg_profile_mm_iterate_dev(const mg_profile* p, const double* d_weight0, const double* d_genome_len, uint32_t max_iter,
+                              double tol, double* d_extra, uint32_t* iterations_run, double* last_change, uint64_t* nclasses) {
+  MG_REQUIRE_READY();
+  if (!p || !d_weight0 || !d_extra || !iterations_run || !last_change) return fail(MG_ERR_ARG, "null argument");
+  if (max_iter < 1) return fail(MG_ERR_ARG, "max_iter must be at least 1");
+  if (!(tol >= 0.0)) return fail(MG_ERR_ARG, "tol must not be negative");
+  if (!p->committed) return fail(MG_ERR_STATE, "profile shard not committed");
+  MG_TRY(fetch_mm(const_cast<mg_profile*>(p)));
+  return mm_iterate_dev(p->mm_offsets.as<uint64_t>(), p->mm_tax.as<uint32_t>(), p->mm_hitlen.as<uint64_t>(), p->mm_nreads,
+                        p->mm_nentries, p->ntax, d_weight0, d_genome_len, max_iter, tol, d_extra, iterations_run, last_change,
+                        nclasses);
+}
+
 int mg_profile_multimapped_size(const mg_profile* p, uint64_t* nreads, uint64_t* nentries) {
   if (!p) return fail(MG_ERR_ARG, "null profile");
   MG_REQUIRE_READY();

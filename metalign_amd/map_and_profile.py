@@ -939,7 +939,13 @@ def resolve_multi_prop_csr(args, taxids2abs, mm, taxid2info):
     for taxid, row in taxids2abs.items():
         weight[index[taxid]] = row[1]
     glen = np.array([taxid2info[x][0] for x in taxids], dtype=np.float64) if args.length_normalize else None
-    extra, touched = _hip.multimapped_shares(mm['mm_offsets'], mm['mm_tax'], mm['mm_hitlen'], weight, glen)
+    n_iter = _multimap_iterations(args)
+    if n_iter > 1:  # (--multimap_iterations; 1 is the call below, as ever)
+        extra, touched, ran, last = _hip.multimapped_shares_iter(mm['mm_offsets'], mm['mm_tax'], mm['mm_hitlen'], weight, glen,
+                                                                 n_iter, float(getattr(args, 'multimap_tol', 1e-8)))
+        echo('Multimapped reads reassigned in %d iteration(s); last relative change %.3g' % (ran, last), args.verbose)
+    else:
+        extra, touched = _hip.multimapped_shares(mm['mm_offsets'], mm['mm_tax'], mm['mm_hitlen'], weight, glen)
     for i in np.nonzero(touched)[0]:
         taxids2abs[taxids[int(i)]][1] += float(extra[i])
     return taxids2abs
@@ -987,7 +993,13 @@ def resolve_multi_prop_device(args, taxids2abs, mm, taxid2info):
     for taxid, row in taxids2abs.items():
         weight[index[taxid]] = row[1]
     glen = np.array([taxid2info[x][0] for x in taxids], dtype=np.float64) if args.length_normalize else None
-    extra = mm['resident'].resolve_multimapped(weight, glen)
+    n_iter = _multimap_iterations(args)
+    if n_iter > 1:  # (--multimap_iterations: over classes of reads with the same taxa; 1 is the call below, as ever)
+        extra, ran, last, ncls = mm['resident'].iterate_multimapped(weight, glen, n_iter, float(getattr(args, 'multimap_tol', 1e-8)))
+        echo('Multimapped reads reassigned in %d iteration(s) over %d classes of %d reads; last relative change %.3g'
+             % (ran, ncls, mm['mm_nreads'], last), args.verbose)
+    else:
+        extra = mm['resident'].resolve_multimapped(weight, glen)
     for i in np.nonzero(extra)[0]:
         taxids2abs[taxids[int(i)]][1] += float(extra[i])
     return taxids2abs
@@ -1248,6 +1260,21 @@ def write_results(args, rank_results):
                 out.write('\t'.join(str(x) for x in row) + '\n')
 
 
+def _multimap_iterations(args):
+    return int(getattr(args, 'multimap_iterations', 1))  # (callers build Namespaces without it)
+
+
+def check_multimap_flags(args):
+    """--multimap_iterations / --multimap_tol: refused before any input is read."""
+    n, tol = _multimap_iterations(args), float(getattr(args, 'multimap_tol', 1e-8))
+    if n < 1:
+        sys.exit('Error: --multimap_iterations must be at least 1.')
+    if not tol >= 0.0:
+        sys.exit('Error: --multimap_tol must not be negative.')
+    if n > 1 and args.low_mem:
+        sys.exit('Error: --multimap_iterations above 1 cannot be combined with --low_mem, which keeps no multimapped lists to iterate over.')
+
+
 def map_main(args=None):
     if args is None:
         args = profile_parseargs()
@@ -1262,6 +1289,7 @@ def map_main(args=None):
         sys.exit('Error: --coverage runs in one process on one GPU; start it without torch.distributed.run.')
     if _wants_coverage(args) and (getattr(args, 'paf_input', False) or any(f.endswith('.paf') for f in args.infiles)):
         sys.exit('Error: --coverage needs SAM or BAM alignments: a PAF line has no POS and CIGAR columns.')
+    check_multimap_flags(args)
     args.data = cli.with_slash(args.data)
     if args.dbinfo == 'AUTO':
         args.dbinfo = args.data + 'db_info.txt'

@@ -57,6 +57,7 @@ def main(argv=None):
         sys.exit('Error: --read_assignments runs in one process on one GPU; start it without torch.distributed.run.')
     if args.coverage != 'NONE' and int(os.environ.get('WORLD_SIZE', '1')) > 1:
         sys.exit('Error: --coverage runs in one process on one GPU; start it without torch.distributed.run.')
+    mapper.check_multimap_flags(args)
     args.data = cli.with_slash(args.data)
     own_temp = args.temp_dir == 'AUTO/'  # a directory of this process's own making (one per rank in a multi-GPU launch)
     if own_temp:
