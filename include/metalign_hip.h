@@ -94,7 +94,7 @@ int mg_device_count(void);
  *   return their batch keyed and not yet collated); genome_slab_bytes (mg_genomes_stream_open: the size of a page-locked slab,
  *   default 8 MiB, at least 4 KiB), genome_guard (test hook: mg_genomes_parse_dev fills the 16 bytes behind its bases and the
  *   word behind its offsets with 0xa5 before its kernels run); cov_grid (test hook, k3_grid's meaning for k_cov_add /
- *   k_cov_count, mg_coverage.hip); mm_hash_bits (test hook, mg_profile_mm_iterate_dev: only this many low bits of a list's hash
+ *   k_cov_count, mg_coverage.hip); depth_grid (test hook, the same for every grid of mg_depth.hip); mm_hash_bits (test hook, mg_profile_mm_iterate_dev: only this many low bits of a list's hash
  *   are kept, so that different lists collide).
  * Needs no device and no mg_init.  MG_ERR_ARG for a key that does not exist. */
 int mg_debug_set(const char* key, int64_t value);
@@ -970,6 +970,33 @@ int mg_coverage_create(const uint64_t* lengths, uint32_t nacc, mg_coverage** out
 int mg_coverage_add_dev(mg_coverage* c, const mg_aln_rec* d_recs, const mg_aln_place* d_place, uint64_t n, double pct_id);
 int mg_coverage_result(mg_coverage* c, uint64_t* alignments, uint64_t* aligned_bases, uint64_t* covered_bases, uint64_t* unplaced);
 void mg_coverage_free(mg_coverage* c);
+
+/* PER-BASE DEPTH OF COVERAGE (--depth, --depth_windows; metalign_amd/csrc/mg_depth.hip; the definition is metalign_amd/depth.py).
+ * create: one int32 slot per reference base plus one per accession, zeroed, accession a at a slot offset held in 64 bits; window
+ *   = W, the width of the windows (0: none are kept; otherwise a u64 and a u32 per window as well).  nacc = 0 and lengths of 0
+ *   are legal.  MG_ERR_NOMEM (the byte count in the message) when the slots do not fit.
+ * add_dev: every counting record (clean_read_hits' rule, as mg_coverage_add_dev) with a place inside its accession adds +1 at the
+ *   first slot of its clipped interval and -1 behind its last; a counting record without one (span 0, pos0 >= length, accession
+ *   row >= nacc) is one more unplaced.  Asynchronous on the library stream; several calls sum.  MG_ERR_STATE after finish.
+ * finish: downloads the alignments (u64[nacc]) and *unplaced, gives every accession with an alignment a histogram row, scans the
+ *   slots (tile sums, their scan by one workgroup, then a second read of the slots), fills the rows and the windows, and keeps
+ *   the windows with depth_sum > 0.  *nrows, *nwindows: what the two fetches give.  Synchronises; frees the slots.  Once.
+ * fetch_rows: accessions[nrows] (ascending) and hist[nrows * 4096]: hist[r * 4096 + c] = the positions of accessions[r] whose
+ *   depth, clamped to 4095, is c.  An accession without a row has depth 0 everywhere.  Once, after finish (else MG_ERR_STATE).
+ * fetch_windows: the kept windows ordered by (accession, index); depth_sum is NOT clamped.  Once, after finish. */
+typedef struct mg_depth mg_depth;
+typedef struct mg_depth_window {
+  uint64_t index;     /* window [index W, min((index + 1) W, length)) */
+  uint64_t depth_sum; /* the sum of depth[p] over the window */
+  uint32_t acc;       /* accession row */
+  uint32_t covered;   /* positions with depth > 0 */
+} mg_depth_window;
+int mg_depth_create(const uint64_t* lengths, uint32_t nacc, uint32_t window, mg_depth** out);
+int mg_depth_add_dev(mg_depth* d, const mg_aln_rec* d_recs, const mg_aln_place* d_place, uint64_t n, double pct_id);
+int mg_depth_finish(mg_depth* d, uint64_t* alignments, uint64_t* unplaced, uint64_t* nrows, uint64_t* nwindows);
+int mg_depth_fetch_rows(mg_depth* d, uint32_t* accessions, uint64_t* hist);
+int mg_depth_fetch_windows(mg_depth* d, mg_depth_window* windows);
+void mg_depth_free(mg_depth* d);
 
 /* Host-buffer convenience, single shard = whole stream. Capacities: mm_* as
  * above with mm_cap_reads / mm_cap_entries entries available. */

@@ -49,6 +49,7 @@ EXPORTS = [
     "mg_sam_tokenize_dev_ex", "mg_sam_tokenize_ex", "mg_bam_tokenize_dev_ex", "mg_sam_stream_file_ex", "mg_bam_stream_file_ex",
     "mg_sam_batch_places_download", "mg_sam_batch_places_device_ptr",
     "mg_coverage_create", "mg_coverage_add_dev", "mg_coverage_result", "mg_coverage_free",
+    "mg_depth_create", "mg_depth_add_dev", "mg_depth_finish", "mg_depth_fetch_rows", "mg_depth_fetch_windows", "mg_depth_free",
     "mg_gunzip_open", "mg_gunzip_read", "mg_gunzip_close", "mg_zcat_files", "mg_stream_thin_file",
     "mg_inflate_dev", "mg_inflated_bytes", "mg_inflated_download", "mg_inflated_free", "mg_inflate_config", "mg_inflate_stats",
     "mg_sketch_genomes", "mg_sketch_genomes_prefix", "mg_db_upload", "mg_db_upload_sorted", "mg_db_ngenomes", "mg_db_max_hash", "mg_db_free",
@@ -78,6 +79,9 @@ ERR_HIP, ERR_ARG, ERR_CAPACITY, ERR_STATE, ERR_NOMEM = -1, -2, -3, -4, -5
 # what a batch carries beside its records (include/metalign_hip.h: MG_BATCH_*), and a record's place (mg_aln_place)
 BATCH_KEYS, BATCH_NAMES, BATCH_PLACES, BATCH_COLLATE = 1, 2, 4, 8
 PLACE_DTYPE = np.dtype([("pos0", np.uint32), ("span", np.uint32)])
+# a kept window of a Depth (mg_depth_window) and the histogram's bins (depth clamped to DEPTH_BINS - 1)
+DEPTH_WINDOW_DTYPE = np.dtype([("index", np.uint64), ("depth_sum", np.uint64), ("acc", np.uint32), ("covered", np.uint32)])
+DEPTH_BINS = 4096
 
 
 def _want(keyed=False, named=False, placed=False, collate=False):
@@ -129,6 +133,7 @@ def load_library(path=LIB_PATH):
     lib.mg_kcounts_free.restype = None
     lib.mg_profile_free.restype = None
     lib.mg_coverage_free.restype = None
+    lib.mg_depth_free.restype = None
     lib.mg_shutdown.restype = None
     return lib
 
@@ -1110,6 +1115,90 @@ class Coverage:
             self.handle = None
 
 
+class Depth:
+    """One int32 slot per reference base (and one per accession) on the device: per-base depth as a histogram per accession and as
+    windows of `window` bases (mg_depth_*; metalign_amd/depth.py is the definition).  lengths: one per accession row; window = 0:
+    no windows.  HipError with code ERR_NOMEM when the slots do not fit, ERR_STATE for an add after finish()."""
+
+    def __init__(self, hip, lengths, window=0):
+        self.hip = hip
+        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
+        self.nacc, self.window = int(ln.size), int(window)
+        h = _vp()
+        hip._chk(hip.lib.mg_depth_create(_np(ln if ln.size else np.zeros(1, np.uint64), ctypes.c_uint64), ctypes.c_uint32(self.nacc),
+                                         ctypes.c_uint32(self.window), ctypes.byref(h)))
+        self.handle = h
+
+    def add_ptr(self, d_recs, d_places, n, pct_id):
+        """n records and their places at device pointers (asynchronous; the arrays must outlive the next synchronisation)."""
+        self.hip._chk(self.hip.lib.mg_depth_add_dev(self.handle, _vp(d_recs), _vp(d_places), ctypes.c_uint64(int(n)),
+                                                    ctypes.c_double(float(pct_id))))
+
+    def add_batch(self, batch, pct_id):
+        """A placed SamBatch."""
+        if batch.count:
+            self.add_ptr(batch.ptr, batch.places_ptr, batch.count, pct_id)
+            self.hip.sync()
+
+    def add(self, recs, places, pct_id):
+        """Host arrays REC_DTYPE[n], PLACE_DTYPE[n]."""
+        recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
+        places = np.ascontiguousarray(places, dtype=PLACE_DTYPE)
+        assert len(recs) == len(places)
+        if not len(recs):
+            self.add_ptr(None, None, 0, pct_id)  # (ERR_STATE after finish, whatever the count)
+            return
+        d_r, d_p = self.hip.array(recs.view(np.uint8)), self.hip.array(places.view(np.uint8))
+        try:
+            self.add_ptr(d_r.ptr, d_p.ptr, len(recs), pct_id)
+            self.hip.sync()
+        finally:
+            d_r.free()
+            d_p.free()
+
+    def finish(self):
+        """The scan and the histogram / window passes (mg_depth_finish) -> (alignments uint64[nacc], unplaced, nrows, nwindows)."""
+        aln = np.zeros(max(self.nacc, 1), dtype=np.uint64)
+        unplaced, nrows, nwin = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.hip._chk(self.hip.lib.mg_depth_finish(self.handle, _np(aln, ctypes.c_uint64), ctypes.byref(unplaced), ctypes.byref(nrows),
+                                                   ctypes.byref(nwin)))
+        self.nrows, self.nwindows = int(nrows.value), int(nwin.value)
+        return aln[:self.nacc], int(unplaced.value), self.nrows, self.nwindows
+
+    def fetch_rows(self):
+        """-> (accession rows uint32[nrows], histograms uint64[nrows, DEPTH_BINS]); once."""
+        acc = np.zeros(self.nrows + 1, dtype=np.uint32)
+        hist = np.zeros(self.nrows * DEPTH_BINS + 1, dtype=np.uint64)
+        self.hip._chk(self.hip.lib.mg_depth_fetch_rows(self.handle, _np(acc, ctypes.c_uint32), _np(hist, ctypes.c_uint64)))
+        return acc[:self.nrows], hist[:self.nrows * DEPTH_BINS].reshape(self.nrows, DEPTH_BINS)
+
+    def fetch_windows(self):
+        """-> DEPTH_WINDOW_DTYPE[nwindows], ordered by (accession row, index); once."""
+        win = np.zeros(self.nwindows + 1, dtype=DEPTH_WINDOW_DTYPE)
+        self.hip._chk(self.hip.lib.mg_depth_fetch_windows(self.handle, _vp(win.ctypes.data)))
+        return win[:self.nwindows]
+
+    def result(self):
+        """finish() and both fetches -> (alignments, unplaced, {accession row: {clamped depth: positions}},
+        {accession row: [(index, depth_sum, covered)]})."""
+        aln, unplaced, _, _ = self.finish()
+        acc, hist = self.fetch_rows()
+        win = self.fetch_windows()
+        per = {}
+        for r, a in enumerate(acc):
+            nz = np.flatnonzero(hist[r])
+            per[int(a)] = {int(c): int(hist[r, c]) for c in nz}
+        windows = {}
+        for a, j, s, c in zip(win["acc"].tolist(), win["index"].tolist(), win["depth_sum"].tolist(), win["covered"].tolist()):
+            windows.setdefault(a, []).append((j, s, c))
+        return aln, unplaced, per, windows
+
+    def free(self):
+        if self.handle:
+            self.hip.lib.mg_depth_free(self.handle)
+            self.handle = None
+
+
 class ResidentProfile:
     """A committed stage-C shard kept on the device together with the buffers it reads (multimapped CSR included)."""
 
@@ -1205,6 +1294,10 @@ class Hip:
     def coverage(self, lengths):
         """A Coverage over accessions of these lengths (mg_coverage_create)."""
         return Coverage(self, lengths)
+
+    def depth(self, lengths, window=0):
+        """A Depth over accessions of these lengths, with windows of `window` bases (mg_depth_create)."""
+        return Depth(self, lengths, window)
 
     def array(self, host, dtype=None):
         host = np.ascontiguousarray(host, dtype=dtype)

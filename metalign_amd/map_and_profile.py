@@ -29,7 +29,7 @@ import time
 
 import numpy as np
 
-from . import _hip, assignments, bam, cli, collate, coverage
+from . import _hip, assignments, bam, cli, collate, coverage, depth
 
 start = time.time()
 RANKS = ['superkingdom', 'phylum', 'class', 'order', 'family', 'genus', 'species', 'strain']
@@ -488,6 +488,62 @@ def _coverage_close(args, path, lengths, dev, acc_index, acc2info, taxid2info):
     _append_coverage(args, path, coverage.Coverage(lengths, per, unplaced), acc2info, taxid2info)
 
 
+def _wanted(args, name):
+    return getattr(args, name, 'NONE') not in (None, 'NONE')  # (callers build Namespaces without it)
+
+
+def _wants_depth(args):
+    """--depth or --depth_windows: either one asks for the per-base depth."""
+    return _wanted(args, 'depth') or _wanted(args, 'depth_windows')
+
+
+def _depth_window(args):
+    return int(getattr(args, 'depth_window_size', 1000)) if _wanted(args, 'depth_windows') else 0
+
+
+def _depth_bytes(lengths, window, nrec):
+    """What a Depth holds on the device: 4 B per reference base and accession, 12 B per window, a 32 KB histogram row per
+    accession that is hit (at most one per record)."""
+    total, nacc = sum(lengths.values()), len(lengths)
+    nwin = sum((n + window - 1) // window for n in lengths.values()) if window else 0
+    return 4 * (total + nacc) + 12 * nwin + 8 * _hip.DEPTH_BINS * min(nacc, nrec)
+
+
+def _depth_open(args, hip, lengths, acc_index):
+    """--depth / --depth_windows for one input file: the device's slots over its lengths (those of --coverage)."""
+    arr = np.zeros(len(acc_index), dtype=np.uint64)
+    for a, i in acc_index.items():
+        arr[i] = lengths[a]
+    try:
+        return hip.depth(arr, _depth_window(args))
+    except _hip.HipError as e:
+        if e.code != _hip.ERR_NOMEM:
+            raise
+        sys.exit('Error: --depth keeps four bytes per reference base on the GPU; %d MB for this database do not fit.'
+                 % (_depth_bytes(lengths, _depth_window(args), 0) >> 20))
+
+
+def _append_depth(args, path, dep, acc2info, taxid2info):
+    """One input file's blocks behind those of the files before it (map_main wrote the column headers)."""
+    source = path if len(getattr(args, 'infiles', [])) > 1 else None
+    if _wanted(args, 'depth'):
+        depth.write_depth(args.depth, depth.rows(dep, acc2info, taxid2info), dep.unplaced, source=source, append=True)
+    if _wanted(args, 'depth_windows'):
+        depth.write_windows(args.depth_windows, depth.window_rows(dep, acc2info), source=source, append=True)
+
+
+def _depth_close(args, path, lengths, dev, acc_index, acc2info, taxid2info):
+    """The device's histogram rows and windows -> the file's blocks."""
+    try:
+        aln, unplaced, hist, win = dev.result()
+    finally:
+        dev.free()
+    names = {i: a for a, i in acc_index.items()}
+    per = {names[r]: [int(aln[r]), H] for r, H in hist.items()}
+    windows = {names[r]: w for r, w in win.items()}
+    _append_depth(args, path, depth.Depth(lengths, per, unplaced, dev.window, windows), acc2info, taxid2info)
+
+
 def assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=True):
     """Kernel outputs -> the (taxids2abs, multimapped, low_mem_mmap) triple of the reference (:193-264).
     want_lists=False leaves `multimapped` as the CSR dict for the vectorised tail (compute_abundances)."""
@@ -518,7 +574,7 @@ def assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=True):
 
 
 def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _resident=False, _paf=False, _bam=False, _collate=False,
-                         _assignments=False, _coverage=None):
+                         _assignments=False, _coverage=None, _depth=None):
     """map_and_process for a plain SAM FILE, without the text or the records ever being host arrays: the file goes up
     through page-locked chunks (Hip.upload_file), is tokenised where it lands and stage C runs on the records the
     tokeniser left in HBM.  A line the reference cannot parse makes this return None: the caller then takes the
@@ -529,9 +585,11 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
     _assignments (--read_assignments): the tokeniser also keeps the reads' names, stage C also writes every read's verdict and the rows
     are appended to args.read_assignments; never together with _collate (a named batch is not collated).
     _coverage (--coverage): the file's header lines — the batch also carries the records' places, which feed the coverage bitmap
-    before stage C takes the batch, and the file's block is appended to args.coverage."""
+    before stage C takes the batch, and the file's block is appended to args.coverage.
+    _depth (--depth, --depth_windows): the file's header lines likewise — the same placed batch feeds the depth slots, and the
+    file's blocks are appended to args.depth / args.depth_windows."""
     assert not (_assignments and _collate)
-    placed = _coverage is not None
+    placed = _coverage is not None or _depth is not None
     acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
     _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
     hip = _hip.Hip.get()
@@ -539,7 +597,7 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
     for a, i in acc_index.items():
         names[i] = a
     index = hip.acc_index(names)
-    d_text = batch = cov_lengths = cov_dev = None
+    d_text = batch = cov_lengths = cov_dev = dep_dev = None
     try:
         # the text plus ~60 B per line of line index and tokeniser output must fit beside what is resident already:
         # otherwise straight to the streaming path (256 MB chunks), without first filling the device and failing
@@ -559,9 +617,13 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
             need += 64 * (os.path.getsize(path) // (50 if _bam or _is_gzip(path) else 100))
         if placed:
             # 8 B of place per record (and as much again where a collation permutes them) and one bit per reference base
-            need += 16 * (os.path.getsize(path) // (50 if _bam or _is_gzip(path) else 100))
-            cov_lengths = coverage.lengths_of(_coverage, acc2info)
-            need += sum(cov_lengths.values()) // 8
+            nrec = os.path.getsize(path) // (50 if _bam or _is_gzip(path) else 100)
+            need += 16 * nrec
+            cov_lengths = coverage.lengths_of(_coverage if _coverage is not None else _depth, acc2info)
+            if _coverage is not None:
+                need += sum(cov_lengths.values()) // 8
+            if _depth is not None:  # 4 B per reference base, the histogram rows and the windows
+                need += _depth_bytes(cov_lengths, _depth_window(args), nrec)
         if need > free + pooled:
             return None
         try:
@@ -595,22 +657,29 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
         finally:
             if d_text is not None:
                 d_text.free()
-        if placed:  # (before stage C takes the batch over)
+        if _coverage is not None:  # (before stage C takes the batch over)
             cov_dev = _coverage_open(hip, cov_lengths, acc_index)
             cov_dev.add_batch(batch, float(args.pct_id))
+        if _depth is not None:
+            dep_dev = _depth_open(args, hip, cov_lengths, acc_index)
+            dep_dev.add_batch(batch, float(args.pct_id))
         res = hip.profile_assign_dev_records(batch.ptr, batch.count, ref2tax, len(taxids), float(args.pct_id), [batch],
                                              resident=_resident, assign=_assignments)
         batch = None  # owned by the result now
     except BaseException:
         if cov_dev is not None:
             cov_dev.free()
+        if dep_dev is not None:
+            dep_dev.free()
         raise
     finally:
         index.free()
         if batch is not None:
             batch.free()
-    if placed:
+    if cov_dev is not None:
         _coverage_close(args, path, cov_lengths, cov_dev, acc_index, acc2info, taxid2info)
+    if dep_dev is not None:
+        _depth_close(args, path, cov_lengths, dep_dev, acc_index, acc2info, taxid2info)
     if _assignments:
         _append_assignments(args, assignment_rows(res, taxids))
     if not _want_lists:
@@ -803,17 +872,18 @@ class _CudaWords:
 
 
 def map_and_process(args, instream, acc2info, taxid2info, _assign=None, _want_lists=True, _resident=False, _assignments=False,
-                    _coverage=None):
+                    _coverage=None, _depth=None):
     """Reference signature (:193).  `_assign` is a test seam; product code never passes it.
     _assignments (--read_assignments): every chunk's read names are collected beside its records, stage C runs over the records
     uploaded as one array with the verdict words written, and the rows are appended to args.read_assignments.
     _coverage (--coverage): the name the block is written under — every chunk's places are collected beside its records, the
-    lengths come from the leading '@' lines of the stream, and places and records go up together for the coverage kernels."""
+    lengths come from the leading '@' lines of the stream, and places and records go up together for the coverage kernels.
+    _depth (--depth, --depth_windows): the name its blocks are written under, likewise — the same places feed the depth kernels."""
     acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
-    if _coverage is not None:
+    if _coverage is not None or _depth is not None:
         if _assign is not None:
-            raise ValueError('--coverage needs the device path')
-        return _map_and_process_covered(args, instream, acc2info, taxid2info, _want_lists, _resident, _assignments, _coverage)
+            raise ValueError('--coverage and --depth need the device path')
+        return _map_and_process_covered(args, instream, acc2info, taxid2info, _want_lists, _resident, _assignments, _coverage, _depth)
     _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
     # test seam: an injected record-level backend is fed by the host tokeniser; product code never passes one
     tokenise = _device_tokenise if _assign is None else tokenise_sam
@@ -841,8 +911,9 @@ def map_and_process(args, instream, acc2info, taxid2info, _assign=None, _want_li
     return assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=_want_lists)
 
 
-def _map_and_process_covered(args, instream, acc2info, taxid2info, _want_lists, _resident, _assignments, source):
-    """map_and_process with --coverage (and --read_assignments where that is on)."""
+def _map_and_process_covered(args, instream, acc2info, taxid2info, _want_lists, _resident, _assignments, source, depth_source=None):
+    """map_and_process with --coverage (source) and / or --depth, --depth_windows (depth_source), and --read_assignments where that
+    is on."""
     acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
     _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
     names, places, header = ([] if _assignments else None), [], []
@@ -853,19 +924,28 @@ def _map_and_process_covered(args, instream, acc2info, taxid2info, _want_lists, 
     d_recs = hip.array(recs if len(recs) else np.zeros(1, _hip.REC_DTYPE))
     try:
         lengths = coverage.lengths_of(header, acc2info)
-        dev = _coverage_open(hip, lengths, acc_index)
+        devs = []
         try:
+            if source is not None:
+                devs.append(_coverage_open(hip, lengths, acc_index))
+            if depth_source is not None:
+                devs.append(_depth_open(args, hip, lengths, acc_index))
             if len(recs):
                 d_place = hip.array(place.view(np.uint8))
                 try:
-                    dev.add_ptr(d_recs.ptr, d_place.ptr, len(recs), float(args.pct_id))
+                    for dev in devs:
+                        dev.add_ptr(d_recs.ptr, d_place.ptr, len(recs), float(args.pct_id))
                     hip.sync()
                 finally:
                     d_place.free()
         except BaseException:
-            dev.free()
+            for dev in devs:
+                dev.free()
             raise
-        _coverage_close(args, source, lengths, dev, acc_index, acc2info, taxid2info)
+        if source is not None:
+            _coverage_close(args, source, lengths, devs[0], acc_index, acc2info, taxid2info)
+        if depth_source is not None:  # (should the first close raise, this handle goes with the process)
+            _depth_close(args, depth_source, lengths, devs[-1], acc_index, acc2info, taxid2info)
     except BaseException:
         d_recs.free()  # (stage C has not taken the records over yet)
         raise
@@ -1075,15 +1155,18 @@ def compute_abundances(args, infile, acc2info, tax2info):
     paf = bool(getattr(args, 'paf_input', False))
     want_rows = _wants_assignments(args)
     want_cov = _wants_coverage(args)
+    want_dep = _wants_depth(args)
     if want_cov and not seams_untouched:
         raise ValueError('--coverage needs the device path')
+    if want_dep and not seams_untouched:
+        raise ValueError('--depth needs the device path')
     if args.input_type == 'sam' and not paf and bam.is_bam(infile):  # decided per file: a BAM is never SAM text
         instream.close()
         return _compute_abundances_bam(args, infile, acc2info, tax2info, on_device, seams_untouched)
     if args.input_type == 'sam' and not paf and _wants_collation(args, lambda: _sam_header_lines(infile)):
         instream.close()
         return _compute_abundances_collated(args, infile, acc2info, tax2info, on_device, seams_untouched)
-    if args.input_type == 'sam' and seams_untouched and not paf and not want_rows and not want_cov:
+    if args.input_type == 'sam' and seams_untouched and not paf and not want_rows and not want_cov and not want_dep:
         from .select_db import dist_context
         ctx = dist_context()
         if ctx is not None:  # one process per GPU: the ranks tokenise the text between them, rank 0 does the rest
@@ -1095,10 +1178,12 @@ def compute_abundances(args, infile, acc2info, tax2info):
     if args.input_type == 'sam' and seams_untouched and done is None:
         # a plain file (SAM, or a PAF replay): all the way on the device
         done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _paf=paf,
-                                    _assignments=want_rows, _coverage=_sam_header_lines(infile) if want_cov else None)
+                                    _assignments=want_rows, _coverage=_sam_header_lines(infile) if want_cov else None,
+                                    _depth=_sam_header_lines(infile) if want_dep else None)
     if done is None:
         done = map_and_process(args, instream, acc2info, tax2info, _want_lists=False, _resident=on_device,
-                               _assignments=want_rows and seams_untouched, _coverage=infile if want_cov else None)
+                               _assignments=want_rows and seams_untouched, _coverage=infile if want_cov else None,
+                               _depth=infile if want_dep else None)
     taxids2abs, mm, low_mem_mmap = done
     if args.input_type == 'sam':
         instream.close()
@@ -1152,14 +1237,18 @@ def _compute_abundances_collated(args, infile, acc2info, tax2info, on_device, se
         return None
     done = None
     want_cov = _wants_coverage(args) and seams_untouched
+    want_dep = _wants_depth(args) and seams_untouched
     if seams_untouched:
         done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _collate=True,
-                                    _coverage=_sam_header_lines(infile) if want_cov else None)
+                                    _coverage=_sam_header_lines(infile) if want_cov else None,
+                                    _depth=_sam_header_lines(infile) if want_dep else None)
     if done is None:
         done = map_and_process(args, collate.collated_lines(_sam_file_lines(infile)), acc2info, tax2info, _want_lists=False,
                                _resident=on_device)
         if want_cov:  # (the definition over the file's lines: coverage does not depend on their order)
             _append_coverage(args, infile, coverage.coverage(_sam_file_lines(infile), acc2info, args.pct_id), acc2info, tax2info)
+        if want_dep:  # (likewise)
+            _append_depth(args, infile, depth.depth(_sam_file_lines(infile), acc2info, args.pct_id, _depth_window(args)), acc2info, tax2info)
     if _wants_assignments(args):  # (a named batch is not collated: the rows of a collated input come from the definition)
         _append_assignments(args, assignments.read_assignments(collate.collated_lines(_sam_file_lines(infile)), acc2info, args.pct_id))
     taxids2abs, mm, _ = done
@@ -1177,18 +1266,23 @@ def _compute_abundances_bam(args, infile, acc2info, tax2info, on_device, seams_u
     done = None
     want_rows = _wants_assignments(args)
     want_cov = _wants_coverage(args) and seams_untouched
+    want_dep = _wants_depth(args) and seams_untouched
     if seams_untouched:
         # (the reference list's l_ref equals the header's @SQ text: the text is what gives the lengths)
         done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _bam=True,
                                     _collate=collating, _assignments=want_rows and not collating,
-                                    _coverage=_bam_header_lines(infile) if want_cov else None)
+                                    _coverage=_bam_header_lines(infile) if want_cov else None,
+                                    _depth=_bam_header_lines(infile) if want_dep else None)
     if done is None:
         lines = bam.sam_lines(infile)
         done = map_and_process(args, collate.collated_lines(lines) if collating else lines, acc2info, tax2info, _want_lists=False,
                                _resident=on_device, _assignments=want_rows and not collating and seams_untouched,
-                               _coverage=infile if want_cov and not collating else None)
+                               _coverage=infile if want_cov and not collating else None,
+                               _depth=infile if want_dep and not collating else None)
         if want_cov and collating:
             _append_coverage(args, infile, coverage.coverage(bam.sam_lines(infile), acc2info, args.pct_id), acc2info, tax2info)
+        if want_dep and collating:
+            _append_depth(args, infile, depth.depth(bam.sam_lines(infile), acc2info, args.pct_id, _depth_window(args)), acc2info, tax2info)
     if want_rows and collating:  # (as a collated SAM file: the definition over the regrouped lines)
         _append_assignments(args, assignments.read_assignments(collate.collated_lines(bam.sam_lines(infile)), acc2info, args.pct_id))
     taxids2abs, mm, _ = done
@@ -1289,6 +1383,12 @@ def map_main(args=None):
         sys.exit('Error: --coverage runs in one process on one GPU; start it without torch.distributed.run.')
     if _wants_coverage(args) and (getattr(args, 'paf_input', False) or any(f.endswith('.paf') for f in args.infiles)):
         sys.exit('Error: --coverage needs SAM or BAM alignments: a PAF line has no POS and CIGAR columns.')
+    if _wants_depth(args) and int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        sys.exit('Error: --depth and --depth_windows run in one process on one GPU; start it without torch.distributed.run.')
+    if _wants_depth(args) and (getattr(args, 'paf_input', False) or any(f.endswith('.paf') for f in args.infiles)):
+        sys.exit('Error: --depth and --depth_windows need SAM or BAM alignments: a PAF line has no POS and CIGAR columns.')
+    if int(getattr(args, 'depth_window_size', 1000)) < 1:
+        sys.exit('Error: --depth_window_size must be at least 1.')
     check_multimap_flags(args)
     args.data = cli.with_slash(args.data)
     if args.dbinfo == 'AUTO':
@@ -1311,6 +1411,10 @@ def map_main(args=None):
             assignments.write_assignments(args.read_assignments, [])  # the header; every input file appends its rows
         if _wants_coverage(args):
             coverage.write_coverage(args.coverage)  # the column header; every input file appends its block
+        if _wanted(args, 'depth'):
+            depth.write_depth(args.depth)  # likewise
+        if _wanted(args, 'depth_windows'):
+            depth.write_windows(args.depth_windows)
     acc2info, taxid2info = get_acc2info(args)
     rank_results = gather_results(args, acc2info, taxid2info)
     if not getattr(args, '_not_root', False):

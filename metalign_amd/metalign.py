@@ -58,6 +58,10 @@ def main(argv=None):
     if args.coverage != 'NONE' and int(os.environ.get('WORLD_SIZE', '1')) > 1:
         sys.exit('Error: --coverage runs in one process on one GPU; start it without torch.distributed.run.')
     mapper.check_multimap_flags(args)
+    if (args.depth != 'NONE' or args.depth_windows != 'NONE') and int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        sys.exit('Error: --depth and --depth_windows run in one process on one GPU; start it without torch.distributed.run.')
+    if args.depth_window_size < 1:
+        sys.exit('Error: --depth_window_size must be at least 1.')
     args.data = cli.with_slash(args.data)
     own_temp = args.temp_dir == 'AUTO/'  # a directory of this process's own making (one per rank in a multi-GPU launch)
     if own_temp:
