@@ -71,6 +71,14 @@ typedef struct mg_aln_place {
   uint32_t span;
 } mg_aln_place;
 
+/* How well a record matches its reference (--identity; metalign_amd/identity.py): cols = the sum of the CIGAR's M, I, D and X
+ * lengths (at most 2^32 - 1), nm = the value of the first field `NM:i:` from the twelfth field on, usable when it is [+-]?[0-9]+
+ * with 0 <= value <= 2^32 - 2. */
+typedef struct mg_aln_edit {
+  uint32_t nm; /* 0xffffffff: no usable NM:i: */
+  uint32_t cols;
+} mg_aln_edit;
+
 /* ------------------------------------------------------------------------ *
  * Lifecycle, errors, raw device memory
  * ------------------------------------------------------------------------ */
@@ -94,7 +102,7 @@ int mg_device_count(void);
  *   return their batch keyed and not yet collated); genome_slab_bytes (mg_genomes_stream_open: the size of a page-locked slab,
  *   default 8 MiB, at least 4 KiB), genome_guard (test hook: mg_genomes_parse_dev fills the 16 bytes behind its bases and the
  *   word behind its offsets with 0xa5 before its kernels run); cov_grid (test hook, k3_grid's meaning for k_cov_add /
- *   k_cov_count, mg_coverage.hip); depth_grid (test hook, the same for every grid of mg_depth.hip); mm_hash_bits (test hook, mg_profile_mm_iterate_dev: only this many low bits of a list's hash
+ *   k_cov_count, mg_coverage.hip); depth_grid (test hook, the same for every grid of mg_depth.hip); ident_grid (test hook, the same for k_ident_add, mg_identity.hip); mm_hash_bits (test hook, mg_profile_mm_iterate_dev: only this many low bits of a list's hash
  *   are kept, so that different lists collide).
  * Needs no device and no mg_init.  MG_ERR_ARG for a key that does not exist. */
 int mg_debug_set(const char* key, int64_t value);
@@ -931,11 +939,14 @@ int mg_sam_batch_names_download(const mg_sam_batch* b, uint64_t* off, uint8_t* b
  * MG_ERR_STATE, as mg_sam_batch_collate_dev says.  PLACES (--coverage): mg_aln_place[count] in record order, the same from SAM
  * text and from BAM (pos < 0: not placed), 8 bytes per record; it combines with each of the others — a placed batch that is
  * collated has its places permuted with its records.  PLACES with paf = 1: MG_ERR_ARG (a PAF line has no POS / CIGAR columns).  A file stream keeps keys only to collate
- * by them: KEYS without COLLATE is MG_ERR_ARG there. */
+ * by them: KEYS without COLLATE is MG_ERR_ARG there.  EDITS (--identity): mg_aln_edit[count] in record order, the same from SAM
+ * text and from BAM (a BAM record's aux fields are read as they render); it combines with the others exactly as PLACES does and
+ * is permuted with the records by a collation.  EDITS with paf = 1: MG_ERR_ARG. */
 #define MG_BATCH_KEYS 1u
 #define MG_BATCH_NAMES 2u
 #define MG_BATCH_PLACES 4u
 #define MG_BATCH_COLLATE 8u
+#define MG_BATCH_EDITS 16u
 int mg_sam_tokenize_dev_ex(const uint8_t* d_text, uint64_t nbytes, int paf, const mg_acc_index* ix, const char* prev_qname,
                            mg_sam_batch** out, int* err_kind, uint64_t* err_line, unsigned want);
 int mg_sam_tokenize_ex(const uint8_t* text, uint64_t nbytes, int paf, const mg_acc_index* ix, const char* prev_qname,
@@ -950,6 +961,9 @@ int mg_bam_stream_file_ex(const char* path, const mg_acc_index* ix, uint64_t chu
 /* The places of a placed batch.  MG_ERR_STATE for a batch without places. */
 int mg_sam_batch_places_download(const mg_sam_batch* b, mg_aln_place* places);
 int mg_sam_batch_places_device_ptr(const mg_sam_batch* b, const mg_aln_place** d_places);
+/* The edits of a batch tokenised with MG_BATCH_EDITS.  MG_ERR_STATE for a batch without edits. */
+int mg_sam_batch_edits_download(const mg_sam_batch* b, mg_aln_edit* edits);
+int mg_sam_batch_edits_device_ptr(const mg_sam_batch* b, const mg_aln_edit** d_edits);
 uint64_t mg_sam_batch_count(const mg_sam_batch* b);
 const char* mg_sam_batch_last_qname(const mg_sam_batch* b);
 int mg_sam_batch_device_ptr(const mg_sam_batch* b, const mg_aln_rec** d_recs);
@@ -997,6 +1011,23 @@ int mg_depth_finish(mg_depth* d, uint64_t* alignments, uint64_t* unplaced, uint6
 int mg_depth_fetch_rows(mg_depth* d, uint32_t* accessions, uint64_t* hist);
 int mg_depth_fetch_windows(mg_depth* d, mg_depth_window* windows);
 void mg_depth_free(mg_depth* d);
+
+/* ALIGNMENT IDENTITY (--identity; metalign_amd/csrc/mg_identity.hip; the definition is metalign_amd/identity.py).
+ * create: u64[nacc * 1001] histogram bins, three u64 per accession and the unscored count, zeroed.  nacc = 0 is legal.
+ *   MG_ERR_NOMEM (the byte count in the message) when they do not fit.
+ * add_dev: records and their edits (device pointers, n of each; any number of calls, which sum; n = 0 is legal).  A record counts
+ *   by clean_read_hits' rule, as mg_coverage_add_dev.  A counting record with a usable nm, cols > 0 and an accession row < nacc is
+ *   scored: e = min(nm, cols), bin = (cols - e) * 1000 / cols; it adds 1, cols and e to its accession's alignments, columns and
+ *   edits and 1 to bin `bin` of its histogram.  Every other counting record is one more unscored.  Asynchronous on the library
+ *   stream.
+ * result: alignments, columns, edits (u64[nacc] each) and *unscored.  Synchronises.  May be called again after further add_dev calls.
+ * fetch_hist: hist[r * 1001 + b] = bin b of accession rows[r] (each < nacc, else MG_ERR_ARG).  Synchronises. */
+typedef struct mg_identity mg_identity;
+int mg_identity_create(uint32_t nacc, mg_identity** out);
+int mg_identity_add_dev(mg_identity* h, const mg_aln_rec* d_recs, const mg_aln_edit* d_edit, uint64_t n, double pct_id);
+int mg_identity_result(mg_identity* h, uint64_t* alignments, uint64_t* columns, uint64_t* edits, uint64_t* unscored);
+int mg_identity_fetch_hist(mg_identity* h, const uint32_t* rows, uint32_t nrows, uint64_t* hist);
+void mg_identity_free(mg_identity* h);
 
 /* Host-buffer convenience, single shard = whole stream. Capacities: mm_* as
  * above with mm_cap_reads / mm_cap_entries entries available. */

@@ -50,6 +50,8 @@ EXPORTS = [
     "mg_sam_batch_places_download", "mg_sam_batch_places_device_ptr",
     "mg_coverage_create", "mg_coverage_add_dev", "mg_coverage_result", "mg_coverage_free",
     "mg_depth_create", "mg_depth_add_dev", "mg_depth_finish", "mg_depth_fetch_rows", "mg_depth_fetch_windows", "mg_depth_free",
+    "mg_sam_batch_edits_download", "mg_sam_batch_edits_device_ptr",
+    "mg_identity_create", "mg_identity_add_dev", "mg_identity_result", "mg_identity_fetch_hist", "mg_identity_free",
     "mg_gunzip_open", "mg_gunzip_read", "mg_gunzip_close", "mg_zcat_files", "mg_stream_thin_file",
     "mg_inflate_dev", "mg_inflated_bytes", "mg_inflated_download", "mg_inflated_free", "mg_inflate_config", "mg_inflate_stats",
     "mg_sketch_genomes", "mg_sketch_genomes_prefix", "mg_db_upload", "mg_db_upload_sorted", "mg_db_ngenomes", "mg_db_max_hash", "mg_db_free",
@@ -79,14 +81,19 @@ ERR_HIP, ERR_ARG, ERR_CAPACITY, ERR_STATE, ERR_NOMEM = -1, -2, -3, -4, -5
 # what a batch carries beside its records (include/metalign_hip.h: MG_BATCH_*), and a record's place (mg_aln_place)
 BATCH_KEYS, BATCH_NAMES, BATCH_PLACES, BATCH_COLLATE = 1, 2, 4, 8
 PLACE_DTYPE = np.dtype([("pos0", np.uint32), ("span", np.uint32)])
+# ... and its edit (mg_aln_edit; --identity): nm = EDIT_NONE without a usable NM:i:
+BATCH_EDITS = 16
+EDIT_DTYPE = np.dtype([("nm", np.uint32), ("cols", np.uint32)])
+EDIT_NONE = 0xFFFFFFFF
+IDENTITY_BINS = 1001
 # a kept window of a Depth (mg_depth_window) and the histogram's bins (depth clamped to DEPTH_BINS - 1)
 DEPTH_WINDOW_DTYPE = np.dtype([("index", np.uint64), ("depth_sum", np.uint64), ("acc", np.uint32), ("covered", np.uint32)])
 DEPTH_BINS = 4096
 
 
-def _want(keyed=False, named=False, placed=False, collate=False):
+def _want(keyed=False, named=False, placed=False, collate=False, edited=False):
     return ctypes.c_uint((BATCH_KEYS if keyed else 0) | (BATCH_NAMES if named else 0) | (BATCH_PLACES if placed else 0)
-                         | (BATCH_COLLATE if collate else 0))
+                         | (BATCH_COLLATE if collate else 0) | (BATCH_EDITS if edited else 0))
 
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -134,6 +141,7 @@ def load_library(path=LIB_PATH):
     lib.mg_profile_free.restype = None
     lib.mg_coverage_free.restype = None
     lib.mg_depth_free.restype = None
+    lib.mg_identity_free.restype = None
     lib.mg_shutdown.restype = None
     return lib
 
@@ -1043,6 +1051,19 @@ class SamBatch:
         self.hip._chk(self.hip.lib.mg_sam_batch_places_device_ptr(self.handle, ctypes.byref(p)))
         return p.value or 0
 
+    def edits(self):
+        """The edits of a batch tokenised with edited=True, EDIT_DTYPE[count] in record order (mg_sam_batch_edits_download);
+        ERR_STATE without them."""
+        ed = np.zeros(self.count, dtype=EDIT_DTYPE)
+        self.hip._chk(self.hip.lib.mg_sam_batch_edits_download(self.handle, _vp(ed.ctypes.data if self.count else None)))
+        return ed
+
+    @property
+    def edits_ptr(self):
+        p = _vp()
+        self.hip._chk(self.hip.lib.mg_sam_batch_edits_device_ptr(self.handle, ctypes.byref(p)))
+        return p.value or 0
+
     def collate(self, want_perm=False):
         """A keyed batch regrouped by read in place, its keys freed (mg_sam_batch_collate_dev; metalign_amd/collate.py is the
         definition).  want_perm: -> uint64[count], the index of the record that now comes t-th."""
@@ -1112,6 +1133,77 @@ class Coverage:
     def free(self):
         if self.handle:
             self.hip.lib.mg_coverage_free(self.handle)
+            self.handle = None
+
+
+class IdentityAcc:
+    """Per accession the scored alignments, their columns and edits and a histogram of 1001 identity bins on the device
+    (mg_identity_*; metalign_amd/identity.py is the definition).  HipError with code ERR_NOMEM when they do not fit."""
+
+    def __init__(self, hip, nacc):
+        self.hip = hip
+        self.nacc = int(nacc)
+        h = _vp()
+        hip._chk(hip.lib.mg_identity_create(ctypes.c_uint32(self.nacc), ctypes.byref(h)))
+        self.handle = h
+
+    def add_ptr(self, d_recs, d_edits, n, pct_id):
+        """n records and their edits at device pointers (asynchronous; the arrays must outlive the next synchronisation)."""
+        self.hip._chk(self.hip.lib.mg_identity_add_dev(self.handle, _vp(d_recs), _vp(d_edits), ctypes.c_uint64(int(n)),
+                                                       ctypes.c_double(float(pct_id))))
+
+    def add_batch(self, batch, pct_id):
+        """A SamBatch tokenised with edited=True."""
+        if batch.count:
+            self.add_ptr(batch.ptr, batch.edits_ptr, batch.count, pct_id)
+            self.hip.sync()
+
+    def add(self, recs, edits, pct_id):
+        """Host arrays REC_DTYPE[n], EDIT_DTYPE[n]."""
+        recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
+        edits = np.ascontiguousarray(edits, dtype=EDIT_DTYPE)
+        assert len(recs) == len(edits)
+        if not len(recs):
+            self.add_ptr(None, None, 0, pct_id)
+            return
+        d_r, d_e = self.hip.array(recs.view(np.uint8)), self.hip.array(edits.view(np.uint8))
+        try:
+            self.add_ptr(d_r.ptr, d_e.ptr, len(recs), pct_id)
+            self.hip.sync()
+        finally:
+            d_r.free()
+            d_e.free()
+
+    def sums(self):
+        """-> (alignments, columns, edits) uint64[nacc] each, unscored (mg_identity_result)."""
+        out = [np.zeros(max(self.nacc, 1), dtype=np.uint64) for _ in range(3)]
+        unscored = ctypes.c_uint64(0)
+        self.hip._chk(self.hip.lib.mg_identity_result(self.handle, *[_np(a, ctypes.c_uint64) for a in out], ctypes.byref(unscored)))
+        return tuple(a[:self.nacc] for a in out) + (int(unscored.value),)
+
+    def hist(self, rows):
+        """-> uint64[len(rows), 1001]: the histogram rows of these accession rows (mg_identity_fetch_hist)."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        out = np.zeros((max(rows.size, 1), IDENTITY_BINS), dtype=np.uint64)
+        self.hip._chk(self.hip.lib.mg_identity_fetch_hist(self.handle, _np(rows if rows.size else np.zeros(1, np.uint32), ctypes.c_uint32),
+                                                          ctypes.c_uint32(rows.size), _np(out, ctypes.c_uint64)))
+        return out[:rows.size]
+
+    def result(self):
+        """-> (alignments, columns, edits, unscored, {accession row: {bin: alignments}}) — rows for the accessions with a scored
+        alignment."""
+        aln, cols, eds, unscored = self.sums()
+        hit = np.flatnonzero(aln).astype(np.uint32)
+        H = self.hist(hit)
+        per = {}
+        for r, a in enumerate(hit.tolist()):
+            nz = np.flatnonzero(H[r])
+            per[a] = dict(zip(nz.tolist(), H[r][nz].tolist()))
+        return aln, cols, eds, unscored, per
+
+    def free(self):
+        if self.handle:
+            self.hip.lib.mg_identity_free(self.handle)
             self.handle = None
 
 
@@ -1294,6 +1386,10 @@ class Hip:
     def coverage(self, lengths):
         """A Coverage over accessions of these lengths (mg_coverage_create)."""
         return Coverage(self, lengths)
+
+    def identity(self, nacc):
+        """An IdentityAcc over nacc accession rows (mg_identity_create)."""
+        return IdentityAcc(self, nacc)
 
     def depth(self, lengths, window=0):
         """A Depth over accessions of these lengths, with windows of `window` bases (mg_depth_create)."""
@@ -1651,16 +1747,16 @@ class Hip:
         return n
 
     def sam_tokenize_dev_batch(self, d_text, nbytes, acc_index, prev_qname="", paf=False, named=False, placed=False, keyed=False,
-                               collate=False):
+                               collate=False, edited=False):
         """SAM (or, paf=True, PAF) text resident in HBM -> SamBatch (records stay on the device).  SamParseError as
         sam_tokenize.  named: the batch also carries the reads' names (mg_sam_tokenize_named_dev; SamBatch.names).  placed (with
         any of named / keyed / collate): their places too (mg_sam_tokenize_dev_ex; SamBatch.places)."""
         h = _vp()
         kind, line = ctypes.c_int(0), ctypes.c_uint64(0)
-        if placed or keyed or collate:
+        if placed or keyed or collate or edited:  # (edited: the records' edits too, SamBatch.edits)
             rc = self.lib.mg_sam_tokenize_dev_ex(_vp(d_text), ctypes.c_uint64(nbytes), ctypes.c_int(1 if paf else 0), acc_index.handle,
                                                  ctypes.c_char_p(prev_qname.encode()), ctypes.byref(h), ctypes.byref(kind), ctypes.byref(line),
-                                                 _want(keyed, named, placed, collate))
+                                                 _want(keyed, named, placed, collate, edited))
         elif named:
             rc = self.lib.mg_sam_tokenize_named_dev(_vp(d_text), ctypes.c_uint64(nbytes), ctypes.c_int(1 if paf else 0), acc_index.handle,
                                                     ctypes.c_char_p(prev_qname.encode()), ctypes.byref(h), ctypes.byref(kind), ctypes.byref(line))
@@ -1703,17 +1799,18 @@ class Hip:
             d_p.free()
 
     def sam_stream_file(self, path, acc_index, paf=False, offset=0, length=0, chunk_bytes=0, nthreads=0, collate=False, named=False,
-                        placed=False):
+                        placed=False, edited=False):
         """The alignment file (SAM; paf=True: PAF; plain, gzip or BGZF) -> SamBatch, streamed through page-locked chunks
         inside the library (mg_sam_stream_file): the file read, the upload and the tokeniser overlap, and the text never
         exists as a host array.  SamParseError for a line the reference cannot parse.  placed: the batch carries the records'
         places (mg_sam_stream_file_ex), with collate or named where those are on."""
         h = _vp()
         kind, line = ctypes.c_int(0), ctypes.c_uint64(0)
-        if placed:
+        if placed or edited:  # (edited: and / or their edits)
             rc = self.lib.mg_sam_stream_file_ex(os.fsencode(path), ctypes.c_int(1 if paf else 0), acc_index.handle, ctypes.c_uint64(int(offset)),
                                                 ctypes.c_uint64(int(length)), ctypes.c_uint64(int(chunk_bytes)), ctypes.c_int(int(nthreads)),
-                                                ctypes.byref(h), ctypes.byref(kind), ctypes.byref(line), _want(False, named, True, collate))
+                                                ctypes.byref(h), ctypes.byref(kind), ctypes.byref(line),
+                                                _want(False, named, placed, collate, edited))
             if rc != 0 and kind.value:
                 raise SamParseError(kind.value, line.value)
             self._chk(rc)
@@ -1730,15 +1827,16 @@ class Hip:
         self._chk(rc)
         return SamBatch(self, h)
 
-    def bam_stream_file(self, path, acc_index, chunk_bytes=0, nthreads=0, collate=False, named=False, placed=False):
+    def bam_stream_file(self, path, acc_index, chunk_bytes=0, nthreads=0, collate=False, named=False, placed=False, edited=False):
         """A BAM file -> SamBatch: the records its SAM rendering gives through sam_stream_file (mg_bam_stream_file).  SamParseError
         for a record whose rendering the reference cannot parse, that the device does not decide (kind 6) or that is not a BAM
         record the package takes (kind 7); `line` is the record's number within its piece."""
         h = _vp()
         kind, rec = ctypes.c_int(0), ctypes.c_uint64(0)
-        if placed:  # (the batch carries the records' places: mg_bam_stream_file_ex)
+        if placed or edited:  # (the batch carries the records' places and / or edits: mg_bam_stream_file_ex)
             rc = self.lib.mg_bam_stream_file_ex(os.fsencode(path), acc_index.handle, ctypes.c_uint64(int(chunk_bytes)), ctypes.c_int(int(nthreads)),
-                                                ctypes.byref(h), ctypes.byref(kind), ctypes.byref(rec), _want(False, named, True, collate))
+                                                ctypes.byref(h), ctypes.byref(kind), ctypes.byref(rec),
+                                                _want(False, named, placed, collate, edited))
             if rc != 0 and kind.value:
                 raise SamParseError(kind.value, rec.value)
             self._chk(rc)
@@ -1754,7 +1852,8 @@ class Hip:
         self._chk(rc)
         return SamBatch(self, h)
 
-    def bam_tokenize_dev(self, d_bytes, nbytes, refmap, acc_index, prev_qname="", final=True, keyed=False, named=False, placed=False):
+    def bam_tokenize_dev(self, d_bytes, nbytes, refmap, acc_index, prev_qname="", final=True, keyed=False, named=False, placed=False,
+                         edited=False, collate=False):
         """BAM record bytes resident in HBM (behind the header) -> (SamBatch, consumed) (mg_bam_tokenize_dev); refmap: the accession row
         of every header reference (-1: none, -2: not one SAM field).  SamParseError as bam_stream_file."""
         rm = np.ascontiguousarray(refmap, dtype=np.int32)
@@ -1765,8 +1864,8 @@ class Hip:
             assert not keyed
             fn = self.lib.mg_bam_tokenize_named_dev
         extra = ()
-        if placed:  # (the batch carries the records' places)
-            fn, extra = self.lib.mg_bam_tokenize_dev_ex, (_want(keyed, named, True),)
+        if placed or edited or collate:  # (the batch carries the records' places and / or edits)
+            fn, extra = self.lib.mg_bam_tokenize_dev_ex, (_want(keyed, named, placed, collate, edited),)
         rc = fn(_vp(d_bytes), ctypes.c_uint64(nbytes), _np(rm if rm.size else np.zeros(1, np.int32), ctypes.c_int32),
                                           ctypes.c_uint32(rm.size), acc_index.handle, ctypes.c_char_p(prev_qname.encode()),
                                           ctypes.c_int(1 if final else 0), ctypes.byref(used), ctypes.byref(h), ctypes.byref(kind),
@@ -1786,7 +1885,7 @@ class Hip:
                                               ctypes.c_uint32(len(names)), ctypes.byref(h)))
         return AccIndex(self, h)
 
-    def sam_tokenize(self, text, acc_index, prev_qname="", paf=False, named=False, placed=False):
+    def sam_tokenize(self, text, acc_index, prev_qname="", paf=False, named=False, placed=False, edited=False):
         """One chunk of SAM (paf=True: PAF) text (ending on a line boundary) -> (records REC_DTYPE[], QNAME of its last
         retained line).  Raises SamParseError for a line the reference cannot parse.  named: -> (records, last QNAME, (name bytes,
         offsets)) — the names of the reads that open in this chunk (mg_sam_tokenize_named)."""
@@ -1794,10 +1893,10 @@ class Hip:
         h = _vp()
         kind, line = ctypes.c_int(0), ctypes.c_uint64(0)
         src = buf if buf.size else np.zeros(1, np.uint8)
-        if placed:  # (one more element at the end of what is returned: the records' places, PLACE_DTYPE[])
+        if placed or edited:  # (at the end of what is returned: the records' places, PLACE_DTYPE[], then their edits, EDIT_DTYPE[])
             rc = self.lib.mg_sam_tokenize_ex(_np(src, ctypes.c_uint8), ctypes.c_uint64(buf.size), ctypes.c_int(1 if paf else 0),
                                              acc_index.handle, ctypes.c_char_p(prev_qname.encode()), ctypes.byref(h),
-                                             ctypes.byref(kind), ctypes.byref(line), _want(False, named, True))
+                                             ctypes.byref(kind), ctypes.byref(line), _want(False, named, placed, False, edited))
         elif named:
             rc = self.lib.mg_sam_tokenize_named(_np(src, ctypes.c_uint8), ctypes.c_uint64(buf.size), ctypes.c_int(1 if paf else 0),
                                                 acc_index.handle, ctypes.c_char_p(prev_qname.encode()), ctypes.byref(h),
@@ -1821,6 +1920,10 @@ class Hip:
                 pl = np.zeros(n, dtype=PLACE_DTYPE)
                 self._chk(self.lib.mg_sam_batch_places_download(h, _vp(pl.ctypes.data if n else None)))
                 tail = (pl,)
+            if edited:
+                ed = np.zeros(n, dtype=EDIT_DTYPE)
+                self._chk(self.lib.mg_sam_batch_edits_download(h, _vp(ed.ctypes.data if n else None)))
+                tail = tail + (ed,)
             if named:
                 nr, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
                 self._chk(self.lib.mg_sam_batch_names_size(h, ctypes.byref(nr), ctypes.byref(nb)))

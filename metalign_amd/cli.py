@@ -54,6 +54,10 @@ _OPTIONS = {
                      'genome (G rows) the placed alignments, aligned bases, covered bases, breadth, mean depth and the breadth that '
                      'depth predicts, from the alignments stage C keeps (metalign_amd/coverage.py is the definition). SAM / BAM '
                      'input, one process only.'),
+    'identity': dict(default='NONE', help='Also write alignment identity here (TSV): per accession (S rows) and per genome (G rows) '
+                     'the scored alignments, their aligned columns and summed edit distance (NM:i:), the identity those give, the '
+                     'median and 10th percentile of per-alignment identity and the alignments at 90, 95, 97 and 99 %% or more '
+                     '(metalign_amd/identity.py is the definition). SAM / BAM input, one process only.'),
     'depth': dict(default='NONE', help='Also write the distribution of per-base depth here (TSV): per accession (S rows) and per '
                   'genome (G rows) the mean, median, 5-95 %% trimmed mean, variance and maximum of the depth (clamped at 4095) and the '
                   'bases at 1x, 5x, 10x and 30x or more (metalign_amd/depth.py is the definition). SAM / BAM input, one process only.'),
@@ -82,7 +86,7 @@ _TOOLS = {
                  'low_mem', 'min_abundance', 'no_quantify_unmapped', 'output', 'pct_id', 'precise', 'rank_renormalize',
                  'read_cutoff', 'sampleID', 'sensitive', 'strain_level', 'temp_dir', 'threads', 'verbose',
                  'sketch_table', 'min_count', 'sketch_size', 'kmer_match', 'device_multimap', 'collate', 'read_assignments', 'coverage',
-                 'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size']),
+                 'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size', 'identity']),
     'select_db': dict(
         description='Run CMash and select a subset of the whole database to align to.',
         positionals=[('reads', dict(help='Reads file (FASTA / FASTQ, optionally .gz, or a BAM of reads).')),
@@ -98,7 +102,7 @@ _TOOLS = {
                  ('input_type', ['fastq', 'fasta', 'sam', 'AUTO']), 'length_normalize', 'low_mem', 'min_abundance',
                  'rank_renormalize', 'output', 'pct_id', 'no_quantify_unmapped', 'read_cutoff', 'sampleID', 'threads',
                  'verbose', 'device_multimap', 'collate', 'read_assignments', 'coverage',
-                 'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size']),
+                 'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size', 'identity']),
 }
 
 

@@ -86,6 +86,13 @@ __global__ __launch_bounds__(256) void k_collate_gather_places(const mg_aln_plac
   for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += stride) out[t] = place[perm[t]];
 }
 
+// ... and its edits (MG_BATCH_EDITS)
+__global__ __launch_bounds__(256) void k_collate_gather_edits(const mg_aln_edit* __restrict__ edit, const uint64_t* __restrict__ perm,
+                                                              uint64_t n, mg_aln_edit* __restrict__ out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += stride) out[t] = edit[perm[t]];
+}
+
 // keys and flags -> d_perm[t] = the index of the record that comes t-th; *d_fkey (optional) = the sorted final keys (scratch:
 // valid until the next collation).  n > 0.
 static int collate_order(const uint64_t* d_keys2, const mg_aln_rec* d_recs, uint64_t n, uint64_t* d_perm, const uint64_t** d_fkey) {
@@ -138,12 +145,20 @@ int collate_batch(mg_sam_batch* b, uint64_t* d_perm_or_null) {
                          b->places.as<mg_aln_place>(), d_perm, n, out_places.as<mg_aln_place>());
       MG_HIP(hipGetLastError());
     }
+    DevBuf out_edits;
+    if (b->edited) {
+      MG_TRY(out_edits.alloc((n + 1) * sizeof(mg_aln_edit)));
+      hipLaunchKernelGGL(k_collate_gather_edits, dim3(grid_for(n, 256, (unsigned)ctx().num_cus * 16)), dim3(256), 0, st,
+                         b->edits.as<mg_aln_edit>(), d_perm, n, out_edits.as<mg_aln_edit>());
+      MG_HIP(hipGetLastError());
+    }
     hipLaunchKernelGGL(k_collate_gather, dim3(grid_for(n, 256, (unsigned)ctx().num_cus * 16)), dim3(256), 0, st, b->recs.as<mg_aln_rec>(),
                        d_perm, d_fkey, n, out.as<mg_aln_rec>());
     MG_HIP(hipGetLastError());
     MG_HIP(hipStreamSynchronize(st));
     b->recs = std::move(out);
     if (b->placed) b->places = std::move(out_places);
+    if (b->edited) b->edits = std::move(out_edits);
   }
   b->keys.release();
   b->keyed = false;

@@ -18,6 +18,7 @@
 
 #include "mg_collate_core.h"
 #include "mg_coverage_core.h"
+#include "mg_identity_core.h"
 #include "mg_internal.h"
 
 namespace mg {
@@ -282,9 +283,13 @@ __device__ __forceinline__ int64_t acc_lookup(const AccTable& t, const uint8_t* 
 
 // One thread per line: everything except the new-read bit.  err: [0] = first failing line (atomicMin),
 // kinds[line] holds the failure kind for the host to look up.
+// kFields (MG_BATCH_EDITS): a retained line also leaves where its CIGAR field and its twelfth field start in fields[2 l], [2 l + 1],
+// so that k_sam_edit steps over neither the line's front nor SEQ and QUAL again.  The instantiation without it is the kernel as it was.
+template <bool kFields>
 __global__ void k_sam_parse(const uint8_t* __restrict__ text, const uint64_t* __restrict__ line_end, uint64_t nlines,
                             AccTable acc, LineOut* __restrict__ out, uint32_t* __restrict__ retained,
-                            unsigned long long* __restrict__ err, uint32_t* __restrict__ err_kind, uint32_t thin) {
+                            unsigned long long* __restrict__ err, uint32_t* __restrict__ err_kind, uint32_t thin,
+                            uint64_t* __restrict__ fields) {
   uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (; l < nlines; l += stride) {
@@ -366,6 +371,10 @@ __global__ void k_sam_parse(const uint8_t* __restrict__ text, const uint64_t* __
               o.rec.flag_len = (uint32_t)(flag & MG_REC_FLAG_MASK) | ((uint32_t)slen << MG_REC_LEN_SHIFT);
               o.qbeg = fb[0];
               o.qlen = (uint32_t)(fe[0] - fb[0]);
+              if (kFields) {
+                fields[2 * l] = fb[5];
+                fields[2 * l + 1] = fb[11];
+              }
             }
           }
         }
@@ -594,6 +603,31 @@ __global__ __launch_bounds__(256) void k_bam_place(const uint8_t* __restrict__ b
   uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (; r < nret; r += stride) place[r] = mgv::place_of_bam(bytes, lines[ret_line[r]].qbeg);
+}
+
+// EDITED (--identity): record r is retained line ret_line[r]; its CIGAR (field 6) and the fields from the twelfth on -> edit[r]
+// (mg_identity_core.h: edit_of_line).  The parser left both fields' offsets (fields[2 l], [2 l + 1]), so a thread reads the few bytes
+// of the CIGAR and then the tags up to the end of the first NM:i: field — minimap2 writes it first, so that is ~8 bytes.  A field
+// that is not NM:i: is stepped over with the parser's 8-byte loads.  Thinned text keeps every byte from the tags on and its CIGAR
+// where it was.
+struct WideSkip {
+  __device__ __forceinline__ uint64_t operator()(const uint8_t* text, uint64_t p, uint64_t end) const { return scan_to_ws(text, p, end); }
+};
+__global__ __launch_bounds__(256) void k_sam_edit(const uint8_t* __restrict__ text, const uint64_t* __restrict__ line_end, const uint64_t* __restrict__ fields,
+                           const uint64_t* __restrict__ ret_line, uint64_t nret, mg_aln_edit* __restrict__ edit) {
+  uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (; r < nret; r += stride) {
+    const uint64_t l = ret_line[r];
+    edit[r] = mgi::edit_of_line(text, fields[2 * l], fields[2 * l + 1], line_end[l], WideSkip());
+  }
+}
+// ... of a BAM record: the packed ops behind the QNAME, then the aux fields as they render, never past the record's end
+__global__ __launch_bounds__(256) void k_bam_edit(const uint8_t* __restrict__ bytes, const LineOut* __restrict__ lines, const uint64_t* __restrict__ ret_line,
+                           uint64_t nret, mg_aln_edit* __restrict__ edit) {
+  uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (; r < nret; r += stride) edit[r] = mgi::edit_of_bam(bytes, lines[ret_line[r]].qbeg);
 }
 
 // Shared: build the line index of a text buffer.  If the text does not end in '\n' the last partial
@@ -896,10 +930,11 @@ __global__ void k_sam_last_qname(const uint8_t* __restrict__ text, const LineOut
 // the byte after the last newline (what follows is carried to the next piece by the caller, mg_stream.hip).
 int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg_acc_index* ix, const char* prev_qname,
                                 bool paf, bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_line,
-                                bool thin, bool keyed, bool named, bool placed) {
+                                bool thin, bool keyed, bool named, bool placed, bool edited) {
   MG_REQUIRE_READY();
   if (!out || !ix) return fail(MG_ERR_ARG, "null argument");
   if (placed && paf) return fail(MG_ERR_ARG, "a PAF line has no POS and CIGAR columns: no places from PAF");
+  if (edited && paf) return fail(MG_ERR_ARG, "no edits from PAF (its NM:i: and cg:Z: tags are not read)");
   *out = nullptr;
   if (err_kind) *err_kind = 0;
   if (err_line) *err_line = 0;
@@ -919,6 +954,7 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
     if (keyed) MG_TRY(sb->keys.alloc(16));
     if (named) MG_TRY(names_empty(sb.get()));
     if (placed) MG_TRY(places_empty(sb.get()));
+    if (edited) MG_TRY(edits_empty(sb.get()));
     *out = sb.release();
     return MG_OK;
   }
@@ -931,6 +967,11 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
   const size_t plen = prev_qname ? strlen(prev_qname) : 0;
   uint8_t* d_prev = (uint8_t*)scratch("sam_prev", plen + 16);
   if (!d_lines || !d_ret || !d_rank || !d_kind || !d_err || !d_prev) return MG_ERR_NOMEM;
+  uint64_t* d_fields = nullptr;
+  if (edited) {
+    d_fields = (uint64_t*)scratch("sam_fields", nlines * 2 * sizeof(uint64_t));
+    if (!d_fields) return MG_ERR_NOMEM;
+  }
   MG_HIP(hipMemsetAsync(d_err, 0xff, sizeof(unsigned long long), st));
   if (plen) MG_HIP(hipMemcpyAsync(d_prev, prev_qname, plen, hipMemcpyHostToDevice, st));
   AccTable at{ix->slot_hash.as<uint64_t>(), ix->slot_row.as<uint32_t>(), ix->slots - 1, ix->names.as<uint8_t>(),
@@ -941,9 +982,12 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
     if (paf)
       hipLaunchKernelGGL(k_paf_parse, dim3(grid_for(nlines, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_text, d_le,
                          nlines, at, d_lines, d_ret, d_err, d_kind);
+    else if (edited)
+      hipLaunchKernelGGL(k_sam_parse<true>, dim3(grid_for(nlines, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_text, d_le,
+                         nlines, at, d_lines, d_ret, d_err, d_kind, thin ? 1u : 0u, d_fields);
     else
-      hipLaunchKernelGGL(k_sam_parse, dim3(grid_for(nlines, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_text, d_le,
-                         nlines, at, d_lines, d_ret, d_err, d_kind, thin ? 1u : 0u);
+      hipLaunchKernelGGL(k_sam_parse<false>, dim3(grid_for(nlines, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_text, d_le,
+                         nlines, at, d_lines, d_ret, d_err, d_kind, thin ? 1u : 0u, (uint64_t*)nullptr);
     MG_HIP(hipGetLastError());
     uint64_t* pin = host_words();
     MG_HIP(hipMemcpyAsync(pin + 14, d_err, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));  // (rides on the scan's synchronisation)
@@ -958,7 +1002,7 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
       return fail(MG_ERR_ARG, "%s line %llu: parse error kind %u", paf ? "PAF" : "SAM", h_err, kind);
     }
     MG_TRY(aln_emit_retained(d_text, d_lines, d_ret, d_rank, nlines, nret, d_prev, (uint32_t)plen, sb.get(), keyed, named,
-                             placed ? kPlaceSam : kPlaceNone, d_le));
+                             placed ? kPlaceSam : kPlaceNone, d_le, edited ? kPlaceSam : kPlaceNone, d_fields));
   }
   sb->nrecs = nret;
   *out = sb.release();
@@ -969,7 +1013,7 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
 // sb->last_qname.  The SAM / PAF tokeniser above and the BAM decoder (mg_bam.hip) end here.
 int mg::aln_emit_retained(const uint8_t* d_text, const LineOut* d_lines, const uint32_t* d_ret, const uint64_t* d_rank, uint64_t nlines,
                           uint64_t nret, const uint8_t* d_prev, uint32_t plen, mg_sam_batch* sb, bool keyed, bool named, int placed,
-                          const uint64_t* d_line_end) {
+                          const uint64_t* d_line_end, int edited, const uint64_t* d_fields) {
   Context& c = ctx();
   hipStream_t st = c.stream;
   MG_TRY(sb->recs.alloc((nret + 1) * sizeof(mg_aln_rec)));
@@ -979,6 +1023,11 @@ int mg::aln_emit_retained(const uint8_t* d_text, const LineOut* d_lines, const u
     if (placed == kPlaceSam && !d_line_end) return fail(MG_ERR_ARG, "places from text need its line index");
     MG_TRY(sb->places.alloc((nret + 1) * sizeof(mg_aln_place)));
     sb->placed = true;
+  }
+  if (edited) {
+    if (edited == kPlaceSam && (!d_line_end || !d_fields)) return fail(MG_ERR_ARG, "edits from text need its line index and field offsets");
+    MG_TRY(sb->edits.alloc((nret + 1) * sizeof(mg_aln_edit)));
+    sb->edited = true;
   }
   if (nret) {
     uint64_t* d_list = (uint64_t*)scratch("sam_list", nret * sizeof(uint64_t));
@@ -999,6 +1048,15 @@ int mg::aln_emit_retained(const uint8_t* d_text, const LineOut* d_lines, const u
         hipLaunchKernelGGL(k_sam_place, dim3(grid), dim3(256), 0, st, d_text, d_line_end, d_list, nret, sb->places.as<mg_aln_place>());
       else
         hipLaunchKernelGGL(k_bam_place, dim3(grid), dim3(256), 0, st, d_text, d_lines, d_list, nret, sb->places.as<mg_aln_place>());
+      MG_HIP(hipGetLastError());
+    }
+    if (edited) {  // (likewise)
+      ProfScope ps("ingest_edits");
+      const unsigned grid = grid_for(nret, 256, (unsigned)c.num_cus * 16);
+      if (edited == kPlaceSam)
+        hipLaunchKernelGGL(k_sam_edit, dim3(grid), dim3(256), 0, st, d_text, d_line_end, d_fields, d_list, nret, sb->edits.as<mg_aln_edit>());
+      else
+        hipLaunchKernelGGL(k_bam_edit, dim3(grid), dim3(256), 0, st, d_text, d_lines, d_list, nret, sb->edits.as<mg_aln_edit>());
       MG_HIP(hipGetLastError());
     }
     // QNAME of the last retained line, for the next chunk: its span and its first kQnameInline bytes in ONE round trip
@@ -1062,6 +1120,12 @@ int mg::places_empty(mg_sam_batch* sb) {
   return MG_OK;
 }
 
+int mg::edits_empty(mg_sam_batch* sb) {
+  MG_TRY(sb->edits.alloc(16));
+  sb->edited = true;
+  return MG_OK;
+}
+
 int mg::names_empty(mg_sam_batch* sb) {
   MG_TRY(sb->name_off.alloc(2 * sizeof(uint64_t)));
   MG_TRY(sb->name_bytes.alloc(16));
@@ -1091,13 +1155,15 @@ int mg_sam_tokenize_named(const uint8_t* text, uint64_t nbytes, int paf, const m
 // The flag-taking family: what the plain, keyed, named and collated calls give, and the places, by one mask.
 int mg_sam_tokenize_dev_ex(const uint8_t* d_text, uint64_t nbytes, int paf, const mg_acc_index* ix, const char* prev_qname,
                            mg_sam_batch** out, int* err_kind, uint64_t* err_line, unsigned want) {
-  if (want & ~(MG_BATCH_KEYS | MG_BATCH_NAMES | MG_BATCH_PLACES | MG_BATCH_COLLATE)) return fail(MG_ERR_ARG, "unknown bits in want");
+  if (want & ~(MG_BATCH_KEYS | MG_BATCH_NAMES | MG_BATCH_PLACES | MG_BATCH_COLLATE | MG_BATCH_EDITS)) return fail(MG_ERR_ARG, "unknown bits in want");
   if ((want & MG_BATCH_PLACES) && paf) return fail(MG_ERR_ARG, "a PAF line has no POS and CIGAR columns: no places from PAF");
+  if ((want & MG_BATCH_EDITS) && paf) return fail(MG_ERR_ARG, "no edits from PAF (its NM:i: and cg:Z: tags are not read)");
   if ((want & MG_BATCH_NAMES) && (want & MG_BATCH_COLLATE))
     return fail(MG_ERR_STATE, "a named batch is not collated (its names are in the order the reads came in)");
   const bool collate = (want & MG_BATCH_COLLATE) != 0;
   MG_TRY(mg::aln_tokenize_prefix_dev(d_text, nbytes, ix, prev_qname, paf != 0, true, nullptr, out, err_kind, err_line, false,
-                                     collate || (want & MG_BATCH_KEYS), (want & MG_BATCH_NAMES) != 0, (want & MG_BATCH_PLACES) != 0));
+                                     collate || (want & MG_BATCH_KEYS), (want & MG_BATCH_NAMES) != 0, (want & MG_BATCH_PLACES) != 0,
+                                     (want & MG_BATCH_EDITS) != 0));
   if (collate) {
     const int rc = mg::collate_batch(*out, nullptr);
     if (rc != MG_OK) { delete *out; *out = nullptr; return rc; }
@@ -1127,6 +1193,22 @@ int mg_sam_batch_places_device_ptr(const mg_sam_batch* b, const mg_aln_place** d
   if (!b || !d_places) return fail(MG_ERR_ARG, "null argument");
   if (!b->placed) return fail(MG_ERR_STATE, "the batch carries no places (tokenise it with MG_BATCH_PLACES)");
   *d_places = b->places.as<mg_aln_place>();
+  return MG_OK;
+}
+
+int mg_sam_batch_edits_download(const mg_sam_batch* b, mg_aln_edit* edits) {
+  MG_REQUIRE_READY();
+  if (!b) return fail(MG_ERR_ARG, "null batch");
+  if (!b->edited) return fail(MG_ERR_STATE, "the batch carries no edits (tokenise it with MG_BATCH_EDITS)");
+  if (b->nrecs && !edits) return fail(MG_ERR_ARG, "null argument");
+  if (b->nrecs) MG_TRY(mg_memcpy_d2h(edits, b->edits.p, b->nrecs * sizeof(mg_aln_edit)));
+  return MG_OK;
+}
+
+int mg_sam_batch_edits_device_ptr(const mg_sam_batch* b, const mg_aln_edit** d_edits) {
+  if (!b || !d_edits) return fail(MG_ERR_ARG, "null argument");
+  if (!b->edited) return fail(MG_ERR_STATE, "the batch carries no edits (tokenise it with MG_BATCH_EDITS)");
+  *d_edits = b->edits.as<mg_aln_edit>();
   return MG_OK;
 }
 

@@ -1023,13 +1023,14 @@ int mg_reads_from_bam_file(const char* path, uint64_t chunk_bytes, int nthreads,
 // named pieces: their names appended, their offsets moved up by the bytes in front of them (a read that goes on into the next
 // piece opens no read there, so it is named once)
 static int concat_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uint64_t total, const std::string& prev, bool keyed,
-                          mg_sam_batch** out, bool named = false, bool placed = false) {
+                          mg_sam_batch** out, bool named = false, bool placed = false, bool edited = false) {
   std::unique_ptr<mg_sam_batch> all(new mg_sam_batch());
   all->last_qname = prev;
   all->nrecs = total;
   all->keyed = keyed;
   if (named && parts.empty()) MG_TRY(names_empty(all.get()));
   if (placed && parts.empty()) MG_TRY(places_empty(all.get()));
+  if (edited && parts.empty()) MG_TRY(edits_empty(all.get()));
   if (parts.size() == 1) {
     all->recs = std::move(parts[0]->recs);
     all->keys = std::move(parts[0]->keys);
@@ -1040,12 +1041,18 @@ static int concat_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uin
     all->named = parts[0]->named;
     all->places = std::move(parts[0]->places);
     all->placed = parts[0]->placed;
+    all->edits = std::move(parts[0]->edits);
+    all->edited = parts[0]->edited;
   } else {
     MG_TRY(all->recs.alloc((total + 1) * sizeof(mg_aln_rec)));
     if (keyed) MG_TRY(all->keys.alloc((total + 1) * 2 * sizeof(uint64_t)));
     if (placed && !parts.empty()) {  // the pieces' places, joined in record order like the keys
       MG_TRY(all->places.alloc((total + 1) * sizeof(mg_aln_place)));
       all->placed = true;
+    }
+    if (edited && !parts.empty()) {  // ... and their edits
+      MG_TRY(all->edits.alloc((total + 1) * sizeof(mg_aln_edit)));
+      all->edited = true;
     }
     uint64_t at = 0;
     hipStream_t st = ctx().stream;
@@ -1056,6 +1063,8 @@ static int concat_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uin
         MG_HIP(hipMemcpyAsync(all->keys.as<uint64_t>() + 2 * at, p->keys.p, p->nrecs * 2 * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
       if (placed && p->nrecs)
         MG_HIP(hipMemcpyAsync(all->places.as<mg_aln_place>() + at, p->places.p, p->nrecs * sizeof(mg_aln_place), hipMemcpyDeviceToDevice, st));
+      if (edited && p->nrecs)
+        MG_HIP(hipMemcpyAsync(all->edits.as<mg_aln_edit>() + at, p->edits.p, p->nrecs * sizeof(mg_aln_edit), hipMemcpyDeviceToDevice, st));
       at += p->nrecs;
     }
     if (named && !parts.empty()) {
@@ -1088,9 +1097,9 @@ static int concat_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uin
 // ... and, for the collated entry points, regrouped by read (mg_collate.hip).  The knob collate_defer (a test hook) leaves the
 // batch as it was tokenised, keys and all, for the caller to look at and collate (mg_sam_batch_collate_dev).
 static int finish_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uint64_t total, const std::string& prev, bool collate,
-                          mg_sam_batch** out, bool named = false, bool placed = false) {
+                          mg_sam_batch** out, bool named = false, bool placed = false, bool edited = false) {
   mg_sam_batch* all = nullptr;
-  MG_TRY(concat_batches(parts, total, prev, collate, &all, named, placed));
+  MG_TRY(concat_batches(parts, total, prev, collate, &all, named, placed, edited));
   if (collate && !dbg("collate_defer")) {
     parts.clear();  // (the pieces' buffers go back to the pool before the sort asks for its own)
     const int rc = collate_batch(all, nullptr);
@@ -1107,7 +1116,7 @@ static int finish_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uin
 // the file through the host tokeniser, which raises what the reference raises).
 static int sam_stream_file_impl(const char* path, int paf, const mg_acc_index* ix, uint64_t offset, uint64_t length,
                                 uint64_t chunk_bytes, int nthreads, mg_sam_batch** out, int* err_kind, uint64_t* err_line, bool collate,
-                                bool named = false, bool placed = false) {
+                                bool named = false, bool placed = false, bool edited = false) {
   MG_REQUIRE_READY();
   if (!path || !ix || !out) return fail(MG_ERR_ARG, "null argument");
   *out = nullptr;
@@ -1122,19 +1131,20 @@ static int sam_stream_file_impl(const char* path, int paf, const mg_acc_index* i
   uint64_t total = 0;
   MG_TRY(stream_file(path, plan, [&](const uint8_t* d_text, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
     mg_sam_batch* b = nullptr;
-    MG_TRY(aln_tokenize_prefix_dev(d_text, nbytes, ix, prev.c_str(), paf != 0, final, consumed, &b, err_kind, err_line, thinned, collate, named, placed));
+    MG_TRY(aln_tokenize_prefix_dev(d_text, nbytes, ix, prev.c_str(), paf != 0, final, consumed, &b, err_kind, err_line, thinned, collate, named, placed, edited));
     prev = b->last_qname;
     total += b->nrecs;
     parts.emplace_back(b);
     return MG_OK;
   }, &thinned));
-  return finish_batches(parts, total, prev, collate, out, named, placed);
+  return finish_batches(parts, total, prev, collate, out, named, placed, edited);
 }
 
 // The flag-taking streams (MG_BATCH_*): KEYS alone keeps the keys on the batch (as the knob collate_defer does for a collated call).
 static int stream_want_check(unsigned want, int paf) {
-  if (want & ~(MG_BATCH_KEYS | MG_BATCH_NAMES | MG_BATCH_PLACES | MG_BATCH_COLLATE)) return fail(MG_ERR_ARG, "unknown bits in want");
+  if (want & ~(MG_BATCH_KEYS | MG_BATCH_NAMES | MG_BATCH_PLACES | MG_BATCH_COLLATE | MG_BATCH_EDITS)) return fail(MG_ERR_ARG, "unknown bits in want");
   if ((want & MG_BATCH_PLACES) && paf) return fail(MG_ERR_ARG, "a PAF line has no POS and CIGAR columns: no places from PAF");
+  if ((want & MG_BATCH_EDITS) && paf) return fail(MG_ERR_ARG, "no edits from PAF (its NM:i: and cg:Z: tags are not read)");
   if ((want & MG_BATCH_NAMES) && (want & MG_BATCH_COLLATE))
     return fail(MG_ERR_STATE, "a named batch is not collated (its names are in the order the reads came in)");
   if ((want & MG_BATCH_KEYS) && !(want & MG_BATCH_COLLATE))
@@ -1146,7 +1156,8 @@ int mg_sam_stream_file_ex(const char* path, int paf, const mg_acc_index* ix, uin
                           uint64_t chunk_bytes, int nthreads, mg_sam_batch** out, int* err_kind, uint64_t* err_line, unsigned want) {
   MG_TRY(stream_want_check(want, paf));
   return sam_stream_file_impl(path, paf, ix, offset, length, chunk_bytes, nthreads, out, err_kind, err_line,
-                              (want & MG_BATCH_COLLATE) != 0, (want & MG_BATCH_NAMES) != 0, (want & MG_BATCH_PLACES) != 0);
+                              (want & MG_BATCH_COLLATE) != 0, (want & MG_BATCH_NAMES) != 0, (want & MG_BATCH_PLACES) != 0,
+                              (want & MG_BATCH_EDITS) != 0);
 }
 
 int mg_sam_stream_file_named(const char* path, int paf, const mg_acc_index* ix, uint64_t offset, uint64_t length,
@@ -1168,7 +1179,8 @@ int mg_sam_stream_file_collated(const char* path, int paf, const mg_acc_index* i
 // the header read here with zlib and stepped over in the first piece(s), every piece cut after its last complete record
 // (mg_bam.hip).
 static int bam_stream_file_impl(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,
-                                int* err_kind, uint64_t* err_rec, bool collate, bool named = false, bool placed = false) {
+                                int* err_kind, uint64_t* err_rec, bool collate, bool named = false, bool placed = false,
+                                bool edited = false) {
   MG_REQUIRE_READY();
   if (!path || !ix || !out) return fail(MG_ERR_ARG, "null argument");
   *out = nullptr;
@@ -1188,20 +1200,20 @@ static int bam_stream_file_impl(const char* path, const mg_acc_index* ix, uint64
   MG_TRY(stream_file(path, plan, skip_bam_header(hdr.bytes, path, [&](const uint8_t* d_recs, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
     mg_sam_batch* b = nullptr;
     MG_TRY(bam_tokenize_prefix_dev(d_recs, nbytes, d_map.as<int32_t>(), (int32_t)hdr.names.size(), prev.c_str(), final, consumed, &b,
-                                   err_kind, err_rec, collate, named, placed));
+                                   err_kind, err_rec, collate, named, placed, edited));
     prev = b->last_qname;
     total += b->nrecs;
     parts.emplace_back(b);
     return MG_OK;
   })));
-  return finish_batches(parts, total, prev, collate, out, named, placed);
+  return finish_batches(parts, total, prev, collate, out, named, placed, edited);
 }
 
 int mg_bam_stream_file_ex(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,
                           int* err_kind, uint64_t* err_rec, unsigned want) {
   MG_TRY(stream_want_check(want, 0));
   return bam_stream_file_impl(path, ix, chunk_bytes, nthreads, out, err_kind, err_rec, (want & MG_BATCH_COLLATE) != 0,
-                              (want & MG_BATCH_NAMES) != 0, (want & MG_BATCH_PLACES) != 0);
+                              (want & MG_BATCH_NAMES) != 0, (want & MG_BATCH_PLACES) != 0, (want & MG_BATCH_EDITS) != 0);
 }
 
 int mg_bam_stream_file_named(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,

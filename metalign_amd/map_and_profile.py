@@ -29,7 +29,7 @@ import time
 
 import numpy as np
 
-from . import _hip, assignments, bam, cli, collate, coverage, depth
+from . import _hip, assignments, bam, cli, collate, coverage, depth, identity
 
 start = time.time()
 RANKS = ['superkingdom', 'phylum', 'class', 'order', 'family', 'genus', 'species', 'strain']
@@ -284,6 +284,16 @@ def _host_places(lines):
     return np.array(out, dtype=_hip.PLACE_DTYPE) if out else np.zeros(0, dtype=_hip.PLACE_DTYPE)
 
 
+def _host_edits(lines):
+    """The edits of the lines the host tokeniser retains (identity.edit_of), EDIT_DTYPE[] in record order."""
+    out = []
+    for ln in lines:
+        f = coverage.retained_fields(ln)
+        if f is not None:
+            out.append(identity.edit_of(f))
+    return np.array(out, dtype=_hip.EDIT_DTYPE) if out else np.zeros(0, dtype=_hip.EDIT_DTYPE)
+
+
 def _leading_header(chunk, header, state):
     """--coverage on the chunked path: the stream's leading '@' lines -> header, scanned only while lines start with '@'."""
     if not state['leading']:
@@ -306,13 +316,14 @@ def _leading_header(chunk, header, state):
         pos = end
 
 
-def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names=None, places=None, header=None):
+def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names=None, places=None, header=None, edits=None):
     """SAM (paf=True: PAF) stream -> records on the MI355X (mg_sam_tokenize / mg_paf_tokenize).  A line the reference
     cannot parse is re-run through the host tokeniser so that the very same exception (type and message) surfaces.
     read_names (--read_assignments): a list that takes every chunk's read names, (bytes, offsets) from mg_sam_tokenize_named — a read that
     goes on from the chunk before is named there.
     places (--coverage): a list that takes every chunk's places (PLACE_DTYPE[], beside its records); header: a list that takes the
-    stream's leading '@' lines as the chunks pass."""
+    stream's leading '@' lines as the chunks pass.
+    edits (--identity): a list that takes every chunk's edits (EDIT_DTYPE[], beside its records)."""
     hip = _hip.Hip.get()
     hstate = {'leading': True}
     names = [None] * len(acc_index)
@@ -325,12 +336,17 @@ def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names
             if header is not None:
                 _leading_header(chunk, header, hstate)
             try:
-                if places is not None:
-                    got = hip.sam_tokenize(chunk, index, prev, paf=paf, named=read_names is not None, placed=True)
+                if places is not None or edits is not None:
+                    got = hip.sam_tokenize(chunk, index, prev, paf=paf, named=read_names is not None, placed=places is not None,
+                                           edited=edits is not None)
                     recs, prev = got[0], got[1]
                     if read_names is not None:
                         read_names.append(got[2])
-                    places.append(got[-1])
+                    if edits is not None:  # (the edits come last, the places in front of them)
+                        edits.append(got[-1])
+                        got = got[:-1]
+                    if places is not None:
+                        places.append(got[-1])
                 elif read_names is not None:
                     recs, prev, nm = hip.sam_tokenize(chunk, index, prev, paf=paf, named=True)
                     read_names.append(nm)
@@ -361,6 +377,8 @@ def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names
                     read_names.append(_pack_names(host_names))
                 if places is not None:
                     places.append(_host_places(ln.decode('utf-8') for ln in lines))
+                if edits is not None:
+                    edits.append(_host_edits(ln.decode('utf-8') for ln in lines))
             parts.append(recs)
     finally:
         index.free()
@@ -544,6 +562,44 @@ def _depth_close(args, path, lengths, dev, acc_index, acc2info, taxid2info):
     _append_depth(args, path, depth.Depth(lengths, per, unplaced, dev.window, windows), acc2info, taxid2info)
 
 
+def _wants_identity(args):
+    return _wanted(args, 'identity')
+
+
+def _identity_bytes(nacc, nrec):
+    """What --identity holds on the device: 1001 bins of 8 B and three sums per accession, 8 B of edit per record (and as much
+    again where a collation permutes them)."""
+    return 8 * (_hip.IDENTITY_BINS + 3) * nacc + 16 * nrec
+
+
+def _identity_open(hip, acc_index):
+    """--identity for one input file: the device's histograms and sums, one row per accession."""
+    try:
+        return hip.identity(len(acc_index))
+    except _hip.HipError as e:
+        if e.code != _hip.ERR_NOMEM:
+            raise
+        sys.exit('Error: --identity keeps 1001 bins of eight bytes per accession on the GPU; %d MB for this database do not fit.'
+                 % (_identity_bytes(len(acc_index), 0) >> 20))
+
+
+def _append_identity(args, path, idn, acc2info, taxid2info):
+    """One input file's block behind those of the files before it (map_main wrote the column header)."""
+    source = path if len(getattr(args, 'infiles', [])) > 1 else None
+    identity.write_identity(args.identity, identity.rows(idn, acc2info, taxid2info), idn.unscored, source=source, append=True)
+
+
+def _identity_close(args, path, dev, acc_index, acc2info, taxid2info):
+    """The device's sums and histogram rows -> the file's block."""
+    try:
+        aln, cols, eds, unscored, hist = dev.result()
+    finally:
+        dev.free()
+    names = {i: a for a, i in acc_index.items()}
+    per = {names[r]: [int(aln[r]), int(cols[r]), int(eds[r]), H] for r, H in hist.items()}
+    _append_identity(args, path, identity.Identity(per, unscored), acc2info, taxid2info)
+
+
 def assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=True):
     """Kernel outputs -> the (taxids2abs, multimapped, low_mem_mmap) triple of the reference (:193-264).
     want_lists=False leaves `multimapped` as the CSR dict for the vectorised tail (compute_abundances)."""
@@ -574,7 +630,7 @@ def assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=True):
 
 
 def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _resident=False, _paf=False, _bam=False, _collate=False,
-                         _assignments=False, _coverage=None, _depth=None):
+                         _assignments=False, _coverage=None, _depth=None, _identity=False):
     """map_and_process for a plain SAM FILE, without the text or the records ever being host arrays: the file goes up
     through page-locked chunks (Hip.upload_file), is tokenised where it lands and stage C runs on the records the
     tokeniser left in HBM.  A line the reference cannot parse makes this return None: the caller then takes the
@@ -587,9 +643,13 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
     _coverage (--coverage): the file's header lines — the batch also carries the records' places, which feed the coverage bitmap
     before stage C takes the batch, and the file's block is appended to args.coverage.
     _depth (--depth, --depth_windows): the file's header lines likewise — the same placed batch feeds the depth slots, and the
-    file's blocks are appended to args.depth / args.depth_windows."""
+    file's blocks are appended to args.depth / args.depth_windows.
+    _identity (--identity): the batch also carries the records' edits, which feed the identity histograms, and the file's block is
+    appended to args.identity.  One tokenisation carries every side array that was asked for."""
     assert not (_assignments and _collate)
     placed = _coverage is not None or _depth is not None
+    edited = bool(_identity)
+    sided = placed or edited
     acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
     _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
     hip = _hip.Hip.get()
@@ -597,13 +657,13 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
     for a, i in acc_index.items():
         names[i] = a
     index = hip.acc_index(names)
-    d_text = batch = cov_lengths = cov_dev = dep_dev = None
+    d_text = batch = cov_lengths = cov_dev = dep_dev = idn_dev = None
     try:
         # the text plus ~60 B per line of line index and tokeniser output must fit beside what is resident already:
         # otherwise straight to the streaming path (256 MB chunks), without first filling the device and failing
         free, _, pooled = hip.mem_info()
         streamed = os.environ.get('MG_NO_STREAM') != '1'
-        if placed and not streamed and _is_gzip(path):
+        if sided and not streamed and _is_gzip(path):
             streamed = True  # (the whole-text call has no inflater in front of it: a compressed file's places come from the stream)
         # (streamed: only the 16-byte records — ~1/20 of the text — and three chunks of text are ever resident)
         need = os.path.getsize(path) // 8 if streamed or _collate else 2 * os.path.getsize(path)
@@ -624,16 +684,18 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
                 need += sum(cov_lengths.values()) // 8
             if _depth is not None:  # 4 B per reference base, the histogram rows and the windows
                 need += _depth_bytes(cov_lengths, _depth_window(args), nrec)
+        if edited:
+            need += _identity_bytes(len(acc_index), os.path.getsize(path) // (50 if _bam or _is_gzip(path) else 100))
         if need > free + pooled:
             return None
         try:
-            if placed and not streamed and not _bam and not _collate:  # (one call over the whole text: the flag-taking tokeniser)
+            if sided and not streamed and not _bam and not _collate:  # (one call over the whole text: the flag-taking tokeniser)
                 d_text, size = hip.upload_file(path)
-                batch = hip.sam_tokenize_dev_batch(d_text.ptr, size, index, '', named=_assignments, placed=True)
-            elif placed:
+                batch = hip.sam_tokenize_dev_batch(d_text.ptr, size, index, '', named=_assignments, placed=placed, edited=edited)
+            elif sided:
                 stream = hip.bam_stream_file if _bam else hip.sam_stream_file
                 batch = stream(path, index, chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)), collate=_collate,
-                               named=_assignments, placed=True)
+                               named=_assignments, placed=placed, edited=edited)
             elif _bam:  # (a BAM is always streamed: ~16 B of records per ~60 B of the compressed file stay resident)
                 batch = hip.bam_stream_file(path, index, chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)), collate=_collate,
                                             named=_assignments)
@@ -663,6 +725,9 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
         if _depth is not None:
             dep_dev = _depth_open(args, hip, cov_lengths, acc_index)
             dep_dev.add_batch(batch, float(args.pct_id))
+        if edited:
+            idn_dev = _identity_open(hip, acc_index)
+            idn_dev.add_batch(batch, float(args.pct_id))
         res = hip.profile_assign_dev_records(batch.ptr, batch.count, ref2tax, len(taxids), float(args.pct_id), [batch],
                                              resident=_resident, assign=_assignments)
         batch = None  # owned by the result now
@@ -671,6 +736,8 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
             cov_dev.free()
         if dep_dev is not None:
             dep_dev.free()
+        if idn_dev is not None:
+            idn_dev.free()
         raise
     finally:
         index.free()
@@ -680,6 +747,8 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
         _coverage_close(args, path, cov_lengths, cov_dev, acc_index, acc2info, taxid2info)
     if dep_dev is not None:
         _depth_close(args, path, cov_lengths, dep_dev, acc_index, acc2info, taxid2info)
+    if idn_dev is not None:
+        _identity_close(args, path, idn_dev, acc_index, acc2info, taxid2info)
     if _assignments:
         _append_assignments(args, assignment_rows(res, taxids))
     if not _want_lists:
@@ -872,18 +941,21 @@ class _CudaWords:
 
 
 def map_and_process(args, instream, acc2info, taxid2info, _assign=None, _want_lists=True, _resident=False, _assignments=False,
-                    _coverage=None, _depth=None):
+                    _coverage=None, _depth=None, _identity=None):
     """Reference signature (:193).  `_assign` is a test seam; product code never passes it.
     _assignments (--read_assignments): every chunk's read names are collected beside its records, stage C runs over the records
     uploaded as one array with the verdict words written, and the rows are appended to args.read_assignments.
     _coverage (--coverage): the name the block is written under — every chunk's places are collected beside its records, the
     lengths come from the leading '@' lines of the stream, and places and records go up together for the coverage kernels.
-    _depth (--depth, --depth_windows): the name its blocks are written under, likewise — the same places feed the depth kernels."""
+    _depth (--depth, --depth_windows): the name its blocks are written under, likewise — the same places feed the depth kernels.
+    _identity (--identity): the name its block is written under — every chunk's edits are collected beside its records and go up
+    with them for the identity kernel."""
     acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
-    if _coverage is not None or _depth is not None:
+    if _coverage is not None or _depth is not None or _identity is not None:
         if _assign is not None:
-            raise ValueError('--coverage and --depth need the device path')
-        return _map_and_process_covered(args, instream, acc2info, taxid2info, _want_lists, _resident, _assignments, _coverage, _depth)
+            raise ValueError('--coverage, --depth and --identity need the device path')
+        return _map_and_process_covered(args, instream, acc2info, taxid2info, _want_lists, _resident, _assignments, _coverage, _depth,
+                                        _identity)
     _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
     # test seam: an injected record-level backend is fed by the host tokeniser; product code never passes one
     tokenise = _device_tokenise if _assign is None else tokenise_sam
@@ -911,41 +983,60 @@ def map_and_process(args, instream, acc2info, taxid2info, _assign=None, _want_li
     return assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=_want_lists)
 
 
-def _map_and_process_covered(args, instream, acc2info, taxid2info, _want_lists, _resident, _assignments, source, depth_source=None):
-    """map_and_process with --coverage (source) and / or --depth, --depth_windows (depth_source), and --read_assignments where that
-    is on."""
+def _map_and_process_covered(args, instream, acc2info, taxid2info, _want_lists, _resident, _assignments, source, depth_source=None,
+                             identity_source=None):
+    """map_and_process with --coverage (source), --depth / --depth_windows (depth_source) and / or --identity (identity_source), and
+    --read_assignments where that is on."""
     acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
     _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
-    names, places, header = ([] if _assignments else None), [], []
-    recs = _device_tokenise(instream, acc_index, decode=(args.input_type != 'sam'), read_names=names, places=places, header=header)
+    want_places = source is not None or depth_source is not None
+    names, places, header = ([] if _assignments else None), ([] if want_places else None), []
+    edits = [] if identity_source is not None else None
+    recs = _device_tokenise(instream, acc_index, decode=(args.input_type != 'sam'), read_names=names, places=places, header=header,
+                            edits=edits)
     place = np.concatenate(places) if places else np.zeros(0, dtype=_hip.PLACE_DTYPE)
-    assert len(place) == len(recs)
+    edit = np.concatenate(edits) if edits else np.zeros(0, dtype=_hip.EDIT_DTYPE)
+    assert not want_places or len(place) == len(recs)
+    assert edits is None or len(edit) == len(recs)
     hip = _hip.Hip.get()
     d_recs = hip.array(recs if len(recs) else np.zeros(1, _hip.REC_DTYPE))
     try:
         lengths = coverage.lengths_of(header, acc2info)
-        devs = []
+        devs, idn_dev = [], None
         try:
             if source is not None:
                 devs.append(_coverage_open(hip, lengths, acc_index))
             if depth_source is not None:
                 devs.append(_depth_open(args, hip, lengths, acc_index))
+            if identity_source is not None:
+                idn_dev = _identity_open(hip, acc_index)
             if len(recs):
-                d_place = hip.array(place.view(np.uint8))
+                d_place = hip.array(place.view(np.uint8)) if want_places else None
+                d_edit = None
                 try:
+                    d_edit = hip.array(edit.view(np.uint8)) if idn_dev is not None else None
                     for dev in devs:
                         dev.add_ptr(d_recs.ptr, d_place.ptr, len(recs), float(args.pct_id))
+                    if idn_dev is not None:
+                        idn_dev.add_ptr(d_recs.ptr, d_edit.ptr, len(recs), float(args.pct_id))
                     hip.sync()
                 finally:
-                    d_place.free()
+                    if d_place is not None:
+                        d_place.free()
+                    if d_edit is not None:
+                        d_edit.free()
         except BaseException:
             for dev in devs:
                 dev.free()
+            if idn_dev is not None:
+                idn_dev.free()
             raise
         if source is not None:
             _coverage_close(args, source, lengths, devs[0], acc_index, acc2info, taxid2info)
         if depth_source is not None:  # (should the first close raise, this handle goes with the process)
             _depth_close(args, depth_source, lengths, devs[-1], acc_index, acc2info, taxid2info)
+        if idn_dev is not None:
+            _identity_close(args, identity_source, idn_dev, acc_index, acc2info, taxid2info)
     except BaseException:
         d_recs.free()  # (stage C has not taken the records over yet)
         raise
@@ -1160,13 +1251,16 @@ def compute_abundances(args, infile, acc2info, tax2info):
         raise ValueError('--coverage needs the device path')
     if want_dep and not seams_untouched:
         raise ValueError('--depth needs the device path')
+    want_idn = _wants_identity(args)
+    if want_idn and not seams_untouched:
+        raise ValueError('--identity needs the device path')
     if args.input_type == 'sam' and not paf and bam.is_bam(infile):  # decided per file: a BAM is never SAM text
         instream.close()
         return _compute_abundances_bam(args, infile, acc2info, tax2info, on_device, seams_untouched)
     if args.input_type == 'sam' and not paf and _wants_collation(args, lambda: _sam_header_lines(infile)):
         instream.close()
         return _compute_abundances_collated(args, infile, acc2info, tax2info, on_device, seams_untouched)
-    if args.input_type == 'sam' and seams_untouched and not paf and not want_rows and not want_cov and not want_dep:
+    if args.input_type == 'sam' and seams_untouched and not paf and not want_rows and not want_cov and not want_dep and not want_idn:
         from .select_db import dist_context
         ctx = dist_context()
         if ctx is not None:  # one process per GPU: the ranks tokenise the text between them, rank 0 does the rest
@@ -1179,11 +1273,11 @@ def compute_abundances(args, infile, acc2info, tax2info):
         # a plain file (SAM, or a PAF replay): all the way on the device
         done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _paf=paf,
                                     _assignments=want_rows, _coverage=_sam_header_lines(infile) if want_cov else None,
-                                    _depth=_sam_header_lines(infile) if want_dep else None)
+                                    _depth=_sam_header_lines(infile) if want_dep else None, _identity=want_idn)
     if done is None:
         done = map_and_process(args, instream, acc2info, tax2info, _want_lists=False, _resident=on_device,
                                _assignments=want_rows and seams_untouched, _coverage=infile if want_cov else None,
-                               _depth=infile if want_dep else None)
+                               _depth=infile if want_dep else None, _identity=infile if want_idn else None)
     taxids2abs, mm, low_mem_mmap = done
     if args.input_type == 'sam':
         instream.close()
@@ -1238,10 +1332,11 @@ def _compute_abundances_collated(args, infile, acc2info, tax2info, on_device, se
     done = None
     want_cov = _wants_coverage(args) and seams_untouched
     want_dep = _wants_depth(args) and seams_untouched
+    want_idn = _wants_identity(args) and seams_untouched
     if seams_untouched:
         done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _collate=True,
                                     _coverage=_sam_header_lines(infile) if want_cov else None,
-                                    _depth=_sam_header_lines(infile) if want_dep else None)
+                                    _depth=_sam_header_lines(infile) if want_dep else None, _identity=want_idn)
     if done is None:
         done = map_and_process(args, collate.collated_lines(_sam_file_lines(infile)), acc2info, tax2info, _want_lists=False,
                                _resident=on_device)
@@ -1249,6 +1344,8 @@ def _compute_abundances_collated(args, infile, acc2info, tax2info, on_device, se
             _append_coverage(args, infile, coverage.coverage(_sam_file_lines(infile), acc2info, args.pct_id), acc2info, tax2info)
         if want_dep:  # (likewise)
             _append_depth(args, infile, depth.depth(_sam_file_lines(infile), acc2info, args.pct_id, _depth_window(args)), acc2info, tax2info)
+        if want_idn:  # (likewise)
+            _append_identity(args, infile, identity.identity(_sam_file_lines(infile), acc2info, args.pct_id), acc2info, tax2info)
     if _wants_assignments(args):  # (a named batch is not collated: the rows of a collated input come from the definition)
         _append_assignments(args, assignments.read_assignments(collate.collated_lines(_sam_file_lines(infile)), acc2info, args.pct_id))
     taxids2abs, mm, _ = done
@@ -1267,22 +1364,26 @@ def _compute_abundances_bam(args, infile, acc2info, tax2info, on_device, seams_u
     want_rows = _wants_assignments(args)
     want_cov = _wants_coverage(args) and seams_untouched
     want_dep = _wants_depth(args) and seams_untouched
+    want_idn = _wants_identity(args) and seams_untouched
     if seams_untouched:
         # (the reference list's l_ref equals the header's @SQ text: the text is what gives the lengths)
         done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _bam=True,
                                     _collate=collating, _assignments=want_rows and not collating,
                                     _coverage=_bam_header_lines(infile) if want_cov else None,
-                                    _depth=_bam_header_lines(infile) if want_dep else None)
+                                    _depth=_bam_header_lines(infile) if want_dep else None, _identity=want_idn)
     if done is None:
         lines = bam.sam_lines(infile)
         done = map_and_process(args, collate.collated_lines(lines) if collating else lines, acc2info, tax2info, _want_lists=False,
                                _resident=on_device, _assignments=want_rows and not collating and seams_untouched,
                                _coverage=infile if want_cov and not collating else None,
-                               _depth=infile if want_dep and not collating else None)
+                               _depth=infile if want_dep and not collating else None,
+                               _identity=infile if want_idn and not collating else None)
         if want_cov and collating:
             _append_coverage(args, infile, coverage.coverage(bam.sam_lines(infile), acc2info, args.pct_id), acc2info, tax2info)
         if want_dep and collating:
             _append_depth(args, infile, depth.depth(bam.sam_lines(infile), acc2info, args.pct_id, _depth_window(args)), acc2info, tax2info)
+        if want_idn and collating:
+            _append_identity(args, infile, identity.identity(bam.sam_lines(infile), acc2info, args.pct_id), acc2info, tax2info)
     if want_rows and collating:  # (as a collated SAM file: the definition over the regrouped lines)
         _append_assignments(args, assignments.read_assignments(collate.collated_lines(bam.sam_lines(infile)), acc2info, args.pct_id))
     taxids2abs, mm, _ = done
@@ -1387,6 +1488,10 @@ def map_main(args=None):
         sys.exit('Error: --depth and --depth_windows run in one process on one GPU; start it without torch.distributed.run.')
     if _wants_depth(args) and (getattr(args, 'paf_input', False) or any(f.endswith('.paf') for f in args.infiles)):
         sys.exit('Error: --depth and --depth_windows need SAM or BAM alignments: a PAF line has no POS and CIGAR columns.')
+    if _wants_identity(args) and int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        sys.exit('Error: --identity runs in one process on one GPU; start it without torch.distributed.run.')
+    if _wants_identity(args) and (getattr(args, 'paf_input', False) or any(f.endswith('.paf') for f in args.infiles)):
+        sys.exit('Error: --identity needs SAM or BAM alignments: the NM:i: and cg:Z: tags of a PAF line are not read.')
     if int(getattr(args, 'depth_window_size', 1000)) < 1:
         sys.exit('Error: --depth_window_size must be at least 1.')
     check_multimap_flags(args)
@@ -1415,6 +1520,8 @@ def map_main(args=None):
             depth.write_depth(args.depth)  # likewise
         if _wanted(args, 'depth_windows'):
             depth.write_windows(args.depth_windows)
+        if _wants_identity(args):
+            identity.write_identity(args.identity)
     acc2info, taxid2info = get_acc2info(args)
     rank_results = gather_results(args, acc2info, taxid2info)
     if not getattr(args, '_not_root', False):

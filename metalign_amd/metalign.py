@@ -60,6 +60,8 @@ def main(argv=None):
     mapper.check_multimap_flags(args)
     if (args.depth != 'NONE' or args.depth_windows != 'NONE') and int(os.environ.get('WORLD_SIZE', '1')) > 1:
         sys.exit('Error: --depth and --depth_windows run in one process on one GPU; start it without torch.distributed.run.')
+    if args.identity != 'NONE' and int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        sys.exit('Error: --identity runs in one process on one GPU; start it without torch.distributed.run.')
     if args.depth_window_size < 1:
         sys.exit('Error: --depth_window_size must be at least 1.')
     args.data = cli.with_slash(args.data)
