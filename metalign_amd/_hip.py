@@ -1084,9 +1084,49 @@ class SamBatch:
             self.handle = None
 
 
-class Coverage:
+class _SideAccumulator:
+    """What Coverage, Depth and IdentityAcc share: a handle that takes records beside one side array of their batch.  _add / _free: the
+    library functions; _side_ptr: the SamBatch pointer that holds the side array; _side_dtype: its host form."""
+    _add = _free = _side_ptr = _side_dtype = None
+
+    def add_ptr(self, d_recs, d_side, n, pct_id):
+        """n records and their side array at device pointers (asynchronous; the arrays must outlive the next synchronisation).  n = 0
+        is still a call: the library answers ERR_STATE where the handle takes no more."""
+        self.hip._chk(getattr(self.hip.lib, self._add)(self.handle, _vp(d_recs), _vp(d_side), ctypes.c_uint64(int(n)),
+                                                       ctypes.c_double(float(pct_id))))
+
+    def add_batch(self, batch, pct_id):
+        """A SamBatch that carries the side array (tokenised with placed / edited)."""
+        if batch.count:
+            self.add_ptr(batch.ptr, getattr(batch, self._side_ptr), batch.count, pct_id)
+            self.hip.sync()
+
+    def add(self, recs, side, pct_id):
+        """Host arrays REC_DTYPE[n] and _side_dtype[n]."""
+        recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
+        side = np.ascontiguousarray(side, dtype=self._side_dtype)
+        assert len(recs) == len(side)
+        if not len(recs):
+            self.add_ptr(None, None, 0, pct_id)
+            return
+        d_r, d_s = self.hip.array(recs.view(np.uint8)), self.hip.array(side.view(np.uint8))
+        try:
+            self.add_ptr(d_r.ptr, d_s.ptr, len(recs), pct_id)
+            self.hip.sync()
+        finally:
+            d_r.free()
+            d_s.free()
+
+    def free(self):
+        if self.handle:
+            getattr(self.hip.lib, self._free)(self.handle)
+            self.handle = None
+
+
+class Coverage(_SideAccumulator):
     """One bit per reference base on the device and the per-accession sums (mg_coverage_*; metalign_amd/coverage.py is the
     definition).  lengths: one per accession row.  HipError with code ERR_NOMEM when the bitmap does not fit."""
+    _add, _free, _side_ptr, _side_dtype = "mg_coverage_add_dev", "mg_coverage_free", "places_ptr", PLACE_DTYPE
 
     def __init__(self, hip, lengths):
         self.hip = hip
@@ -1097,32 +1137,6 @@ class Coverage:
                                             ctypes.byref(h)))
         self.handle = h
 
-    def add_ptr(self, d_recs, d_places, n, pct_id):
-        """n records and their places at device pointers (asynchronous; the arrays must outlive the next synchronisation)."""
-        self.hip._chk(self.hip.lib.mg_coverage_add_dev(self.handle, _vp(d_recs), _vp(d_places), ctypes.c_uint64(int(n)),
-                                                       ctypes.c_double(float(pct_id))))
-
-    def add_batch(self, batch, pct_id):
-        """A placed SamBatch."""
-        if batch.count:
-            self.add_ptr(batch.ptr, batch.places_ptr, batch.count, pct_id)
-            self.hip.sync()
-
-    def add(self, recs, places, pct_id):
-        """Host arrays REC_DTYPE[n], PLACE_DTYPE[n]."""
-        recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
-        places = np.ascontiguousarray(places, dtype=PLACE_DTYPE)
-        assert len(recs) == len(places)
-        if not len(recs):
-            return
-        d_r, d_p = self.hip.array(recs.view(np.uint8)), self.hip.array(places.view(np.uint8))
-        try:
-            self.add_ptr(d_r.ptr, d_p.ptr, len(recs), pct_id)
-            self.hip.sync()
-        finally:
-            d_r.free()
-            d_p.free()
-
     def result(self):
         """-> (alignments, aligned_bases, covered_bases) uint64[nacc] each, unplaced."""
         out = [np.zeros(max(self.nacc, 1), dtype=np.uint64) for _ in range(3)]
@@ -1130,15 +1144,11 @@ class Coverage:
         self.hip._chk(self.hip.lib.mg_coverage_result(self.handle, *[_np(a, ctypes.c_uint64) for a in out], ctypes.byref(unplaced)))
         return tuple(a[:self.nacc] for a in out) + (int(unplaced.value),)
 
-    def free(self):
-        if self.handle:
-            self.hip.lib.mg_coverage_free(self.handle)
-            self.handle = None
 
-
-class IdentityAcc:
+class IdentityAcc(_SideAccumulator):
     """Per accession the scored alignments, their columns and edits and a histogram of 1001 identity bins on the device
     (mg_identity_*; metalign_amd/identity.py is the definition).  HipError with code ERR_NOMEM when they do not fit."""
+    _add, _free, _side_ptr, _side_dtype = "mg_identity_add_dev", "mg_identity_free", "edits_ptr", EDIT_DTYPE
 
     def __init__(self, hip, nacc):
         self.hip = hip
@@ -1146,33 +1156,6 @@ class IdentityAcc:
         h = _vp()
         hip._chk(hip.lib.mg_identity_create(ctypes.c_uint32(self.nacc), ctypes.byref(h)))
         self.handle = h
-
-    def add_ptr(self, d_recs, d_edits, n, pct_id):
-        """n records and their edits at device pointers (asynchronous; the arrays must outlive the next synchronisation)."""
-        self.hip._chk(self.hip.lib.mg_identity_add_dev(self.handle, _vp(d_recs), _vp(d_edits), ctypes.c_uint64(int(n)),
-                                                       ctypes.c_double(float(pct_id))))
-
-    def add_batch(self, batch, pct_id):
-        """A SamBatch tokenised with edited=True."""
-        if batch.count:
-            self.add_ptr(batch.ptr, batch.edits_ptr, batch.count, pct_id)
-            self.hip.sync()
-
-    def add(self, recs, edits, pct_id):
-        """Host arrays REC_DTYPE[n], EDIT_DTYPE[n]."""
-        recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
-        edits = np.ascontiguousarray(edits, dtype=EDIT_DTYPE)
-        assert len(recs) == len(edits)
-        if not len(recs):
-            self.add_ptr(None, None, 0, pct_id)
-            return
-        d_r, d_e = self.hip.array(recs.view(np.uint8)), self.hip.array(edits.view(np.uint8))
-        try:
-            self.add_ptr(d_r.ptr, d_e.ptr, len(recs), pct_id)
-            self.hip.sync()
-        finally:
-            d_r.free()
-            d_e.free()
 
     def sums(self):
         """-> (alignments, columns, edits) uint64[nacc] each, unscored (mg_identity_result)."""
@@ -1201,16 +1184,12 @@ class IdentityAcc:
             per[a] = dict(zip(nz.tolist(), H[r][nz].tolist()))
         return aln, cols, eds, unscored, per
 
-    def free(self):
-        if self.handle:
-            self.hip.lib.mg_identity_free(self.handle)
-            self.handle = None
 
-
-class Depth:
+class Depth(_SideAccumulator):
     """One int32 slot per reference base (and one per accession) on the device: per-base depth as a histogram per accession and as
     windows of `window` bases (mg_depth_*; metalign_amd/depth.py is the definition).  lengths: one per accession row; window = 0:
     no windows.  HipError with code ERR_NOMEM when the slots do not fit, ERR_STATE for an add after finish()."""
+    _add, _free, _side_ptr, _side_dtype = "mg_depth_add_dev", "mg_depth_free", "places_ptr", PLACE_DTYPE
 
     def __init__(self, hip, lengths, window=0):
         self.hip = hip
@@ -1220,33 +1199,6 @@ class Depth:
         hip._chk(hip.lib.mg_depth_create(_np(ln if ln.size else np.zeros(1, np.uint64), ctypes.c_uint64), ctypes.c_uint32(self.nacc),
                                          ctypes.c_uint32(self.window), ctypes.byref(h)))
         self.handle = h
-
-    def add_ptr(self, d_recs, d_places, n, pct_id):
-        """n records and their places at device pointers (asynchronous; the arrays must outlive the next synchronisation)."""
-        self.hip._chk(self.hip.lib.mg_depth_add_dev(self.handle, _vp(d_recs), _vp(d_places), ctypes.c_uint64(int(n)),
-                                                    ctypes.c_double(float(pct_id))))
-
-    def add_batch(self, batch, pct_id):
-        """A placed SamBatch."""
-        if batch.count:
-            self.add_ptr(batch.ptr, batch.places_ptr, batch.count, pct_id)
-            self.hip.sync()
-
-    def add(self, recs, places, pct_id):
-        """Host arrays REC_DTYPE[n], PLACE_DTYPE[n]."""
-        recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
-        places = np.ascontiguousarray(places, dtype=PLACE_DTYPE)
-        assert len(recs) == len(places)
-        if not len(recs):
-            self.add_ptr(None, None, 0, pct_id)  # (ERR_STATE after finish, whatever the count)
-            return
-        d_r, d_p = self.hip.array(recs.view(np.uint8)), self.hip.array(places.view(np.uint8))
-        try:
-            self.add_ptr(d_r.ptr, d_p.ptr, len(recs), pct_id)
-            self.hip.sync()
-        finally:
-            d_r.free()
-            d_p.free()
 
     def finish(self):
         """The scan and the histogram / window passes (mg_depth_finish) -> (alignments uint64[nacc], unplaced, nrows, nwindows)."""
@@ -1284,11 +1236,6 @@ class Depth:
         for a, j, s, c in zip(win["acc"].tolist(), win["index"].tolist(), win["depth_sum"].tolist(), win["covered"].tolist()):
             windows.setdefault(a, []).append((j, s, c))
         return aln, unplaced, per, windows
-
-    def free(self):
-        if self.handle:
-            self.hip.lib.mg_depth_free(self.handle)
-            self.handle = None
 
 
 class ResidentProfile:

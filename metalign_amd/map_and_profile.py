@@ -29,7 +29,8 @@ import time
 
 import numpy as np
 
-from . import _hip, assignments, bam, cli, collate, coverage, depth, identity
+from . import _hip, assignments, bam, cli, collate, coverage, identity
+from .side_outputs import ASSIGNMENTS, COVERAGE, DEPTH, IDENTITY, FAMILIES, SideOutputs, check_flags, write_headers
 
 start = time.time()
 RANKS = ['superkingdom', 'phylum', 'class', 'order', 'family', 'genus', 'species', 'strain']
@@ -274,24 +275,15 @@ def _join_names(parts):
     return b''.join(blobs), np.concatenate(offs)
 
 
-def _host_places(lines):
-    """The places of the lines the host tokeniser retains (coverage.placement), PLACE_DTYPE[] in record order."""
+def _host_side(lines, of, dtype):
+    """A side array of the lines the host tokeniser retains, dtype[] in record order; of: a retained line's fields -> its entry
+    (coverage.placement for the places, identity.edit_of for the edits)."""
     out = []
     for ln in lines:
         f = coverage.retained_fields(ln)
         if f is not None:
-            out.append(coverage.placement(f))
-    return np.array(out, dtype=_hip.PLACE_DTYPE) if out else np.zeros(0, dtype=_hip.PLACE_DTYPE)
-
-
-def _host_edits(lines):
-    """The edits of the lines the host tokeniser retains (identity.edit_of), EDIT_DTYPE[] in record order."""
-    out = []
-    for ln in lines:
-        f = coverage.retained_fields(ln)
-        if f is not None:
-            out.append(identity.edit_of(f))
-    return np.array(out, dtype=_hip.EDIT_DTYPE) if out else np.zeros(0, dtype=_hip.EDIT_DTYPE)
+            out.append(of(f))
+    return np.array(out, dtype=dtype) if out else np.zeros(0, dtype=dtype)
 
 
 def _leading_header(chunk, header, state):
@@ -316,6 +308,14 @@ def _leading_header(chunk, header, state):
         pos = end
 
 
+def _acc_index_of(hip, acc_index):
+    """{accession: row} -> the device's index of the names, row by row (Hip.acc_index)."""
+    names = [None] * len(acc_index)
+    for a, i in acc_index.items():
+        names[i] = a
+    return hip.acc_index(names)
+
+
 def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names=None, places=None, header=None, edits=None):
     """SAM (paf=True: PAF) stream -> records on the MI355X (mg_sam_tokenize / mg_paf_tokenize).  A line the reference
     cannot parse is re-run through the host tokeniser so that the very same exception (type and message) surfaces.
@@ -326,32 +326,18 @@ def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names
     edits (--identity): a list that takes every chunk's edits (EDIT_DTYPE[], beside its records)."""
     hip = _hip.Hip.get()
     hstate = {'leading': True}
-    names = [None] * len(acc_index)
-    for a, i in acc_index.items():
-        names[i] = a
-    index = hip.acc_index(names)
+    index = _acc_index_of(hip, acc_index)
     parts, prev = [], ''
     try:
         for chunk in _line_chunks(instream, decode):
             if header is not None:
                 _leading_header(chunk, header, hstate)
             try:
-                if places is not None or edits is not None:
-                    got = hip.sam_tokenize(chunk, index, prev, paf=paf, named=read_names is not None, placed=places is not None,
-                                           edited=edits is not None)
-                    recs, prev = got[0], got[1]
-                    if read_names is not None:
-                        read_names.append(got[2])
-                    if edits is not None:  # (the edits come last, the places in front of them)
-                        edits.append(got[-1])
-                        got = got[:-1]
-                    if places is not None:
-                        places.append(got[-1])
-                elif read_names is not None:
-                    recs, prev, nm = hip.sam_tokenize(chunk, index, prev, paf=paf, named=True)
-                    read_names.append(nm)
-                else:
-                    recs, prev = hip.sam_tokenize(chunk, index, prev, paf=paf)
+                # -> records, last QNAME, then what was asked for: the names, the places, the edits, in that order
+                recs, prev, *sides = hip.sam_tokenize(chunk, index, prev, paf=paf, named=read_names is not None,
+                                                      placed=places is not None, edited=edits is not None)
+                for into, got in zip([x for x in (read_names, places, edits) if x is not None], sides):
+                    into.append(got)
             except _hip.SamParseError as e:
                 lines = bytes(chunk).split(b'\n')
                 bad = lines[e.line].decode('utf-8', 'replace')
@@ -376,9 +362,9 @@ def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names
                 if read_names is not None:
                     read_names.append(_pack_names(host_names))
                 if places is not None:
-                    places.append(_host_places(ln.decode('utf-8') for ln in lines))
+                    places.append(_host_side((ln.decode('utf-8') for ln in lines), coverage.placement, _hip.PLACE_DTYPE))
                 if edits is not None:
-                    edits.append(_host_edits(ln.decode('utf-8') for ln in lines))
+                    edits.append(_host_side((ln.decode('utf-8') for ln in lines), identity.edit_of, _hip.EDIT_DTYPE))
             parts.append(recs)
     finally:
         index.free()
@@ -402,10 +388,7 @@ def tokenise_bam_device(path, acc_index, chunk_bytes=0):
     """BAM file -> records on the MI355X (mg_bam_stream_file).  A record the device does not decide, or a file it refuses: the
     file's SAM rendering (bam.sam_lines) through tokenise_sam_device, which raises what the reference raises on that line."""
     hip = _hip.Hip.get()
-    names = [None] * len(acc_index)
-    for a, i in acc_index.items():
-        names[i] = a
-    index = hip.acc_index(names)
+    index = _acc_index_of(hip, acc_index)
     batch = None
     try:
         try:
@@ -472,134 +455,6 @@ def _append_assignments(args, rows):
     assignments.write_assignments(args.read_assignments, rows, append=True)
 
 
-def _wants_coverage(args):
-    return getattr(args, 'coverage', 'NONE') not in (None, 'NONE')  # (callers build Namespaces without it)
-
-
-def _coverage_open(hip, lengths, acc_index):
-    """--coverage for one input file: the device's bitmap over its lengths (coverage.lengths_of: the file's @SQ lines over db_info's)."""
-    arr = np.zeros(len(acc_index), dtype=np.uint64)
-    for a, i in acc_index.items():
-        arr[i] = lengths[a]
-    try:
-        return hip.coverage(arr)
-    except _hip.HipError as e:
-        if e.code != _hip.ERR_NOMEM:
-            raise
-        sys.exit('Error: --coverage keeps one bit per reference base on the GPU; %d MB for this database do not fit.'
-                 % (int(arr.sum()) >> 23))
-
-
-def _append_coverage(args, path, cov, acc2info, taxid2info):
-    """One input file's block behind those of the files before it (map_main wrote the column header)."""
-    source = path if len(getattr(args, 'infiles', [])) > 1 else None
-    coverage.write_coverage(args.coverage, coverage.rows(cov, acc2info, taxid2info), cov.unplaced, source=source, append=True)
-
-
-def _coverage_close(args, path, lengths, dev, acc_index, acc2info, taxid2info):
-    """The device's sums -> the file's block."""
-    try:
-        aln, bases, covered, unplaced = dev.result()
-    finally:
-        dev.free()
-    per = {a: [int(aln[i]), int(bases[i]), int(covered[i])] for a, i in acc_index.items() if aln[i]}
-    _append_coverage(args, path, coverage.Coverage(lengths, per, unplaced), acc2info, taxid2info)
-
-
-def _wanted(args, name):
-    return getattr(args, name, 'NONE') not in (None, 'NONE')  # (callers build Namespaces without it)
-
-
-def _wants_depth(args):
-    """--depth or --depth_windows: either one asks for the per-base depth."""
-    return _wanted(args, 'depth') or _wanted(args, 'depth_windows')
-
-
-def _depth_window(args):
-    return int(getattr(args, 'depth_window_size', 1000)) if _wanted(args, 'depth_windows') else 0
-
-
-def _depth_bytes(lengths, window, nrec):
-    """What a Depth holds on the device: 4 B per reference base and accession, 12 B per window, a 32 KB histogram row per
-    accession that is hit (at most one per record)."""
-    total, nacc = sum(lengths.values()), len(lengths)
-    nwin = sum((n + window - 1) // window for n in lengths.values()) if window else 0
-    return 4 * (total + nacc) + 12 * nwin + 8 * _hip.DEPTH_BINS * min(nacc, nrec)
-
-
-def _depth_open(args, hip, lengths, acc_index):
-    """--depth / --depth_windows for one input file: the device's slots over its lengths (those of --coverage)."""
-    arr = np.zeros(len(acc_index), dtype=np.uint64)
-    for a, i in acc_index.items():
-        arr[i] = lengths[a]
-    try:
-        return hip.depth(arr, _depth_window(args))
-    except _hip.HipError as e:
-        if e.code != _hip.ERR_NOMEM:
-            raise
-        sys.exit('Error: --depth keeps four bytes per reference base on the GPU; %d MB for this database do not fit.'
-                 % (_depth_bytes(lengths, _depth_window(args), 0) >> 20))
-
-
-def _append_depth(args, path, dep, acc2info, taxid2info):
-    """One input file's blocks behind those of the files before it (map_main wrote the column headers)."""
-    source = path if len(getattr(args, 'infiles', [])) > 1 else None
-    if _wanted(args, 'depth'):
-        depth.write_depth(args.depth, depth.rows(dep, acc2info, taxid2info), dep.unplaced, source=source, append=True)
-    if _wanted(args, 'depth_windows'):
-        depth.write_windows(args.depth_windows, depth.window_rows(dep, acc2info), source=source, append=True)
-
-
-def _depth_close(args, path, lengths, dev, acc_index, acc2info, taxid2info):
-    """The device's histogram rows and windows -> the file's blocks."""
-    try:
-        aln, unplaced, hist, win = dev.result()
-    finally:
-        dev.free()
-    names = {i: a for a, i in acc_index.items()}
-    per = {names[r]: [int(aln[r]), H] for r, H in hist.items()}
-    windows = {names[r]: w for r, w in win.items()}
-    _append_depth(args, path, depth.Depth(lengths, per, unplaced, dev.window, windows), acc2info, taxid2info)
-
-
-def _wants_identity(args):
-    return _wanted(args, 'identity')
-
-
-def _identity_bytes(nacc, nrec):
-    """What --identity holds on the device: 1001 bins of 8 B and three sums per accession, 8 B of edit per record (and as much
-    again where a collation permutes them)."""
-    return 8 * (_hip.IDENTITY_BINS + 3) * nacc + 16 * nrec
-
-
-def _identity_open(hip, acc_index):
-    """--identity for one input file: the device's histograms and sums, one row per accession."""
-    try:
-        return hip.identity(len(acc_index))
-    except _hip.HipError as e:
-        if e.code != _hip.ERR_NOMEM:
-            raise
-        sys.exit('Error: --identity keeps 1001 bins of eight bytes per accession on the GPU; %d MB for this database do not fit.'
-                 % (_identity_bytes(len(acc_index), 0) >> 20))
-
-
-def _append_identity(args, path, idn, acc2info, taxid2info):
-    """One input file's block behind those of the files before it (map_main wrote the column header)."""
-    source = path if len(getattr(args, 'infiles', [])) > 1 else None
-    identity.write_identity(args.identity, identity.rows(idn, acc2info, taxid2info), idn.unscored, source=source, append=True)
-
-
-def _identity_close(args, path, dev, acc_index, acc2info, taxid2info):
-    """The device's sums and histogram rows -> the file's block."""
-    try:
-        aln, cols, eds, unscored, hist = dev.result()
-    finally:
-        dev.free()
-    names = {i: a for a, i in acc_index.items()}
-    per = {names[r]: [int(aln[r]), int(cols[r]), int(eds[r]), H] for r, H in hist.items()}
-    _append_identity(args, path, identity.Identity(per, unscored), acc2info, taxid2info)
-
-
 def assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=True):
     """Kernel outputs -> the (taxids2abs, multimapped, low_mem_mmap) triple of the reference (:193-264).
     want_lists=False leaves `multimapped` as the CSR dict for the vectorised tail (compute_abundances)."""
@@ -630,7 +485,7 @@ def assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=True):
 
 
 def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _resident=False, _paf=False, _bam=False, _collate=False,
-                         _assignments=False, _coverage=None, _depth=None, _identity=False):
+                         _assignments=False, _sides=None):
     """map_and_process for a plain SAM FILE, without the text or the records ever being host arrays: the file goes up
     through page-locked chunks (Hip.upload_file), is tokenised where it lands and stage C runs on the records the
     tokeniser left in HBM.  A line the reference cannot parse makes this return None: the caller then takes the
@@ -640,74 +495,55 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
     collate.collated_lines, which the caller falls back to on None).
     _assignments (--read_assignments): the tokeniser also keeps the reads' names, stage C also writes every read's verdict and the rows
     are appended to args.read_assignments; never together with _collate (a named batch is not collated).
-    _coverage (--coverage): the file's header lines — the batch also carries the records' places, which feed the coverage bitmap
-    before stage C takes the batch, and the file's block is appended to args.coverage.
-    _depth (--depth, --depth_windows): the file's header lines likewise — the same placed batch feeds the depth slots, and the
-    file's blocks are appended to args.depth / args.depth_windows.
-    _identity (--identity): the batch also carries the records' edits, which feed the identity histograms, and the file's block is
-    appended to args.identity.  One tokenisation carries every side array that was asked for."""
+    _sides (a SideOutputs: --coverage, --depth / --depth_windows, --identity): the batch also carries the side arrays its families
+    read — the records' places, their edits — which feed the accumulators before stage C takes the batch; the file's blocks are
+    appended to the outputs.  Its header lines give the lengths.  One tokenisation carries every side array that was asked for."""
     assert not (_assignments and _collate)
-    placed = _coverage is not None or _depth is not None
-    edited = bool(_identity)
-    sided = placed or edited
+    sides = _sides if _sides is not None else SideOutputs(args, (), path)
+    assert not (sides and _paf)  # (check_flags refuses the pair)
     acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
     _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
     hip = _hip.Hip.get()
-    names = [None] * len(acc_index)
-    for a, i in acc_index.items():
-        names[i] = a
-    index = hip.acc_index(names)
-    d_text = batch = cov_lengths = cov_dev = dep_dev = idn_dev = None
+    index = _acc_index_of(hip, acc_index)
+    d_text = batch = lengths = None
     try:
         # the text plus ~60 B per line of line index and tokeniser output must fit beside what is resident already:
         # otherwise straight to the streaming path (256 MB chunks), without first filling the device and failing
         free, _, pooled = hip.mem_info()
         streamed = os.environ.get('MG_NO_STREAM') != '1'
-        if sided and not streamed and _is_gzip(path):
+        if sides and not streamed and _is_gzip(path):
             streamed = True  # (the whole-text call has no inflater in front of it: a compressed file's places come from the stream)
         # (streamed: only the 16-byte records — ~1/20 of the text — and three chunks of text are ever resident)
-        need = os.path.getsize(path) // 8 if streamed or _collate else 2 * os.path.getsize(path)
+        size = os.path.getsize(path)
+        need = size // 8 if streamed or _collate else 2 * size
+        # a record is at least ~50 B of BAM / compressed text, ~100 B of plain text
+        nrec = size // (50 if _bam or _is_gzip(path) else 100)
         if _collate:
             # beside the records, per record: 16 B of key, four 8 B sort arrays, ~16 B of the radix sort's own storage and the
-            # 16 B of the regrouped copy = 80 B; a record is at least ~50 B of BAM / compressed text, ~100 B of plain text
-            compressed = _bam or _is_gzip(path)
-            need += 80 * (os.path.getsize(path) // (50 if compressed else 100))
+            # 16 B of the regrouped copy = 80 B
+            need += 80 * nrec
         if _assignments:
             # per read 16 B of verdict words, 8 B of name offset and the name itself (~40 B); a read is at least one record
-            need += 64 * (os.path.getsize(path) // (50 if _bam or _is_gzip(path) else 100))
-        if placed:
-            # 8 B of place per record (and as much again where a collation permutes them) and one bit per reference base
-            nrec = os.path.getsize(path) // (50 if _bam or _is_gzip(path) else 100)
-            need += 16 * nrec
-            cov_lengths = coverage.lengths_of(_coverage if _coverage is not None else _depth, acc2info)
-            if _coverage is not None:
-                need += sum(cov_lengths.values()) // 8
-            if _depth is not None:  # 4 B per reference base, the histogram rows and the windows
-                need += _depth_bytes(cov_lengths, _depth_window(args), nrec)
-        if edited:
-            need += _identity_bytes(len(acc_index), os.path.getsize(path) // (50 if _bam or _is_gzip(path) else 100))
+            need += 64 * nrec
+        if sides.placed:
+            lengths = coverage.lengths_of(sides.header, acc2info)
+        need += sides.need_bytes(lengths, len(acc_index), nrec)
         if need > free + pooled:
             return None
+        chunk_bytes = int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0))
         try:
-            if sided and not streamed and not _bam and not _collate:  # (one call over the whole text: the flag-taking tokeniser)
-                d_text, size = hip.upload_file(path)
-                batch = hip.sam_tokenize_dev_batch(d_text.ptr, size, index, '', named=_assignments, placed=placed, edited=edited)
-            elif sided:
-                stream = hip.bam_stream_file if _bam else hip.sam_stream_file
-                batch = stream(path, index, chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)), collate=_collate,
-                               named=_assignments, placed=placed, edited=edited)
+            if not streamed and not _bam and not _collate:  # the whole text up, then one tokeniser call
+                d_text, nbytes = hip.upload_file(path)
+                batch = hip.sam_tokenize_dev_batch(d_text.ptr, nbytes, index, '', paf=_paf, named=_assignments, placed=sides.placed,
+                                                   edited=sides.edited)
             elif _bam:  # (a BAM is always streamed: ~16 B of records per ~60 B of the compressed file stay resident)
-                batch = hip.bam_stream_file(path, index, chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)), collate=_collate,
-                                            named=_assignments)
-            elif _collate:  # (always streamed: the keys ride on the stream's batches)
-                batch = hip.sam_stream_file(path, index, paf=_paf, chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)), collate=True)
-            elif not streamed:  # the whole text up, then one tokeniser call (round 2's path)
-                d_text, size = hip.upload_file(path)
-                batch = hip.sam_tokenize_dev_batch(d_text.ptr, size, index, '', paf=_paf, named=_assignments)
+                batch = hip.bam_stream_file(path, index, chunk_bytes=chunk_bytes, collate=_collate, named=_assignments,
+                                            placed=sides.placed, edited=sides.edited)
             else:
                 # reader threads -> page-locked chunks -> HBM -> tokeniser, chunk i + 1 in flight while chunk i is tokenised
-                batch = hip.sam_stream_file(path, index, paf=_paf, chunk_bytes=int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0)),
-                                            named=_assignments)
+                # (a collation is always streamed: the keys ride on the stream's batches)
+                batch = hip.sam_stream_file(path, index, paf=_paf, chunk_bytes=chunk_bytes, collate=_collate, named=_assignments,
+                                            placed=sides.placed, edited=sides.edited)
         except _hip.SamParseError:
             return None
         except _hip.HipError as e:
@@ -719,36 +555,19 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
         finally:
             if d_text is not None:
                 d_text.free()
-        if _coverage is not None:  # (before stage C takes the batch over)
-            cov_dev = _coverage_open(hip, cov_lengths, acc_index)
-            cov_dev.add_batch(batch, float(args.pct_id))
-        if _depth is not None:
-            dep_dev = _depth_open(args, hip, cov_lengths, acc_index)
-            dep_dev.add_batch(batch, float(args.pct_id))
-        if edited:
-            idn_dev = _identity_open(hip, acc_index)
-            idn_dev.add_batch(batch, float(args.pct_id))
+        sides.open(hip, lengths, acc_index)  # (before stage C takes the batch over)
+        sides.add_batch(batch, float(args.pct_id))
         res = hip.profile_assign_dev_records(batch.ptr, batch.count, ref2tax, len(taxids), float(args.pct_id), [batch],
                                              resident=_resident, assign=_assignments)
         batch = None  # owned by the result now
     except BaseException:
-        if cov_dev is not None:
-            cov_dev.free()
-        if dep_dev is not None:
-            dep_dev.free()
-        if idn_dev is not None:
-            idn_dev.free()
+        sides.free()
         raise
     finally:
         index.free()
         if batch is not None:
             batch.free()
-    if cov_dev is not None:
-        _coverage_close(args, path, cov_lengths, cov_dev, acc_index, acc2info, taxid2info)
-    if dep_dev is not None:
-        _depth_close(args, path, cov_lengths, dep_dev, acc_index, acc2info, taxid2info)
-    if idn_dev is not None:
-        _identity_close(args, path, idn_dev, acc_index, acc2info, taxid2info)
+    sides.close(acc2info, taxid2info)
     if _assignments:
         _append_assignments(args, assignment_rows(res, taxids))
     if not _want_lists:
@@ -887,10 +706,7 @@ def map_and_process_file_dist(args, path, acc2info, taxid2info, ctx, _want_lists
     dist, rank, world, hip = ctx
     acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
     _ = taxid2info['Unmapped']
-    names = [None] * len(acc_index)
-    for a, i in acc_index.items():
-        names[i] = a
-    index = hip.acc_index(names)
+    index = _acc_index_of(hip, acc_index)
     start, end = sam_range_of_rank(path, rank, world)
     d_text = batch = None
     bad = 0
@@ -941,21 +757,21 @@ class _CudaWords:
 
 
 def map_and_process(args, instream, acc2info, taxid2info, _assign=None, _want_lists=True, _resident=False, _assignments=False,
-                    _coverage=None, _depth=None, _identity=None):
+                    _coverage=None, _depth=None, _identity=None, _sides=None):
     """Reference signature (:193).  `_assign` is a test seam; product code never passes it.
     _assignments (--read_assignments): every chunk's read names are collected beside its records, stage C runs over the records
     uploaded as one array with the verdict words written, and the rows are appended to args.read_assignments.
-    _coverage (--coverage): the name the block is written under — every chunk's places are collected beside its records, the
-    lengths come from the leading '@' lines of the stream, and places and records go up together for the coverage kernels.
-    _depth (--depth, --depth_windows): the name its blocks are written under, likewise — the same places feed the depth kernels.
-    _identity (--identity): the name its block is written under — every chunk's edits are collected beside its records and go up
-    with them for the identity kernel."""
+    _sides (a SideOutputs: --coverage, --depth / --depth_windows, --identity): every chunk's places and / or edits are collected
+    beside its records and go up with them for the families' kernels; the lengths come from the leading '@' lines of the stream.
+    _coverage, _depth, _identity: the same asked for family by family, each the name its block is written under."""
+    if _sides is None:
+        named = [(fam, src) for fam, src in ((COVERAGE, _coverage), (DEPTH, _depth), (IDENTITY, _identity)) if src is not None]
+        _sides = SideOutputs(args, [fam for fam, _ in named], named[0][1] if named else None)
     acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
-    if _coverage is not None or _depth is not None or _identity is not None:
+    if _sides:
         if _assign is not None:
             raise ValueError('--coverage, --depth and --identity need the device path')
-        return _map_and_process_covered(args, instream, acc2info, taxid2info, _want_lists, _resident, _assignments, _coverage, _depth,
-                                        _identity)
+        return _map_and_process_sided(args, instream, acc2info, taxid2info, _want_lists, _resident, _assignments, _sides)
     _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
     # test seam: an injected record-level backend is fed by the host tokeniser; product code never passes one
     tokenise = _device_tokenise if _assign is None else tokenise_sam
@@ -983,61 +799,38 @@ def map_and_process(args, instream, acc2info, taxid2info, _assign=None, _want_li
     return assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=_want_lists)
 
 
-def _map_and_process_covered(args, instream, acc2info, taxid2info, _want_lists, _resident, _assignments, source, depth_source=None,
-                             identity_source=None):
-    """map_and_process with --coverage (source), --depth / --depth_windows (depth_source) and / or --identity (identity_source), and
-    --read_assignments where that is on."""
+def _map_and_process_sided(args, instream, acc2info, taxid2info, _want_lists, _resident, _assignments, sides):
+    """map_and_process with side outputs, and --read_assignments where that is on."""
     acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
     _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
-    want_places = source is not None or depth_source is not None
-    names, places, header = ([] if _assignments else None), ([] if want_places else None), []
-    edits = [] if identity_source is not None else None
+    names, header = ([] if _assignments else None), []
+    places, edits = ([] if sides.placed else None), ([] if sides.edited else None)
     recs = _device_tokenise(instream, acc_index, decode=(args.input_type != 'sam'), read_names=names, places=places, header=header,
                             edits=edits)
     place = np.concatenate(places) if places else np.zeros(0, dtype=_hip.PLACE_DTYPE)
     edit = np.concatenate(edits) if edits else np.zeros(0, dtype=_hip.EDIT_DTYPE)
-    assert not want_places or len(place) == len(recs)
+    assert places is None or len(place) == len(recs)
     assert edits is None or len(edit) == len(recs)
     hip = _hip.Hip.get()
     d_recs = hip.array(recs if len(recs) else np.zeros(1, _hip.REC_DTYPE))
     try:
-        lengths = coverage.lengths_of(header, acc2info)
-        devs, idn_dev = [], None
-        try:
-            if source is not None:
-                devs.append(_coverage_open(hip, lengths, acc_index))
-            if depth_source is not None:
-                devs.append(_depth_open(args, hip, lengths, acc_index))
-            if identity_source is not None:
-                idn_dev = _identity_open(hip, acc_index)
-            if len(recs):
-                d_place = hip.array(place.view(np.uint8)) if want_places else None
-                d_edit = None
-                try:
-                    d_edit = hip.array(edit.view(np.uint8)) if idn_dev is not None else None
-                    for dev in devs:
-                        dev.add_ptr(d_recs.ptr, d_place.ptr, len(recs), float(args.pct_id))
-                    if idn_dev is not None:
-                        idn_dev.add_ptr(d_recs.ptr, d_edit.ptr, len(recs), float(args.pct_id))
-                    hip.sync()
-                finally:
-                    if d_place is not None:
-                        d_place.free()
-                    if d_edit is not None:
-                        d_edit.free()
-        except BaseException:
-            for dev in devs:
-                dev.free()
-            if idn_dev is not None:
-                idn_dev.free()
-            raise
-        if source is not None:
-            _coverage_close(args, source, lengths, devs[0], acc_index, acc2info, taxid2info)
-        if depth_source is not None:  # (should the first close raise, this handle goes with the process)
-            _depth_close(args, depth_source, lengths, devs[-1], acc_index, acc2info, taxid2info)
-        if idn_dev is not None:
-            _identity_close(args, identity_source, idn_dev, acc_index, acc2info, taxid2info)
+        sides.open(hip, coverage.lengths_of(header, acc2info), acc_index)
+        if len(recs):
+            d_place = d_edit = None
+            try:
+                d_place = hip.array(place.view(np.uint8)) if sides.placed else None
+                d_edit = hip.array(edit.view(np.uint8)) if sides.edited else None
+                sides.add_ptrs(d_recs.ptr, d_place.ptr if sides.placed else None, d_edit.ptr if sides.edited else None, len(recs),
+                               float(args.pct_id))
+                hip.sync()
+            finally:
+                if d_place is not None:
+                    d_place.free()
+                if d_edit is not None:
+                    d_edit.free()
+        sides.close(acc2info, taxid2info)
     except BaseException:
+        sides.free()
         d_recs.free()  # (stage C has not taken the records over yet)
         raise
     res = hip.profile_assign_dev_records(d_recs.ptr, len(recs), ref2tax, len(taxids), float(args.pct_id), [d_recs],
@@ -1244,23 +1037,20 @@ def compute_abundances(args, infile, acc2info, tax2info):
     seams_untouched = (_device_tokenise is tokenise_sam_device and _device_tokenise_paf is tokenise_paf_device
                        and _device_assign is _DEVICE_ASSIGN)  # (tests reroute them)
     paf = bool(getattr(args, 'paf_input', False))
-    want_rows = _wants_assignments(args)
-    want_cov = _wants_coverage(args)
-    want_dep = _wants_depth(args)
-    if want_cov and not seams_untouched:
-        raise ValueError('--coverage needs the device path')
-    if want_dep and not seams_untouched:
-        raise ValueError('--depth needs the device path')
-    want_idn = _wants_identity(args)
-    if want_idn and not seams_untouched:
-        raise ValueError('--identity needs the device path')
-    if args.input_type == 'sam' and not paf and bam.is_bam(infile):  # decided per file: a BAM is never SAM text
-        instream.close()
-        return _compute_abundances_bam(args, infile, acc2info, tax2info, on_device, seams_untouched)
-    if args.input_type == 'sam' and not paf and _wants_collation(args, lambda: _sam_header_lines(infile)):
-        instream.close()
-        return _compute_abundances_collated(args, infile, acc2info, tax2info, on_device, seams_untouched)
-    if args.input_type == 'sam' and seams_untouched and not paf and not want_rows and not want_cov and not want_dep and not want_idn:
+    want_rows = ASSIGNMENTS.wanted(args)
+    for fam in FAMILIES:
+        if fam.wanted(args) and not seams_untouched:
+            raise ValueError('--%s needs the device path' % fam.flags[0])
+    if args.input_type == 'sam' and not paf:
+        is_bam = bam.is_bam(infile)  # decided per file: a BAM is never SAM text
+        if is_bam or _wants_collation(args, lambda: _sam_header_lines(infile)):
+            instream.close()
+            if int(os.environ.get('RANK', '0')) != 0:
+                return None  # (a multi-GPU launch leaves a BAM or a collated input to rank 0: sharing one between the ranks is not done)
+            collating = not is_bam or _wants_collation(args, lambda: _bam_header_lines(infile))
+            return _compute_abundances_regrouped(args, infile, acc2info, tax2info, on_device, seams_untouched, is_bam, collating)
+    sides = SideOutputs.of(args, infile)
+    if args.input_type == 'sam' and seams_untouched and not paf and not want_rows and not sides:
         from .select_db import dist_context
         ctx = dist_context()
         if ctx is not None:  # one process per GPU: the ranks tokenise the text between them, rank 0 does the rest
@@ -1271,13 +1061,12 @@ def compute_abundances(args, infile, acc2info, tax2info):
             seams_untouched = seams_untouched and done is not None  # (None: rank 0 streams the file, alone)
     if args.input_type == 'sam' and seams_untouched and done is None:
         # a plain file (SAM, or a PAF replay): all the way on the device
+        sides.header = _sam_header_lines(infile) if sides.placed else None
         done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _paf=paf,
-                                    _assignments=want_rows, _coverage=_sam_header_lines(infile) if want_cov else None,
-                                    _depth=_sam_header_lines(infile) if want_dep else None, _identity=want_idn)
+                                    _assignments=want_rows, _sides=sides)
     if done is None:
         done = map_and_process(args, instream, acc2info, tax2info, _want_lists=False, _resident=on_device,
-                               _assignments=want_rows and seams_untouched, _coverage=infile if want_cov else None,
-                               _depth=infile if want_dep else None, _identity=infile if want_idn else None)
+                               _assignments=want_rows and seams_untouched, _sides=sides)
     taxids2abs, mm, low_mem_mmap = done
     if args.input_type == 'sam':
         instream.close()
@@ -1285,10 +1074,6 @@ def compute_abundances(args, infile, acc2info, tax2info):
         mapper.stdout.close()
         mapper.wait()
     return _abundances_tail(args, taxids2abs, mm, tax2info, on_device)
-
-
-def _wants_assignments(args):
-    return getattr(args, 'read_assignments', 'NONE') not in (None, 'NONE')  # (callers build Namespaces without it)
 
 
 def _is_gzip(path):
@@ -1322,70 +1107,32 @@ def _wants_collation(args, header_lines):
     return mode == 'auto' and collate.header_says_coordinate(header_lines())
 
 
-def _compute_abundances_collated(args, infile, acc2info, tax2info, on_device, seams_untouched):
-    """A SAM file whose records are regrouped by read before stage C: on the device (map_and_process_file, _collate), or — for a
-    line the device does not decide, a file it refuses or keys that do not fit — through collate.collated_lines, the definition,
-    whose line stream goes to map_and_process and raises there what the reference raises.  A multi-GPU launch leaves a collated
-    input to rank 0, as a BAM (sharing keys between the ranks is not done)."""
-    if int(os.environ.get('RANK', '0')) != 0:
-        return None
+def _compute_abundances_regrouped(args, infile, acc2info, tax2info, on_device, seams_untouched, is_bam, collating):
+    """A BAM file (is_bam), and / or a file whose records are regrouped by read before stage C (collating; a SAM file comes here only
+    for that) -> clade abundances.  On the device (map_and_process_file), or — for a line or record the device does not decide, a
+    file it refuses or keys that do not fit — the file's lines (bam.sam_lines: a BAM's SAM rendering), through collate.collated_lines,
+    the definition, where collating: that line stream goes to map_and_process and raises there what the reference raises."""
+    lines_of, header_of = (bam.sam_lines, _bam_header_lines) if is_bam else (_sam_file_lines, _sam_header_lines)
+    if is_bam:
+        bam.warn_about(infile, collating=collating)
     done = None
-    want_cov = _wants_coverage(args) and seams_untouched
-    want_dep = _wants_depth(args) and seams_untouched
-    want_idn = _wants_identity(args) and seams_untouched
+    want_rows = ASSIGNMENTS.wanted(args)
+    sides = SideOutputs.of(args, infile, enabled=seams_untouched)
     if seams_untouched:
-        done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _collate=True,
-                                    _coverage=_sam_header_lines(infile) if want_cov else None,
-                                    _depth=_sam_header_lines(infile) if want_dep else None, _identity=want_idn)
+        # (a BAM's reference list's l_ref equals the header's @SQ text: the text is what gives the lengths)
+        sides.header = header_of(infile) if sides.placed else None
+        done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _bam=is_bam,
+                                    _collate=collating, _assignments=want_rows and not collating, _sides=sides)
     if done is None:
-        done = map_and_process(args, collate.collated_lines(_sam_file_lines(infile)), acc2info, tax2info, _want_lists=False,
-                               _resident=on_device)
-        if want_cov:  # (the definition over the file's lines: coverage does not depend on their order)
-            _append_coverage(args, infile, coverage.coverage(_sam_file_lines(infile), acc2info, args.pct_id), acc2info, tax2info)
-        if want_dep:  # (likewise)
-            _append_depth(args, infile, depth.depth(_sam_file_lines(infile), acc2info, args.pct_id, _depth_window(args)), acc2info, tax2info)
-        if want_idn:  # (likewise)
-            _append_identity(args, infile, identity.identity(_sam_file_lines(infile), acc2info, args.pct_id), acc2info, tax2info)
-    if _wants_assignments(args):  # (a named batch is not collated: the rows of a collated input come from the definition)
-        _append_assignments(args, assignments.read_assignments(collate.collated_lines(_sam_file_lines(infile)), acc2info, args.pct_id))
-    taxids2abs, mm, _ = done
-    return _abundances_tail(args, taxids2abs, mm, tax2info, on_device)
-
-
-def _compute_abundances_bam(args, infile, acc2info, tax2info, on_device, seams_untouched):
-    """A BAM file -> clade abundances: its records decoded on the device (map_and_process_file), or — for a record the device does
-    not decide, or a file it refuses — its SAM rendering through the SAM path, which raises what the reference raises on that line.
-    A multi-GPU launch leaves a BAM to rank 0 (sharing one between the ranks is not done)."""
-    if int(os.environ.get('RANK', '0')) != 0:
-        return None
-    collating = _wants_collation(args, lambda: _bam_header_lines(infile))
-    bam.warn_about(infile, collating=collating)
-    done = None
-    want_rows = _wants_assignments(args)
-    want_cov = _wants_coverage(args) and seams_untouched
-    want_dep = _wants_depth(args) and seams_untouched
-    want_idn = _wants_identity(args) and seams_untouched
-    if seams_untouched:
-        # (the reference list's l_ref equals the header's @SQ text: the text is what gives the lengths)
-        done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _bam=True,
-                                    _collate=collating, _assignments=want_rows and not collating,
-                                    _coverage=_bam_header_lines(infile) if want_cov else None,
-                                    _depth=_bam_header_lines(infile) if want_dep else None, _identity=want_idn)
-    if done is None:
-        lines = bam.sam_lines(infile)
+        lines = lines_of(infile)
+        # (a collated stream's side outputs come from the definitions over the file's lines: they do not depend on their order)
         done = map_and_process(args, collate.collated_lines(lines) if collating else lines, acc2info, tax2info, _want_lists=False,
                                _resident=on_device, _assignments=want_rows and not collating and seams_untouched,
-                               _coverage=infile if want_cov and not collating else None,
-                               _depth=infile if want_dep and not collating else None,
-                               _identity=infile if want_idn and not collating else None)
-        if want_cov and collating:
-            _append_coverage(args, infile, coverage.coverage(bam.sam_lines(infile), acc2info, args.pct_id), acc2info, tax2info)
-        if want_dep and collating:
-            _append_depth(args, infile, depth.depth(bam.sam_lines(infile), acc2info, args.pct_id, _depth_window(args)), acc2info, tax2info)
-        if want_idn and collating:
-            _append_identity(args, infile, identity.identity(bam.sam_lines(infile), acc2info, args.pct_id), acc2info, tax2info)
-    if want_rows and collating:  # (as a collated SAM file: the definition over the regrouped lines)
-        _append_assignments(args, assignments.read_assignments(collate.collated_lines(bam.sam_lines(infile)), acc2info, args.pct_id))
+                               _sides=None if collating else sides)
+        if collating:
+            sides.append_from_definition(infile, lambda: lines_of(infile), acc2info, tax2info)
+    if want_rows and collating:  # (a named batch is not collated: the rows of a collated input come from the definition)
+        _append_assignments(args, assignments.read_assignments(collate.collated_lines(lines_of(infile)), acc2info, args.pct_id))
     taxids2abs, mm, _ = done
     return _abundances_tail(args, taxids2abs, mm, tax2info, on_device)
 
@@ -1477,23 +1224,7 @@ def map_main(args=None):
         sys.exit('Error: --pct_id must be between 0.0 and 1.0, inclusive.')
     if args.db == 'NONE' and not args.infiles[0].endswith(('sam', 'paf', 'bam')):
         sys.exit('Error: --db must be specified unless sam files are provided.')
-    if _wants_assignments(args) and int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        # (the records the ranks gather on rank 0 carry no names: refused before the process group or a GPU is touched)
-        sys.exit('Error: --read_assignments runs in one process on one GPU; start it without torch.distributed.run.')
-    if _wants_coverage(args) and int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        sys.exit('Error: --coverage runs in one process on one GPU; start it without torch.distributed.run.')
-    if _wants_coverage(args) and (getattr(args, 'paf_input', False) or any(f.endswith('.paf') for f in args.infiles)):
-        sys.exit('Error: --coverage needs SAM or BAM alignments: a PAF line has no POS and CIGAR columns.')
-    if _wants_depth(args) and int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        sys.exit('Error: --depth and --depth_windows run in one process on one GPU; start it without torch.distributed.run.')
-    if _wants_depth(args) and (getattr(args, 'paf_input', False) or any(f.endswith('.paf') for f in args.infiles)):
-        sys.exit('Error: --depth and --depth_windows need SAM or BAM alignments: a PAF line has no POS and CIGAR columns.')
-    if _wants_identity(args) and int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        sys.exit('Error: --identity runs in one process on one GPU; start it without torch.distributed.run.')
-    if _wants_identity(args) and (getattr(args, 'paf_input', False) or any(f.endswith('.paf') for f in args.infiles)):
-        sys.exit('Error: --identity needs SAM or BAM alignments: the NM:i: and cg:Z: tags of a PAF line are not read.')
-    if int(getattr(args, 'depth_window_size', 1000)) < 1:
-        sys.exit('Error: --depth_window_size must be at least 1.')
+    check_flags(args)  # (refused before the process group or a GPU is touched)
     check_multimap_flags(args)
     args.data = cli.with_slash(args.data)
     if args.dbinfo == 'AUTO':
@@ -1512,16 +1243,7 @@ def map_main(args=None):
         return  # a multi-GPU launch shares only SAM files between the ranks; anything else is rank 0's alone
     if int(os.environ.get('RANK', '0')) == 0:
         open(args.output, 'w').close()
-        if _wants_assignments(args):
-            assignments.write_assignments(args.read_assignments, [])  # the header; every input file appends its rows
-        if _wants_coverage(args):
-            coverage.write_coverage(args.coverage)  # the column header; every input file appends its block
-        if _wanted(args, 'depth'):
-            depth.write_depth(args.depth)  # likewise
-        if _wanted(args, 'depth_windows'):
-            depth.write_windows(args.depth_windows)
-        if _wants_identity(args):
-            identity.write_identity(args.identity)
+        write_headers(args)
     acc2info, taxid2info = get_acc2info(args)
     rank_results = gather_results(args, acc2info, taxid2info)
     if not getattr(args, '_not_root', False):

@@ -53,17 +53,8 @@ def _bam_for_the_aligner(args):
 def main(argv=None):
     args = metalign_parseargs(argv)
     import os
-    if args.read_assignments != 'NONE' and int(os.environ.get('WORLD_SIZE', '1')) > 1:  # (as map_main, before stages A and B run)
-        sys.exit('Error: --read_assignments runs in one process on one GPU; start it without torch.distributed.run.')
-    if args.coverage != 'NONE' and int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        sys.exit('Error: --coverage runs in one process on one GPU; start it without torch.distributed.run.')
+    mapper.check_flags(args)  # (as map_main, before stages A and B run)
     mapper.check_multimap_flags(args)
-    if (args.depth != 'NONE' or args.depth_windows != 'NONE') and int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        sys.exit('Error: --depth and --depth_windows run in one process on one GPU; start it without torch.distributed.run.')
-    if args.identity != 'NONE' and int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        sys.exit('Error: --identity runs in one process on one GPU; start it without torch.distributed.run.')
-    if args.depth_window_size < 1:
-        sys.exit('Error: --depth_window_size must be at least 1.')
     args.data = cli.with_slash(args.data)
     own_temp = args.temp_dir == 'AUTO/'  # a directory of this process's own making (one per rank in a multi-GPU launch)
     if own_temp:

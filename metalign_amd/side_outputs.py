@@ -1,0 +1,293 @@
+"""Stage C's side outputs: what is filled from the tokenised records beside the profile.
+
+A family (COVERAGE, DEPTH, IDENTITY) is a descriptor: its flags, the side array of a batch it reads, its refusals, its header,
+what it holds on the device, and how its device accumulator is opened and turned into the file's block.  ASSIGNMENTS
+(--read_assignments) shares only the flag test, the refusal and the header: its rows come from stage C itself.
+
+SideOutputs is the families wanted for ONE input file.  map_and_profile opens it, feeds it the records and closes it; the
+order is always coverage, depth, identity, and whatever was opened is freed on every way out.
+"""
+import os
+import sys
+
+import numpy as np
+
+from . import _hip, assignments, coverage, depth, identity
+
+
+def _flag(args, name):
+    return getattr(args, name, 'NONE') not in (None, 'NONE')  # (callers build Namespaces without it)
+
+
+def source_label(args, path):
+    """The `source=` of a block: the path only where there is more than one input file."""
+    return path if len(getattr(args, 'infiles', [])) > 1 else None
+
+
+def lengths_array(lengths, acc_index):
+    """{accession: length} -> uint64[accession row]."""
+    arr = np.zeros(len(acc_index), dtype=np.uint64)
+    for a, i in acc_index.items():
+        arr[i] = lengths[a]
+    return arr
+
+
+class _Flags:
+    """A group of flags that ask for one output: the test, the refusals and the header."""
+    flags = ()
+    refuse_world = refuse_paf = None  # (None: not refused)
+
+    def wanted(self, args):
+        return any(_flag(args, f) for f in self.flags)
+
+
+class _Assignments(_Flags):
+    flags = ('read_assignments',)
+    # (the records the ranks gather on rank 0 carry no names)
+    refuse_world = 'Error: --read_assignments runs in one process on one GPU; start it without torch.distributed.run.'
+
+    def write_header(self, args):
+        assignments.write_assignments(args.read_assignments, [])  # the header; every input file appends its rows
+
+
+class _Family(_Flags):
+    """side: the side array of a batch it reads ('places' / 'edits').  nomem: the exit text when the device refuses the memory,
+    with the MB figure of nomem_mb."""
+    side = nomem = None
+
+    def open(self, args, hip, lengths, acc_index):
+        """The device accumulator for one input file (lengths: coverage.lengths_of — the file's @SQ lines over db_info's)."""
+        try:
+            return self._open(args, hip, lengths, acc_index)
+        except _hip.HipError as e:
+            if e.code != _hip.ERR_NOMEM:
+                raise
+            sys.exit(self.nomem % self.nomem_mb(args, lengths, acc_index))
+
+
+class _Coverage(_Family):
+    flags, side = ('coverage',), 'places'
+    refuse_world = 'Error: --coverage runs in one process on one GPU; start it without torch.distributed.run.'
+    refuse_paf = 'Error: --coverage needs SAM or BAM alignments: a PAF line has no POS and CIGAR columns.'
+    nomem = 'Error: --coverage keeps one bit per reference base on the GPU; %d MB for this database do not fit.'
+
+    def write_header(self, args):
+        coverage.write_coverage(args.coverage)  # the column header; every input file appends its block
+
+    def device_bytes(self, args, lengths, nacc, nrec):
+        return sum(lengths.values()) // 8  # one bit per reference base
+
+    def nomem_mb(self, args, lengths, acc_index):
+        return int(lengths_array(lengths, acc_index).sum()) >> 23
+
+    def _open(self, args, hip, lengths, acc_index):
+        return hip.coverage(lengths_array(lengths, acc_index))
+
+    def close(self, args, source, lengths, dev, acc_index, acc2info, taxid2info):
+        """The device's sums -> the file's block."""
+        try:
+            aln, bases, covered, unplaced = dev.result()
+        finally:
+            dev.free()
+        per = {a: [int(aln[i]), int(bases[i]), int(covered[i])] for a, i in acc_index.items() if aln[i]}
+        self.append(args, source, coverage.Coverage(lengths, per, unplaced), acc2info, taxid2info)
+
+    def append(self, args, source, cov, acc2info, taxid2info):
+        coverage.write_coverage(args.coverage, coverage.rows(cov, acc2info, taxid2info), cov.unplaced, source=source_label(args, source),
+                                append=True)
+
+    def append_from_definition(self, args, path, lines, acc2info, taxid2info):
+        self.append(args, path, coverage.coverage(lines, acc2info, args.pct_id), acc2info, taxid2info)
+
+
+class _Depth(_Family):
+    """--depth or --depth_windows: either one asks for the per-base depth."""
+    flags, side = ('depth', 'depth_windows'), 'places'
+    refuse_world = 'Error: --depth and --depth_windows run in one process on one GPU; start it without torch.distributed.run.'
+    refuse_paf = 'Error: --depth and --depth_windows need SAM or BAM alignments: a PAF line has no POS and CIGAR columns.'
+    nomem = 'Error: --depth keeps four bytes per reference base on the GPU; %d MB for this database do not fit.'
+
+    def write_header(self, args):
+        if _flag(args, 'depth'):
+            depth.write_depth(args.depth)
+        if _flag(args, 'depth_windows'):
+            depth.write_windows(args.depth_windows)
+
+    @staticmethod
+    def window(args):
+        return int(getattr(args, 'depth_window_size', 1000)) if _flag(args, 'depth_windows') else 0
+
+    def device_bytes(self, args, lengths, nacc, nrec):
+        """4 B per reference base and accession, 12 B per window, a 32 KB histogram row per accession that is hit (at most one per
+        record)."""
+        window = self.window(args)
+        total = sum(lengths.values())
+        nwin = sum((n + window - 1) // window for n in lengths.values()) if window else 0
+        return 4 * (total + len(lengths)) + 12 * nwin + 8 * _hip.DEPTH_BINS * min(len(lengths), nrec)
+
+    def nomem_mb(self, args, lengths, acc_index):
+        return self.device_bytes(args, lengths, len(acc_index), 0) >> 20
+
+    def _open(self, args, hip, lengths, acc_index):
+        return hip.depth(lengths_array(lengths, acc_index), self.window(args))
+
+    def close(self, args, source, lengths, dev, acc_index, acc2info, taxid2info):
+        """The device's histogram rows and windows -> the file's blocks."""
+        try:
+            aln, unplaced, hist, win = dev.result()
+        finally:
+            dev.free()
+        names = {i: a for a, i in acc_index.items()}
+        per = {names[r]: [int(aln[r]), H] for r, H in hist.items()}
+        windows = {names[r]: w for r, w in win.items()}
+        self.append(args, source, depth.Depth(lengths, per, unplaced, dev.window, windows), acc2info, taxid2info)
+
+    def append(self, args, source, dep, acc2info, taxid2info):
+        source = source_label(args, source)
+        if _flag(args, 'depth'):
+            depth.write_depth(args.depth, depth.rows(dep, acc2info, taxid2info), dep.unplaced, source=source, append=True)
+        if _flag(args, 'depth_windows'):
+            depth.write_windows(args.depth_windows, depth.window_rows(dep, acc2info), source=source, append=True)
+
+    def append_from_definition(self, args, path, lines, acc2info, taxid2info):
+        self.append(args, path, depth.depth(lines, acc2info, args.pct_id, self.window(args)), acc2info, taxid2info)
+
+
+class _Identity(_Family):
+    flags, side = ('identity',), 'edits'
+    refuse_world = 'Error: --identity runs in one process on one GPU; start it without torch.distributed.run.'
+    refuse_paf = 'Error: --identity needs SAM or BAM alignments: the NM:i: and cg:Z: tags of a PAF line are not read.'
+    nomem = 'Error: --identity keeps 1001 bins of eight bytes per accession on the GPU; %d MB for this database do not fit.'
+
+    def write_header(self, args):
+        identity.write_identity(args.identity)
+
+    def device_bytes(self, args, lengths, nacc, nrec):
+        """1001 bins of 8 B and three sums per accession, 8 B of edit per record (and as much again where a collation permutes
+        them)."""
+        return 8 * (_hip.IDENTITY_BINS + 3) * nacc + 16 * nrec
+
+    def nomem_mb(self, args, lengths, acc_index):
+        return self.device_bytes(args, lengths, len(acc_index), 0) >> 20
+
+    def _open(self, args, hip, lengths, acc_index):
+        return hip.identity(len(acc_index))
+
+    def close(self, args, source, lengths, dev, acc_index, acc2info, taxid2info):
+        """The device's sums and histogram rows -> the file's block."""
+        try:
+            aln, cols, eds, unscored, hist = dev.result()
+        finally:
+            dev.free()
+        names = {i: a for a, i in acc_index.items()}
+        per = {names[r]: [int(aln[r]), int(cols[r]), int(eds[r]), H] for r, H in hist.items()}
+        self.append(args, source, identity.Identity(per, unscored), acc2info, taxid2info)
+
+    def append(self, args, source, idn, acc2info, taxid2info):
+        identity.write_identity(args.identity, identity.rows(idn, acc2info, taxid2info), idn.unscored, source=source_label(args, source),
+                                append=True)
+
+    def append_from_definition(self, args, path, lines, acc2info, taxid2info):
+        self.append(args, path, identity.identity(lines, acc2info, args.pct_id), acc2info, taxid2info)
+
+
+ASSIGNMENTS, COVERAGE, DEPTH, IDENTITY = _Assignments(), _Coverage(), _Depth(), _Identity()
+FAMILIES = (COVERAGE, DEPTH, IDENTITY)  # (the order of every open, add and close)
+
+
+def check_flags(args):
+    """What map_main and metalign.main refuse before a process group, the library or a GPU is touched."""
+    world = int(os.environ.get('WORLD_SIZE', '1'))
+    paf = getattr(args, 'paf_input', False) or any(f.endswith('.paf') for f in getattr(args, 'infiles', ()))
+    for fam in (ASSIGNMENTS,) + FAMILIES:
+        if not fam.wanted(args):
+            continue
+        if world > 1:
+            sys.exit(fam.refuse_world)
+        if paf and fam.refuse_paf:
+            sys.exit(fam.refuse_paf)
+    if int(getattr(args, 'depth_window_size', 1000)) < 1:
+        sys.exit('Error: --depth_window_size must be at least 1.')
+
+
+def write_headers(args):
+    """Rank 0, once: the header of every output that was asked for; every input file appends to them."""
+    for fam in (ASSIGNMENTS,) + FAMILIES:
+        if fam.wanted(args):
+            fam.write_header(args)
+
+
+class SideOutputs:
+    """The families wanted for one input file.  source: the name its blocks are written under.  header: the file's header lines,
+    whose @SQ lines give the lengths (None: the caller takes them from the stream)."""
+
+    def __init__(self, args, families, source, header=None):
+        self.args, self.source, self.header = args, source, header
+        self.families = tuple(f for f in FAMILIES if f in families)
+        self.placed = any(f.side == 'places' for f in self.families)
+        self.edited = any(f.side == 'edits' for f in self.families)
+        self._open = []  # (family, accumulator) of what is open
+        self._lengths = self._acc_index = None
+
+    @classmethod
+    def of(cls, args, source, header=None, enabled=True):
+        """What args asks for (enabled=False: nothing).  header: a callable, called where an output needs the lengths."""
+        sides = cls(args, [f for f in FAMILIES if enabled and f.wanted(args)], source)
+        if header is not None and sides.placed:
+            sides.header = header()
+        return sides
+
+    def __bool__(self):
+        return bool(self.families)
+
+    def need_bytes(self, lengths, nacc, nrec):
+        """What the accumulators and the side arrays of nrec records hold on the device."""
+        # 8 B of place per record (and as much again where a collation permutes them), once for coverage and depth
+        need = 16 * nrec if self.placed else 0
+        return need + sum(f.device_bytes(self.args, lengths, nacc, nrec) for f in self.families)
+
+    def open(self, hip, lengths, acc_index):
+        self._lengths, self._acc_index = lengths, acc_index
+        try:
+            for fam in self.families:
+                self._open.append((fam, fam.open(self.args, hip, lengths, acc_index)))
+        except BaseException:
+            self.free()
+            raise
+
+    def add_batch(self, batch, pct_id):
+        """A SamBatch that carries every side array the families read."""
+        try:
+            for _, dev in self._open:
+                dev.add_batch(batch, pct_id)
+        except BaseException:
+            self.free()
+            raise
+
+    def add_ptrs(self, d_recs, d_places, d_edits, n, pct_id):
+        """n records and their side arrays at device pointers (asynchronous, as the accumulators' add_ptr)."""
+        try:
+            for fam, dev in self._open:
+                dev.add_ptr(d_recs, d_places if fam.side == 'places' else d_edits, n, pct_id)
+        except BaseException:
+            self.free()
+            raise
+
+    def close(self, acc2info, taxid2info):
+        """Every accumulator -> its block, appended to its file."""
+        try:
+            while self._open:
+                fam, dev = self._open.pop(0)  # (the family's close frees it)
+                fam.close(self.args, self.source, self._lengths, dev, self._acc_index, acc2info, taxid2info)
+        finally:
+            self.free()
+
+    def free(self):
+        """Whatever is still open, once."""
+        while self._open:
+            self._open.pop()[1].free()
+
+    def append_from_definition(self, path, lines, acc2info, taxid2info):
+        """The host definitions over a line stream (lines(): a fresh iterator): the outputs do not depend on the lines' order."""
+        for fam in self.families:
+            fam.append_from_definition(self.args, path, lines(), acc2info, taxid2info)

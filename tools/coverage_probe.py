@@ -64,7 +64,7 @@ def write_case(d, lines, rng):
 
 def end_to_end(say, d, reps):
     import argparse as ap
-    from metalign_amd import map_and_profile as mp
+    from metalign_amd import cli, map_and_profile as mp
 
     def run(cov):
         args = ap.Namespace(infiles=[os.path.join(d, "probe.sam")], data="data/", db="NONE", dbinfo=os.path.join(d, "db_info.txt"),
@@ -80,7 +80,7 @@ def end_to_end(say, d, reps):
     t = [run(False) for _ in range(reps)]
     say("map_and_profile end to end, no flag      %s ms   (median %.2f, spread %.2f)"
         % (" ".join("%.2f" % (x * 1e3) for x in t), float(np.median(t)) * 1e3, (max(t) - min(t)) * 1e3))
-    if hasattr(mp, "_wants_coverage"):
+    if any(a.dest == "coverage" for a in cli.parser_for("map_and_profile")._actions):  # (the commit under test has the flag)
         run(True)
         t = [run(True) for _ in range(reps)]
         say("map_and_profile end to end, --coverage   %s ms   (median %.2f, spread %.2f)"

@@ -7,7 +7,8 @@ Tokeniser: mg_sam_tokenize_dev against mg_sam_tokenize_dev_ex with MG_BATCH_PLAC
 resident SAM text of --lines lines (tools/coverage_probe.py's file: 10 M lines by default, 3.6 GB, NM:i: the twelfth field), and with
 NM:i: behind five other tags.
 End to end: map_and_profile over that text as a file, with and without --identity (--e2e alone runs at any commit: without the flag
-it uses nothing this tool's other parts need; MG_PROBE_ROOT names the package to import).  Best of --reps for the kernels and the
+it uses nothing this tool's other parts need; MG_PROBE_ROOT names the package to import; --all_flags adds a run with --coverage, --depth
+and --identity together; a flag the commit's parser does not have is left out).  Best of --reps for the kernels and the
 tokeniser; for the end-to-end runs every repeat is printed.
 
     python tools/identity_probe.py --out profiles/r10/identity_probe.txt
@@ -28,29 +29,32 @@ from metalign_amd import _hip  # noqa: E402
 NACC, ACC_LEN, READ = cp.NACC, cp.ACC_LEN, cp.READ
 
 
-def end_to_end(say, d, reps):
+def end_to_end(say, d, reps, all_flags=False):
     import argparse as ap
-    from metalign_amd import map_and_profile as mp
+    from metalign_amd import cli, map_and_profile as mp
 
-    def run(flag):
+    def run(flags):
         args = ap.Namespace(infiles=[os.path.join(d, "probe.sam")], data="data/", db="NONE", dbinfo=os.path.join(d, "db_info.txt"),
                             input_type="sam", length_normalize=False, low_mem=False, min_abundance=10 ** -4, rank_renormalize=False,
                             output=os.path.join(d, "out.cami"), pct_id=0.5, no_quantify_unmapped=False, read_cutoff=1, sampleID="probe",
                             threads=4, verbose=False)
-        if flag:
-            args.identity = os.path.join(d, "identity.tsv")
+        for flag in flags:
+            setattr(args, flag, os.path.join(d, flag + ".tsv"))
         t0 = time.perf_counter()
         mp.map_main(args)
         return time.perf_counter() - t0
-    run(False)
-    t = [run(False) for _ in range(reps)]
-    say("map_and_profile end to end, no flag      %s ms   (median %.2f, spread %.2f)"
-        % (" ".join("%.2f" % (x * 1e3) for x in t), float(np.median(t)) * 1e3, (max(t) - min(t)) * 1e3))
-    if hasattr(mp, "_wants_identity"):
-        run(True)
-        t = [run(True) for _ in range(reps)]
-        say("map_and_profile end to end, --identity   %s ms   (median %.2f, spread %.2f)"
-            % (" ".join("%.2f" % (x * 1e3) for x in t), float(np.median(t)) * 1e3, (max(t) - min(t)) * 1e3))
+    # (the parser says which flags the commit under test has)
+    known = {a.dest for a in cli.parser_for("map_and_profile")._actions}
+    configs = [("no flag", ()), ("--identity", ("identity",))]
+    if all_flags:
+        configs.append(("--coverage --depth --identity", ("coverage", "depth", "identity")))
+    for label, flags in configs:
+        if not set(flags) <= known:
+            continue
+        run(flags)
+        t = [run(flags) for _ in range(reps)]
+        say("map_and_profile end to end, %-12s %s ms   (median %.2f, spread %.2f)"
+            % (label, " ".join("%.2f" % (x * 1e3) for x in t), float(np.median(t)) * 1e3, (max(t) - min(t)) * 1e3))
 
 
 def kernels(say, hip, rng, a):
@@ -152,6 +156,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--e2e", action="store_true", help="only the end-to-end runs")
     ap.add_argument("--kernels", action="store_true", help="only the kernels")
+    ap.add_argument("--all_flags", action="store_true", help="end to end also with --coverage --depth --identity together")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     out = open(a.out, "w") if a.out else None
@@ -172,7 +177,7 @@ def main():
         if not a.e2e:
             kernels(say, hip, rng, a)
             tokeniser(say, hip, accs, text, a)
-        end_to_end(say, d, a.reps)
+        end_to_end(say, d, a.reps, a.all_flags)
 
 
 if __name__ == "__main__":
