@@ -1029,6 +1029,24 @@ int mg_identity_result(mg_identity* h, uint64_t* alignments, uint64_t* columns, 
 int mg_identity_fetch_hist(mg_identity* h, const uint32_t* rows, uint32_t nrows, uint64_t* hist);
 void mg_identity_free(mg_identity* h);
 
+/* SIDE OUTPUTS FROM UNIQUELY ASSIGNED READS (--side_reads unique; metalign_amd/csrc/mg_sidemask.hip; the definition is
+ * metalign_amd/side_reads.py: unique_mask_of_records).
+ * d_out[i] = d_recs[i] for i < n, with FLAG bit 2048 set in flag_len where the record is masked: the bit by which the three
+ *   accumulators above (clean_read_hits' rule) do not count a record.  Nothing else of a record changes.  d_out == d_recs is
+ *   allowed (in place); the arrays must not overlap otherwise, and both are 16-byte aligned (else MG_ERR_ARG).
+ * d_assign: the verdict words of mg_profile_commit_assign_dev for the same records (group_base 0), u64[2 * nreads].  A record's
+ *   read ordinal is the number of records in [0, i] with MG_REC_NEW_BIT, minus one.  A record is kept when its ordinal lies in
+ *   [0, nreads), its accession row is below nref, it is not the line the read loop drops (a NEW record of read 0, or of a read
+ *   whose predecessor's kind is 0: scripts/map_and_profile.py:229-232), its read's kind is 1 and d_ref2tax[row] is the read's
+ *   dense taxon (w0 >> 2); every other record is masked.  d_ref2tax is never read at or above nref, d_assign never at or above
+ *   2 * nreads.
+ * d_stats2 (device, accumulated into): [0] += the records kept, [1] += the records whose ordinal fell outside [0, nreads) —
+ *   0 for the words of the same stream.
+ * Three launches per 2^31 records (NEW bits per tile, the scan of the tiles, the mask pass), asynchronous on the library stream
+ *   behind stage C's; the tile counts come from the library's pool.  n = 0 is legal. */
+int mg_records_mask_unique_dev(const mg_aln_rec* d_recs, uint64_t n, const uint64_t* d_assign, uint64_t nreads,
+                               const uint32_t* d_ref2tax, uint32_t nref, mg_aln_rec* d_out, uint64_t* d_stats2);
+
 /* Host-buffer convenience, single shard = whole stream. Capacities: mm_* as
  * above with mm_cap_reads / mm_cap_entries entries available. */
 int mg_profile_assign(const mg_aln_rec* recs, uint64_t nrecs,

@@ -52,6 +52,7 @@ EXPORTS = [
     "mg_depth_create", "mg_depth_add_dev", "mg_depth_finish", "mg_depth_fetch_rows", "mg_depth_fetch_windows", "mg_depth_free",
     "mg_sam_batch_edits_download", "mg_sam_batch_edits_device_ptr",
     "mg_identity_create", "mg_identity_add_dev", "mg_identity_result", "mg_identity_fetch_hist", "mg_identity_free",
+    "mg_records_mask_unique_dev",
     "mg_gunzip_open", "mg_gunzip_read", "mg_gunzip_close", "mg_zcat_files", "mg_stream_thin_file",
     "mg_inflate_dev", "mg_inflated_bytes", "mg_inflated_download", "mg_inflated_free", "mg_inflate_config", "mg_inflate_stats",
     "mg_sketch_genomes", "mg_sketch_genomes_prefix", "mg_db_upload", "mg_db_upload_sorted", "mg_db_ngenomes", "mg_db_max_hash", "mg_db_free",
@@ -2140,13 +2141,33 @@ class Hip:
         res['resident'] = ResidentProfile(shard, [d_recs, d_r2t, d_acc])
         return res
 
-    def profile_assign_dev_records(self, d_recs_ptr, n, ref2tax, ntax, pct_id, owners, resident=False, assign=False):
+    def records_mask_unique(self, d_recs, n, d_words, nreads, d_ref2tax, nref, d_out, check=True):
+        """mg_records_mask_unique_dev (--side_reads unique; metalign_amd/side_reads.py: unique_mask_of_records): n records at d_recs
+        -> d_out (may be d_recs), FLAG 2048 set in every record that is not unique evidence for its taxon by the verdict words at
+        d_words (uint64[2 * nreads], still on the device) and d_ref2tax (uint32[nref]).  -> (records kept, records whose read
+        ordinal fell outside the words); check: HipError when the second is not 0 — the words are another stream's.
+        Synchronises for the two counts."""
+        d_stats = self.array(np.zeros(2, dtype=np.uint64))
+        try:
+            self._chk(self.lib.mg_records_mask_unique_dev(_vp(d_recs), ctypes.c_uint64(int(n)), _vp(d_words), ctypes.c_uint64(int(nreads)),
+                                                          _vp(d_ref2tax), ctypes.c_uint32(int(nref)), _vp(d_out), _vp(d_stats.ptr)))
+            kept, outside = (int(x) for x in d_stats.download())
+        finally:
+            d_stats.free()
+        if check and outside:
+            raise HipError("%d of %d records belong to no read of the %d the verdict words hold" % (outside, n, nreads))
+        return kept, outside
+
+    def profile_assign_dev_records(self, d_recs_ptr, n, ref2tax, ntax, pct_id, owners, resident=False, assign=False, on_verdicts=None):
         """Stage C over records ALREADY in HBM (the device tokeniser's batch).  owners: objects to free with the
         result (they hold the records).  resident=False: the multimapped CSR is downloaded (same dict as
         profile_assign); True: it stays on the device (same dict as profile_assign_resident).
         assign=True (--read_assignments): also res['assign'] = uint64[2 * reads], every read's verdict words
         (mg_profile_commit_assign_dev), res['names'] = (bytes, offsets) when the first owner is a named SamBatch, and the
-        multimapped CSR downloaded whatever `resident` says (the rows of the multimapped reads are read from it)."""
+        multimapped CSR downloaded whatever `resident` says (the rows of the multimapped reads are read from it).
+        on_verdicts (--side_reads unique): called once, behind the commit, as on_verdicts(d_recs_ptr, n, d_words_ptr, nreads,
+        d_ref2tax_ptr, nref) while the records, the verdict words and ref2tax are all still on the device.  It runs the same
+        variant of the commit as assign=True, but on its own neither downloads the words nor asks for names."""
         ref2tax = np.ascontiguousarray(ref2tax, dtype=np.uint32)
         T = max(int(ntax), 1)
         d_r2t = self.array(ref2tax if ref2tax.size else np.zeros(1, np.uint32))
@@ -2158,7 +2179,7 @@ class Hip:
         shard = self.profile_begin_dev(d_recs_ptr, n, False, d_r2t.ptr, len(ref2tax), ntax, pct_id)
         base = d_acc.ptr
         words = None
-        if assign:
+        if assign or on_verdicts is not None:
             nreads = shard.ngroups if n else 0  # (the map-only pass; the array is sized by it)
             d_words = self.empty(max(2 * nreads, 2), np.uint64)
             try:
@@ -2166,7 +2187,10 @@ class Hip:
                                                         ctypes.c_uint32(ntax)))
                 shard.commit_assign(True, True, 0, base, base + 8 * T, base + 16 * T, base + 24 * T, d_words.ptr)
                 acc = d_acc.download()
-                words = d_words.download()[: 2 * nreads]
+                if on_verdicts is not None:
+                    on_verdicts(d_recs_ptr, n, d_words.ptr, nreads, d_r2t.ptr, len(ref2tax))
+                if assign:
+                    words = d_words.download()[: 2 * nreads]
             finally:
                 d_words.free()
         else:

@@ -91,9 +91,10 @@ def _decide(hits, next_pair1, next_pair2, pct_id):
     return 'U', [kept[0]], hitlen  # :176
 
 
-def read_assignments(lines, acc2info, pct_id):
-    """SAM lines (str or bytes) -> one (qname, cls, taxids, hit_bases) per read, in file order."""
-    prev, hits, opened = '', [], False
+def _replay(lines, acc2info, pct_id):
+    """The loop itself: per read and in file order (qname, cls, taxids, hit_bases, its retained lines [(line, fields, dropped)]),
+    dropped = the line the loop never counts in (:232).  read_assignments and side_reads.unique_lines are both this replay."""
+    prev, hits, opened, mine = '', [], False, []
     for line in lines:
         f = _fields_of(line)
         if f is None:
@@ -103,16 +104,24 @@ def read_assignments(lines, acc2info, pct_id):
             flag = int(f[1])
             if opened:
                 verdict = _decide(hits, bool(flag & 1 and flag & 64), bool(flag & 1 and flag & 128), pct_id)
-                yield (prev,) + verdict
+                yield (prev,) + verdict + (mine,)
                 dropped = verdict[0] == 'A'
             else:
                 dropped = True  # the phantom first boundary: a read without lines is Ambiguous (:155-156)
-            prev, hits, opened = f[0], [], True
+            prev, hits, opened, mine = f[0], [], True, []
             if dropped:
+                mine.append((line, f, True))
                 continue  # (:232: this line is never counted in)
         hits.append((f, taxid))
+        mine.append((line, f, False))
     if opened:
-        yield prev, 'N', [], -1
+        yield prev, 'N', [], -1, mine
+
+
+def read_assignments(lines, acc2info, pct_id):
+    """SAM lines (str or bytes) -> one (qname, cls, taxids, hit_bases) per read, in file order."""
+    for row in _replay(lines, acc2info, pct_id):
+        yield row[:4]
 
 
 def fold(rows):

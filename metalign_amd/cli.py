@@ -65,6 +65,10 @@ _OPTIONS = {
                           '--depth_window_size bases that an alignment touches, the mean depth and the covered bases.'),
     'depth_window_size': dict(type=int, default=1000, help='The width of the windows of --depth_windows (default 1000; 1 gives the '
                               'depth of every base).'),
+    'side_reads': dict(default='all', choices=['all', 'unique'],
+                       help='Which alignments --coverage, --depth, --depth_windows and --identity count: "all" that pass --pct_id (the '
+                            'default), or "unique": only those of reads the profile assigned uniquely, on an accession of the taxon '
+                            'the read was counted for (metalign_amd/side_reads.py is the definition).'),
     'multimap_iterations': dict(type=int, default=1, help='Iterate the reassignment of multimapped reads up to this many times: every '
                                 'iteration shares them in proportion to the bases the one before gave (metalign_amd/multimap.py is '
                                 'the definition). Default 1: the single step, in proportion to uniquely mapped bases.'),
@@ -86,7 +90,7 @@ _TOOLS = {
                  'low_mem', 'min_abundance', 'no_quantify_unmapped', 'output', 'pct_id', 'precise', 'rank_renormalize',
                  'read_cutoff', 'sampleID', 'sensitive', 'strain_level', 'temp_dir', 'threads', 'verbose',
                  'sketch_table', 'min_count', 'sketch_size', 'kmer_match', 'device_multimap', 'collate', 'read_assignments', 'coverage',
-                 'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size', 'identity']),
+                 'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size', 'identity', 'side_reads']),
     'select_db': dict(
         description='Run CMash and select a subset of the whole database to align to.',
         positionals=[('reads', dict(help='Reads file (FASTA / FASTQ, optionally .gz, or a BAM of reads).')),
@@ -102,7 +106,7 @@ _TOOLS = {
                  ('input_type', ['fastq', 'fasta', 'sam', 'AUTO']), 'length_normalize', 'low_mem', 'min_abundance',
                  'rank_renormalize', 'output', 'pct_id', 'no_quantify_unmapped', 'read_cutoff', 'sampleID', 'threads',
                  'verbose', 'device_multimap', 'collate', 'read_assignments', 'coverage',
-                 'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size', 'identity']),
+                 'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size', 'identity', 'side_reads']),
 }
 
 

@@ -29,7 +29,7 @@ import time
 
 import numpy as np
 
-from . import _hip, assignments, bam, cli, collate, coverage, identity
+from . import _hip, assignments, bam, cli, collate, coverage, identity, side_reads
 from .side_outputs import ASSIGNMENTS, COVERAGE, DEPTH, IDENTITY, FAMILIES, SideOutputs, check_flags, write_headers
 
 start = time.time()
@@ -484,6 +484,15 @@ def assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=True):
     return taxids2abs, multimapped, {}
 
 
+def _unique_feed(sides, hip, d_places, d_edits, pct_id):
+    """The on_verdicts hook of Hip.profile_assign_dev_records under --side_reads unique: the records, masked by their reads'
+    verdicts, go to the accumulators beside the side arrays at d_places / d_edits."""
+    def feed(d_recs, n, d_words, nreads, d_ref2tax, nref):
+        if n:  # (as add_batch: an empty stream adds nothing)
+            sides.add_unique_ptrs(hip, d_recs, d_places, d_edits, n, pct_id, d_words, nreads, d_ref2tax, nref)
+    return feed
+
+
 def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _resident=False, _paf=False, _bam=False, _collate=False,
                          _assignments=False, _sides=None):
     """map_and_process for a plain SAM FILE, without the text or the records ever being host arrays: the file goes up
@@ -497,7 +506,8 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
     are appended to args.read_assignments; never together with _collate (a named batch is not collated).
     _sides (a SideOutputs: --coverage, --depth / --depth_windows, --identity): the batch also carries the side arrays its families
     read — the records' places, their edits — which feed the accumulators before stage C takes the batch; the file's blocks are
-    appended to the outputs.  Its header lines give the lengths.  One tokenisation carries every side array that was asked for."""
+    appended to the outputs.  Its header lines give the lengths.  One tokenisation carries every side array that was asked for.
+    Under --side_reads unique (sides.unique) the accumulators are fed from inside stage C instead, through its on_verdicts hook."""
     assert not (_assignments and _collate)
     sides = _sides if _sides is not None else SideOutputs(args, (), path)
     assert not (sides and _paf)  # (check_flags refuses the pair)
@@ -556,9 +566,17 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
             if d_text is not None:
                 d_text.free()
         sides.open(hip, lengths, acc_index)  # (before stage C takes the batch over)
-        sides.add_batch(batch, float(args.pct_id))
-        res = hip.profile_assign_dev_records(batch.ptr, batch.count, ref2tax, len(taxids), float(args.pct_id), [batch],
-                                             resident=_resident, assign=_assignments)
+        if sides.unique:
+            # --side_reads unique: the records are fed from inside stage C, where every read's verdict is known and the batch
+            # (the collated one, with its permuted side arrays, where it was collated) is still alive
+            feed = _unique_feed(sides, hip, batch.places_ptr if sides.placed and batch.count else None,
+                                batch.edits_ptr if sides.edited and batch.count else None, float(args.pct_id))
+            res = hip.profile_assign_dev_records(batch.ptr, batch.count, ref2tax, len(taxids), float(args.pct_id), [batch],
+                                                 resident=_resident, assign=_assignments, on_verdicts=feed)
+        else:
+            sides.add_batch(batch, float(args.pct_id))
+            res = hip.profile_assign_dev_records(batch.ptr, batch.count, ref2tax, len(taxids), float(args.pct_id), [batch],
+                                                 resident=_resident, assign=_assignments)
         batch = None  # owned by the result now
     except BaseException:
         sides.free()
@@ -813,6 +831,31 @@ def _map_and_process_sided(args, instream, acc2info, taxid2info, _want_lists, _r
     assert edits is None or len(edit) == len(recs)
     hip = _hip.Hip.get()
     d_recs = hip.array(recs if len(recs) else np.zeros(1, _hip.REC_DTYPE))
+    if sides.unique:  # (--side_reads unique: the uploaded places and edits live until stage C has fed the accumulators)
+        d_place = d_edit = None
+        try:
+            try:
+                sides.open(hip, coverage.lengths_of(header, acc2info), acc_index)
+                if len(recs):
+                    d_place = hip.array(place.view(np.uint8)) if sides.placed else None
+                    d_edit = hip.array(edit.view(np.uint8)) if sides.edited else None
+            except BaseException:
+                d_recs.free()  # (stage C has not taken the records over yet)
+                raise
+            feed = _unique_feed(sides, hip, d_place.ptr if d_place is not None else None, d_edit.ptr if d_edit is not None else None,
+                                float(args.pct_id))
+            res = hip.profile_assign_dev_records(d_recs.ptr, len(recs), ref2tax, len(taxids), float(args.pct_id), [d_recs],
+                                                 resident=_resident, assign=_assignments, on_verdicts=feed)
+        except BaseException:
+            sides.free()
+            raise
+        finally:
+            if d_place is not None:
+                d_place.free()
+            if d_edit is not None:
+                d_edit.free()
+        sides.close(acc2info, taxid2info)
+        return _sided_tail(args, res, names, taxids, taxid2info, _want_lists, _assignments)
     try:
         sides.open(hip, coverage.lengths_of(header, acc2info), acc_index)
         if len(recs):
@@ -835,6 +878,11 @@ def _map_and_process_sided(args, instream, acc2info, taxid2info, _want_lists, _r
         raise
     res = hip.profile_assign_dev_records(d_recs.ptr, len(recs), ref2tax, len(taxids), float(args.pct_id), [d_recs],
                                          resident=_resident, assign=_assignments)
+    return _sided_tail(args, res, names, taxids, taxid2info, _want_lists, _assignments)
+
+
+def _sided_tail(args, res, names, taxids, taxid2info, _want_lists, _assignments):
+    """What _map_and_process_sided does with stage C's result."""
     if _assignments:
         res['names'] = _join_names(names)
         _append_assignments(args, assignment_rows(res, taxids))
@@ -1129,7 +1177,11 @@ def _compute_abundances_regrouped(args, infile, acc2info, tax2info, on_device, s
         done = map_and_process(args, collate.collated_lines(lines) if collating else lines, acc2info, tax2info, _want_lists=False,
                                _resident=on_device, _assignments=want_rows and not collating and seams_untouched,
                                _sides=None if collating else sides)
-        if collating:
+        if collating and sides.unique:
+            # (... but the unique ones on how the lines are grouped into reads: over the collated stream, as stage C sees it)
+            sides.append_from_definition(infile, lambda: side_reads.unique_lines(collate.collated_lines(lines_of(infile)), acc2info,
+                                                                                 args.pct_id), acc2info, tax2info)
+        elif collating:
             sides.append_from_definition(infile, lambda: lines_of(infile), acc2info, tax2info)
     if want_rows and collating:  # (a named batch is not collated: the rows of a collated input come from the definition)
         _append_assignments(args, assignments.read_assignments(collate.collated_lines(lines_of(infile)), acc2info, args.pct_id))

@@ -6,17 +6,26 @@ what it holds on the device, and how its device accumulator is opened and turned
 
 SideOutputs is the families wanted for ONE input file.  map_and_profile opens it, feeds it the records and closes it; the
 order is always coverage, depth, identity, and whatever was opened is freed on every way out.
+
+--side_reads unique (metalign_amd/side_reads.py is the definition): the accumulators are fed a copy of the records in which every
+record that is not unique evidence for its taxon carries FLAG 2048 (mg_records_mask_unique_dev), the bit by which none of them
+counts a record.  That needs stage C's verdicts, so the records are fed from inside stage C instead of before it.
 """
 import os
 import sys
 
 import numpy as np
 
-from . import _hip, assignments, coverage, depth, identity
+from . import _hip, assignments, coverage, depth, identity, side_reads
 
 
 def _flag(args, name):
     return getattr(args, name, 'NONE') not in (None, 'NONE')  # (callers build Namespaces without it)
+
+
+def reads_mode(args):
+    """--side_reads: 'all' (the default) or 'unique'."""
+    return getattr(args, 'side_reads', 'all')  # (callers build Namespaces without it)
 
 
 def source_label(args, path):
@@ -54,6 +63,10 @@ class _Family(_Flags):
     """side: the side array of a batch it reads ('places' / 'edits').  nomem: the exit text when the device refuses the memory,
     with the MB figure of nomem_mb."""
     side = nomem = None
+
+    def paths(self, args):
+        """The files it writes."""
+        return [getattr(args, f) for f in self.flags if _flag(args, f)]
 
     def open(self, args, hip, lengths, acc_index):
         """The device accumulator for one input file (lengths: coverage.lengths_of — the file's @SQ lines over db_info's)."""
@@ -208,6 +221,8 @@ def check_flags(args):
             sys.exit(fam.refuse_paf)
     if int(getattr(args, 'depth_window_size', 1000)) < 1:
         sys.exit('Error: --depth_window_size must be at least 1.')
+    if reads_mode(args) == 'unique' and not any(fam.wanted(args) for fam in FAMILIES):
+        sys.exit('Error: --side_reads unique needs one of --coverage, --depth, --depth_windows, --identity.')
 
 
 def write_headers(args):
@@ -215,6 +230,10 @@ def write_headers(args):
     for fam in (ASSIGNMENTS,) + FAMILIES:
         if fam.wanted(args):
             fam.write_header(args)
+            if fam in FAMILIES and reads_mode(args) == 'unique':
+                for path in fam.paths(args):
+                    with open(path, 'a') as out:
+                        out.write(side_reads.HEADER_LINE)
 
 
 class SideOutputs:
@@ -226,6 +245,8 @@ class SideOutputs:
         self.families = tuple(f for f in FAMILIES if f in families)
         self.placed = any(f.side == 'places' for f in self.families)
         self.edited = any(f.side == 'edits' for f in self.families)
+        self.reads = reads_mode(args)
+        self.unique = bool(self.families) and self.reads == 'unique'
         self._open = []  # (family, accumulator) of what is open
         self._lengths = self._acc_index = None
 
@@ -244,6 +265,8 @@ class SideOutputs:
         """What the accumulators and the side arrays of nrec records hold on the device."""
         # 8 B of place per record (and as much again where a collation permutes them), once for coverage and depth
         need = 16 * nrec if self.placed else 0
+        if self.unique:
+            need += 32 * nrec  # the masked copy of the records, and at most 16 B of verdict words per record
         return need + sum(f.device_bytes(self.args, lengths, nacc, nrec) for f in self.families)
 
     def open(self, hip, lengths, acc_index):
@@ -272,6 +295,22 @@ class SideOutputs:
         except BaseException:
             self.free()
             raise
+
+    def add_unique_ptrs(self, hip, d_recs, d_places, d_edits, n, pct_id, d_words, nreads, d_ref2tax, nref):
+        """add_ptrs under --side_reads unique, from inside stage C: the records go through mg_records_mask_unique_dev into a copy,
+        which is what the accumulators read.  Returns with the work done: the copy is freed on every way out."""
+        copy = None
+        try:
+            copy = hip.empty(16 * max(int(n), 1), np.uint8)
+            hip.records_mask_unique(d_recs, n, d_words, nreads, d_ref2tax, nref, copy.ptr)
+            self.add_ptrs(copy.ptr, d_places, d_edits, n, pct_id)
+            hip.sync()
+        except BaseException:
+            self.free()
+            raise
+        finally:
+            if copy is not None:
+                copy.free()
 
     def close(self, acc2info, taxid2info):
         """Every accumulator -> its block, appended to its file."""
