@@ -79,6 +79,18 @@ typedef struct mg_aln_edit {
   uint32_t cols;
 } mg_aln_edit;
 
+/* What a record puts on its reference, base by base (--variants; metalign_amd/variants.py): span 4-bit codes, code j for
+ * reference base pos0 + j — 0 .. 3 the read's A, C, G, T there, 4 any other base, 5 a base under a D or N gap — two per byte with
+ * the low nibble first, at pool[off .. off + (span + 1) / 2) of the pool the entries belong to.  Every entry starts on a byte; the
+ * unused high nibble of an odd span is 0.  span == 0: not piled (no place, SEQ `*`, a SEQ whose length is not what the CIGAR's
+ * M, X, I and S ops consume, or a span above MG_MAX_PILE_SPAN); off and pos0 are then 0. */
+typedef struct mg_aln_bases {
+  uint64_t off;
+  uint32_t pos0;
+  uint32_t span;
+} mg_aln_bases;
+#define MG_MAX_PILE_SPAN ((1u << 21) - 1u)
+
 /* ------------------------------------------------------------------------ *
  * Lifecycle, errors, raw device memory
  * ------------------------------------------------------------------------ */
@@ -102,7 +114,7 @@ int mg_device_count(void);
  *   return their batch keyed and not yet collated); genome_slab_bytes (mg_genomes_stream_open: the size of a page-locked slab,
  *   default 8 MiB, at least 4 KiB), genome_guard (test hook: mg_genomes_parse_dev fills the 16 bytes behind its bases and the
  *   word behind its offsets with 0xa5 before its kernels run); cov_grid (test hook, k3_grid's meaning for k_cov_add /
- *   k_cov_count, mg_coverage.hip); depth_grid (test hook, the same for every grid of mg_depth.hip); ident_grid (test hook, the same for k_ident_add, mg_identity.hip); mm_hash_bits (test hook, mg_profile_mm_iterate_dev: only this many low bits of a list's hash
+ *   k_cov_count, mg_coverage.hip); depth_grid (test hook, the same for every grid of mg_depth.hip); ident_grid (test hook, the same for k_ident_add, mg_identity.hip); var_grid (test hook, the same for every grid of mg_variants.hip); mm_hash_bits (test hook, mg_profile_mm_iterate_dev: only this many low bits of a list's hash
  *   are kept, so that different lists collide).
  * Needs no device and no mg_init.  MG_ERR_ARG for a key that does not exist. */
 int mg_debug_set(const char* key, int64_t value);
@@ -941,12 +953,16 @@ int mg_sam_batch_names_download(const mg_sam_batch* b, uint64_t* off, uint8_t* b
  * collated has its places permuted with its records.  PLACES with paf = 1: MG_ERR_ARG (a PAF line has no POS / CIGAR columns).  A file stream keeps keys only to collate
  * by them: KEYS without COLLATE is MG_ERR_ARG there.  EDITS (--identity): mg_aln_edit[count] in record order, the same from SAM
  * text and from BAM (a BAM record's aux fields are read as they render); it combines with the others exactly as PLACES does and
- * is permuted with the records by a collation.  EDITS with paf = 1: MG_ERR_ARG. */
+ * is permuted with the records by a collation.  EDITS with paf = 1: MG_ERR_ARG.  BASES (--variants): mg_aln_bases[count] in
+ * record order and the pool of 4-bit codes they point into, the same from SAM text and from BAM; it combines with the others as
+ * PLACES does — a collation permutes the 16-byte entries with the records, the pool does not move — and a file stream with it
+ * never thins its text (thinning drops SEQ).  BASES with paf = 1: MG_ERR_ARG. */
 #define MG_BATCH_KEYS 1u
 #define MG_BATCH_NAMES 2u
 #define MG_BATCH_PLACES 4u
 #define MG_BATCH_COLLATE 8u
 #define MG_BATCH_EDITS 16u
+#define MG_BATCH_BASES 32u
 int mg_sam_tokenize_dev_ex(const uint8_t* d_text, uint64_t nbytes, int paf, const mg_acc_index* ix, const char* prev_qname,
                            mg_sam_batch** out, int* err_kind, uint64_t* err_line, unsigned want);
 int mg_sam_tokenize_ex(const uint8_t* text, uint64_t nbytes, int paf, const mg_acc_index* ix, const char* prev_qname,
@@ -964,6 +980,10 @@ int mg_sam_batch_places_device_ptr(const mg_sam_batch* b, const mg_aln_place** d
 /* The edits of a batch tokenised with MG_BATCH_EDITS.  MG_ERR_STATE for a batch without edits. */
 int mg_sam_batch_edits_download(const mg_sam_batch* b, mg_aln_edit* edits);
 int mg_sam_batch_edits_device_ptr(const mg_sam_batch* b, const mg_aln_edit** d_edits);
+/* The entries and the pool of a batch tokenised with MG_BATCH_BASES.  MG_ERR_STATE for a batch without them.  device_ptr also
+ * gives the size of the pool in bytes, which is what download writes to `pool`. */
+int mg_sam_batch_bases_download(const mg_sam_batch* b, mg_aln_bases* entries, uint8_t* pool);
+int mg_sam_batch_bases_device_ptr(const mg_sam_batch* b, const mg_aln_bases** d_entries, const uint8_t** d_pool, uint64_t* pool_bytes);
 uint64_t mg_sam_batch_count(const mg_sam_batch* b);
 const char* mg_sam_batch_last_qname(const mg_sam_batch* b);
 int mg_sam_batch_device_ptr(const mg_sam_batch* b, const mg_aln_rec** d_recs);
@@ -1028,6 +1048,36 @@ int mg_identity_add_dev(mg_identity* h, const mg_aln_rec* d_recs, const mg_aln_e
 int mg_identity_result(mg_identity* h, uint64_t* alignments, uint64_t* columns, uint64_t* edits, uint64_t* unscored);
 int mg_identity_fetch_hist(mg_identity* h, const uint32_t* rows, uint32_t nrows, uint64_t* hist);
 void mg_identity_free(mg_identity* h);
+
+/* PER-SITE ALLELE COUNTS AND STRAIN DIVERSITY (--variants, --variant_sites; metalign_amd/csrc/mg_variants.hip; the definition is
+ * metalign_amd/variants.py).
+ * create: u32[4] per reference base (the reads' A, C, G and T there), zeroed, accession a at a site offset held in 64 bits, and
+ *   the per-accession sums.  nacc = 0 and lengths of 0 are legal.  MG_ERR_NOMEM (the byte count in the message) when the counts
+ *   do not fit.
+ * add_dev: records, their entries and the pool the entries point into (device pointers, n records and entries; any number of
+ *   calls, which sum; n = 0 is legal).  A record counts by clean_read_hits' rule, as mg_coverage_add_dev.  A counting record with
+ *   span > 0, an accession row < nacc and pos0 < its accession's length is piled: 1 more alignment of its accession, and for
+ *   every j < span with pos0 + j < length and code j below 4 one add to that site's count of that code.  Every other counting
+ *   record is one more unpiled.  The pool is read only inside the entries of piled records.  Asynchronous on the library stream.
+ * finish: judges every site against min_depth (at least 2), min_count (at least 1) and freq_permille (0 .. 500; else
+ *   MG_ERR_ARG): alignments, callable, polymorphic, pairs, discordant (u64[nacc] each), *unpiled, and *nsites = the polymorphic
+ *   sites, which it keeps for fetch_sites.  Synchronises.  May be called again, with other thresholds or after further add_dev
+ *   calls; the sites kept are those of the last call.
+ * fetch_sites: out[nsites], ordered by (accession row, pos0).  MG_ERR_STATE before a finish. */
+typedef struct mg_variants mg_variants;
+typedef struct mg_variant_site {
+  uint32_t acc;  /* accession row */
+  uint32_t pos0; /* 0-based position */
+  uint32_t n[4]; /* the reads' A, C, G, T */
+} mg_variant_site;
+int mg_variants_create(const uint64_t* lengths, uint32_t nacc, mg_variants** out);
+int mg_variants_add_dev(mg_variants* h, const mg_aln_rec* d_recs, const mg_aln_bases* d_bases, const uint8_t* d_pool, uint64_t n,
+                        double pct_id);
+int mg_variants_finish(mg_variants* h, uint32_t min_depth, uint32_t min_count, uint32_t freq_permille, uint64_t* alignments,
+                       uint64_t* callable_sites, uint64_t* polymorphic_sites, uint64_t* pairs, uint64_t* discordant, uint64_t* unpiled,
+                       uint64_t* nsites);
+int mg_variants_fetch_sites(mg_variants* h, mg_variant_site* out);
+void mg_variants_free(mg_variants* h);
 
 /* SIDE OUTPUTS FROM UNIQUELY ASSIGNED READS (--side_reads unique; metalign_amd/csrc/mg_sidemask.hip; the definition is
  * metalign_amd/side_reads.py: unique_mask_of_records).

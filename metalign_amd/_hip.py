@@ -52,6 +52,8 @@ EXPORTS = [
     "mg_depth_create", "mg_depth_add_dev", "mg_depth_finish", "mg_depth_fetch_rows", "mg_depth_fetch_windows", "mg_depth_free",
     "mg_sam_batch_edits_download", "mg_sam_batch_edits_device_ptr",
     "mg_identity_create", "mg_identity_add_dev", "mg_identity_result", "mg_identity_fetch_hist", "mg_identity_free",
+    "mg_sam_batch_bases_download", "mg_sam_batch_bases_device_ptr",
+    "mg_variants_create", "mg_variants_add_dev", "mg_variants_finish", "mg_variants_fetch_sites", "mg_variants_free",
     "mg_records_mask_unique_dev",
     "mg_gunzip_open", "mg_gunzip_read", "mg_gunzip_close", "mg_zcat_files", "mg_stream_thin_file",
     "mg_inflate_dev", "mg_inflated_bytes", "mg_inflated_download", "mg_inflated_free", "mg_inflate_config", "mg_inflate_stats",
@@ -87,14 +89,20 @@ BATCH_EDITS = 16
 EDIT_DTYPE = np.dtype([("nm", np.uint32), ("cols", np.uint32)])
 EDIT_NONE = 0xFFFFFFFF
 IDENTITY_BINS = 1001
+# ... and what it piles on its reference (mg_aln_bases; --variants): span 4-bit codes at pool[off ...], span = 0: not piled
+BATCH_BASES = 32
+BASES_DTYPE = np.dtype([("off", np.uint64), ("pos0", np.uint32), ("span", np.uint32)])
+MAX_PILE_SPAN = (1 << 21) - 1
+# a polymorphic site of a VariantsAcc (mg_variant_site)
+VARIANT_SITE_DTYPE = np.dtype([("acc", np.uint32), ("pos0", np.uint32), ("n", np.uint32, (4,))])
 # a kept window of a Depth (mg_depth_window) and the histogram's bins (depth clamped to DEPTH_BINS - 1)
 DEPTH_WINDOW_DTYPE = np.dtype([("index", np.uint64), ("depth_sum", np.uint64), ("acc", np.uint32), ("covered", np.uint32)])
 DEPTH_BINS = 4096
 
 
-def _want(keyed=False, named=False, placed=False, collate=False, edited=False):
+def _want(keyed=False, named=False, placed=False, collate=False, edited=False, based=False):
     return ctypes.c_uint((BATCH_KEYS if keyed else 0) | (BATCH_NAMES if named else 0) | (BATCH_PLACES if placed else 0)
-                         | (BATCH_COLLATE if collate else 0) | (BATCH_EDITS if edited else 0))
+                         | (BATCH_COLLATE if collate else 0) | (BATCH_EDITS if edited else 0) | (BATCH_BASES if based else 0))
 
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -143,6 +151,7 @@ def load_library(path=LIB_PATH):
     lib.mg_coverage_free.restype = None
     lib.mg_depth_free.restype = None
     lib.mg_identity_free.restype = None
+    lib.mg_variants_free.restype = None
     lib.mg_shutdown.restype = None
     return lib
 
@@ -1065,6 +1074,33 @@ class SamBatch:
         self.hip._chk(self.hip.lib.mg_sam_batch_edits_device_ptr(self.handle, ctypes.byref(p)))
         return p.value or 0
 
+    def bases(self):
+        """The entries and the pool of a batch tokenised with based=True: (BASES_DTYPE[count] in record order, the pool's bytes)
+        (mg_sam_batch_bases_download); ERR_STATE without them."""
+        e, p, nb = _vp(), _vp(), ctypes.c_uint64(0)
+        self.hip._chk(self.hip.lib.mg_sam_batch_bases_device_ptr(self.handle, ctypes.byref(e), ctypes.byref(p), ctypes.byref(nb)))
+        ent = np.zeros(self.count, dtype=BASES_DTYPE)
+        pool = np.zeros(max(int(nb.value), 1), dtype=np.uint8)
+        self.hip._chk(self.hip.lib.mg_sam_batch_bases_download(self.handle, _vp(ent.ctypes.data if self.count else None), _vp(pool.ctypes.data)))
+        return ent, pool[:int(nb.value)].tobytes()
+
+    def _bases_ptrs(self):
+        e, p, nb = _vp(), _vp(), ctypes.c_uint64(0)
+        self.hip._chk(self.hip.lib.mg_sam_batch_bases_device_ptr(self.handle, ctypes.byref(e), ctypes.byref(p), ctypes.byref(nb)))
+        return e.value or 0, p.value or 0, int(nb.value)
+
+    @property
+    def bases_ptr(self):
+        return self._bases_ptrs()[0]
+
+    @property
+    def pool_ptr(self):
+        return self._bases_ptrs()[1]
+
+    @property
+    def pool_bytes(self):
+        return self._bases_ptrs()[2]
+
     def collate(self, want_perm=False):
         """A keyed batch regrouped by read in place, its keys freed (mg_sam_batch_collate_dev; metalign_amd/collate.py is the
         definition).  want_perm: -> uint64[count], the index of the record that now comes t-th."""
@@ -1184,6 +1220,76 @@ class IdentityAcc(_SideAccumulator):
             nz = np.flatnonzero(H[r])
             per[a] = dict(zip(nz.tolist(), H[r][nz].tolist()))
         return aln, cols, eds, unscored, per
+
+
+class VariantsAcc(_SideAccumulator):
+    """Four uint32 per reference base on the device — the reads' A, C, G and T there — and the per-accession sums (mg_variants_*;
+    metalign_amd/variants.py is the definition).  Its side is a pair: a batch's entries (BASES_DTYPE[]) and the pool of 4-bit codes
+    they point into.  lengths: one per accession row.  HipError with code ERR_NOMEM when the counts do not fit."""
+    _add, _free, _side_ptr, _side_dtype = "mg_variants_add_dev", "mg_variants_free", "bases_ptr", BASES_DTYPE
+
+    def __init__(self, hip, lengths):
+        self.hip = hip
+        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
+        self.nacc = int(ln.size)
+        h = _vp()
+        hip._chk(hip.lib.mg_variants_create(_np(ln if ln.size else np.zeros(1, np.uint64), ctypes.c_uint64), ctypes.c_uint32(self.nacc),
+                                            ctypes.byref(h)))
+        self.handle = h
+        self.nsites = 0
+
+    def add_ptr(self, d_recs, d_side, n, pct_id):
+        """n records beside d_side = (entries, pool) at device pointers (asynchronous, as _SideAccumulator.add_ptr)."""
+        d_entries, d_pool = d_side if d_side is not None else (None, None)
+        self.hip._chk(self.hip.lib.mg_variants_add_dev(self.handle, _vp(d_recs), _vp(d_entries), _vp(d_pool), ctypes.c_uint64(int(n)),
+                                                       ctypes.c_double(float(pct_id))))
+
+    def add_batch(self, batch, pct_id):
+        """A SamBatch tokenised with based=True."""
+        if batch.count:
+            self.add_ptr(batch.ptr, (batch.bases_ptr, batch.pool_ptr), batch.count, pct_id)
+            self.hip.sync()
+
+    def add(self, recs, entries, pool, pct_id):
+        """Host arrays REC_DTYPE[n], BASES_DTYPE[n] and the pool's bytes."""
+        recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
+        entries = np.ascontiguousarray(entries, dtype=BASES_DTYPE)
+        pool = np.frombuffer(bytes(pool), dtype=np.uint8)
+        assert len(recs) == len(entries)
+        if not len(recs):
+            self.add_ptr(None, None, 0, pct_id)
+            return
+        d_r, d_e = self.hip.array(recs.view(np.uint8)), self.hip.array(entries.view(np.uint8))
+        d_p = self.hip.array(pool if pool.size else np.zeros(16, np.uint8))
+        try:
+            self.add_ptr(d_r.ptr, (d_e.ptr, d_p.ptr), len(recs), pct_id)
+            self.hip.sync()
+        finally:
+            d_r.free()
+            d_e.free()
+            d_p.free()
+
+    def finish(self, min_depth, min_count, permille):
+        """Every site judged (mg_variants_finish) -> (alignments, callable, polymorphic, pairs, discordant) uint64[nacc] each,
+        unpiled, nsites; may be called again."""
+        out = [np.zeros(max(self.nacc, 1), dtype=np.uint64) for _ in range(5)]
+        unpiled, nsites = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.hip._chk(self.hip.lib.mg_variants_finish(self.handle, ctypes.c_uint32(int(min_depth)), ctypes.c_uint32(int(min_count)),
+                                                      ctypes.c_uint32(int(permille)), *[_np(a, ctypes.c_uint64) for a in out],
+                                                      ctypes.byref(unpiled), ctypes.byref(nsites)))
+        self.nsites = int(nsites.value)
+        return tuple(a[:self.nacc] for a in out) + (int(unpiled.value), self.nsites)
+
+    def fetch_sites(self):
+        """-> VARIANT_SITE_DTYPE[nsites], the polymorphic sites of the last finish(), ordered by (accession row, pos0)."""
+        sites = np.zeros(self.nsites + 1, dtype=VARIANT_SITE_DTYPE)
+        self.hip._chk(self.hip.lib.mg_variants_fetch_sites(self.handle, _vp(sites.ctypes.data)))
+        return sites[:self.nsites]
+
+    def result(self, min_depth, min_count, permille):
+        """finish() and the fetch -> (alignments, callable, polymorphic, pairs, discordant, unpiled, sites)."""
+        r = self.finish(min_depth, min_count, permille)
+        return r[:6] + (self.fetch_sites(),)
 
 
 class Depth(_SideAccumulator):
@@ -1338,6 +1444,10 @@ class Hip:
     def identity(self, nacc):
         """An IdentityAcc over nacc accession rows (mg_identity_create)."""
         return IdentityAcc(self, nacc)
+
+    def variants(self, lengths):
+        """A VariantsAcc over accessions of these lengths (mg_variants_create)."""
+        return VariantsAcc(self, lengths)
 
     def depth(self, lengths, window=0):
         """A Depth over accessions of these lengths, with windows of `window` bases (mg_depth_create)."""
@@ -1695,16 +1805,16 @@ class Hip:
         return n
 
     def sam_tokenize_dev_batch(self, d_text, nbytes, acc_index, prev_qname="", paf=False, named=False, placed=False, keyed=False,
-                               collate=False, edited=False):
+                               collate=False, edited=False, based=False):
         """SAM (or, paf=True, PAF) text resident in HBM -> SamBatch (records stay on the device).  SamParseError as
         sam_tokenize.  named: the batch also carries the reads' names (mg_sam_tokenize_named_dev; SamBatch.names).  placed (with
         any of named / keyed / collate): their places too (mg_sam_tokenize_dev_ex; SamBatch.places)."""
         h = _vp()
         kind, line = ctypes.c_int(0), ctypes.c_uint64(0)
-        if placed or keyed or collate or edited:  # (edited: the records' edits too, SamBatch.edits)
+        if placed or keyed or collate or edited or based:  # (edited: the records' edits too, SamBatch.edits; based: SamBatch.bases)
             rc = self.lib.mg_sam_tokenize_dev_ex(_vp(d_text), ctypes.c_uint64(nbytes), ctypes.c_int(1 if paf else 0), acc_index.handle,
                                                  ctypes.c_char_p(prev_qname.encode()), ctypes.byref(h), ctypes.byref(kind), ctypes.byref(line),
-                                                 _want(keyed, named, placed, collate, edited))
+                                                 _want(keyed, named, placed, collate, edited, based))
         elif named:
             rc = self.lib.mg_sam_tokenize_named_dev(_vp(d_text), ctypes.c_uint64(nbytes), ctypes.c_int(1 if paf else 0), acc_index.handle,
                                                     ctypes.c_char_p(prev_qname.encode()), ctypes.byref(h), ctypes.byref(kind), ctypes.byref(line))
@@ -1747,18 +1857,18 @@ class Hip:
             d_p.free()
 
     def sam_stream_file(self, path, acc_index, paf=False, offset=0, length=0, chunk_bytes=0, nthreads=0, collate=False, named=False,
-                        placed=False, edited=False):
+                        placed=False, edited=False, based=False):
         """The alignment file (SAM; paf=True: PAF; plain, gzip or BGZF) -> SamBatch, streamed through page-locked chunks
         inside the library (mg_sam_stream_file): the file read, the upload and the tokeniser overlap, and the text never
         exists as a host array.  SamParseError for a line the reference cannot parse.  placed: the batch carries the records'
         places (mg_sam_stream_file_ex), with collate or named where those are on."""
         h = _vp()
         kind, line = ctypes.c_int(0), ctypes.c_uint64(0)
-        if placed or edited:  # (edited: and / or their edits)
+        if placed or edited or based:  # (edited: and / or their edits; based: their entries and pool)
             rc = self.lib.mg_sam_stream_file_ex(os.fsencode(path), ctypes.c_int(1 if paf else 0), acc_index.handle, ctypes.c_uint64(int(offset)),
                                                 ctypes.c_uint64(int(length)), ctypes.c_uint64(int(chunk_bytes)), ctypes.c_int(int(nthreads)),
                                                 ctypes.byref(h), ctypes.byref(kind), ctypes.byref(line),
-                                                _want(False, named, placed, collate, edited))
+                                                _want(False, named, placed, collate, edited, based))
             if rc != 0 and kind.value:
                 raise SamParseError(kind.value, line.value)
             self._chk(rc)
@@ -1775,16 +1885,17 @@ class Hip:
         self._chk(rc)
         return SamBatch(self, h)
 
-    def bam_stream_file(self, path, acc_index, chunk_bytes=0, nthreads=0, collate=False, named=False, placed=False, edited=False):
+    def bam_stream_file(self, path, acc_index, chunk_bytes=0, nthreads=0, collate=False, named=False, placed=False, edited=False,
+                        based=False):
         """A BAM file -> SamBatch: the records its SAM rendering gives through sam_stream_file (mg_bam_stream_file).  SamParseError
         for a record whose rendering the reference cannot parse, that the device does not decide (kind 6) or that is not a BAM
         record the package takes (kind 7); `line` is the record's number within its piece."""
         h = _vp()
         kind, rec = ctypes.c_int(0), ctypes.c_uint64(0)
-        if placed or edited:  # (the batch carries the records' places and / or edits: mg_bam_stream_file_ex)
+        if placed or edited or based:  # (the batch carries the records' places, edits and / or bases: mg_bam_stream_file_ex)
             rc = self.lib.mg_bam_stream_file_ex(os.fsencode(path), acc_index.handle, ctypes.c_uint64(int(chunk_bytes)), ctypes.c_int(int(nthreads)),
                                                 ctypes.byref(h), ctypes.byref(kind), ctypes.byref(rec),
-                                                _want(False, named, placed, collate, edited))
+                                                _want(False, named, placed, collate, edited, based))
             if rc != 0 and kind.value:
                 raise SamParseError(kind.value, rec.value)
             self._chk(rc)
@@ -1801,7 +1912,7 @@ class Hip:
         return SamBatch(self, h)
 
     def bam_tokenize_dev(self, d_bytes, nbytes, refmap, acc_index, prev_qname="", final=True, keyed=False, named=False, placed=False,
-                         edited=False, collate=False):
+                         edited=False, collate=False, based=False):
         """BAM record bytes resident in HBM (behind the header) -> (SamBatch, consumed) (mg_bam_tokenize_dev); refmap: the accession row
         of every header reference (-1: none, -2: not one SAM field).  SamParseError as bam_stream_file."""
         rm = np.ascontiguousarray(refmap, dtype=np.int32)
@@ -1812,8 +1923,8 @@ class Hip:
             assert not keyed
             fn = self.lib.mg_bam_tokenize_named_dev
         extra = ()
-        if placed or edited or collate:  # (the batch carries the records' places and / or edits)
-            fn, extra = self.lib.mg_bam_tokenize_dev_ex, (_want(keyed, named, placed, collate, edited),)
+        if placed or edited or collate or based:  # (the batch carries the records' places, edits and / or bases)
+            fn, extra = self.lib.mg_bam_tokenize_dev_ex, (_want(keyed, named, placed, collate, edited, based),)
         rc = fn(_vp(d_bytes), ctypes.c_uint64(nbytes), _np(rm if rm.size else np.zeros(1, np.int32), ctypes.c_int32),
                                           ctypes.c_uint32(rm.size), acc_index.handle, ctypes.c_char_p(prev_qname.encode()),
                                           ctypes.c_int(1 if final else 0), ctypes.byref(used), ctypes.byref(h), ctypes.byref(kind),
@@ -1833,7 +1944,7 @@ class Hip:
                                               ctypes.c_uint32(len(names)), ctypes.byref(h)))
         return AccIndex(self, h)
 
-    def sam_tokenize(self, text, acc_index, prev_qname="", paf=False, named=False, placed=False, edited=False):
+    def sam_tokenize(self, text, acc_index, prev_qname="", paf=False, named=False, placed=False, edited=False, based=False):
         """One chunk of SAM (paf=True: PAF) text (ending on a line boundary) -> (records REC_DTYPE[], QNAME of its last
         retained line).  Raises SamParseError for a line the reference cannot parse.  named: -> (records, last QNAME, (name bytes,
         offsets)) — the names of the reads that open in this chunk (mg_sam_tokenize_named)."""
@@ -1841,10 +1952,11 @@ class Hip:
         h = _vp()
         kind, line = ctypes.c_int(0), ctypes.c_uint64(0)
         src = buf if buf.size else np.zeros(1, np.uint8)
-        if placed or edited:  # (at the end of what is returned: the records' places, PLACE_DTYPE[], then their edits, EDIT_DTYPE[])
+        if placed or edited or based:  # (at the end of what is returned: the records' places, PLACE_DTYPE[], then their edits,
+            # EDIT_DTYPE[], then (entries BASES_DTYPE[], the pool's bytes))
             rc = self.lib.mg_sam_tokenize_ex(_np(src, ctypes.c_uint8), ctypes.c_uint64(buf.size), ctypes.c_int(1 if paf else 0),
                                              acc_index.handle, ctypes.c_char_p(prev_qname.encode()), ctypes.byref(h),
-                                             ctypes.byref(kind), ctypes.byref(line), _want(False, named, placed, False, edited))
+                                             ctypes.byref(kind), ctypes.byref(line), _want(False, named, placed, False, edited, based))
         elif named:
             rc = self.lib.mg_sam_tokenize_named(_np(src, ctypes.c_uint8), ctypes.c_uint64(buf.size), ctypes.c_int(1 if paf else 0),
                                                 acc_index.handle, ctypes.c_char_p(prev_qname.encode()), ctypes.byref(h),
@@ -1872,6 +1984,13 @@ class Hip:
                 ed = np.zeros(n, dtype=EDIT_DTYPE)
                 self._chk(self.lib.mg_sam_batch_edits_download(h, _vp(ed.ctypes.data if n else None)))
                 tail = tail + (ed,)
+            if based:
+                e, p, nb = _vp(), _vp(), ctypes.c_uint64(0)
+                self._chk(self.lib.mg_sam_batch_bases_device_ptr(h, ctypes.byref(e), ctypes.byref(p), ctypes.byref(nb)))
+                ent = np.zeros(n, dtype=BASES_DTYPE)
+                pool = np.zeros(max(int(nb.value), 1), dtype=np.uint8)
+                self._chk(self.lib.mg_sam_batch_bases_download(h, _vp(ent.ctypes.data if n else None), _vp(pool.ctypes.data)))
+                tail = tail + ((ent, pool[:int(nb.value)].tobytes()),)
             if named:
                 nr, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
                 self._chk(self.lib.mg_sam_batch_names_size(h, ctypes.byref(nr), ctypes.byref(nb)))

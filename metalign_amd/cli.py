@@ -65,6 +65,17 @@ _OPTIONS = {
                           '--depth_window_size bases that an alignment touches, the mean depth and the covered bases.'),
     'depth_window_size': dict(type=int, default=1000, help='The width of the windows of --depth_windows (default 1000; 1 gives the '
                               'depth of every base).'),
+    'variants': dict(default='NONE', help='Also write per-genome strain diversity here (TSV): per accession (S rows) and per genome '
+                     '(G rows) the piled alignments, the callable and the polymorphic sites, the read pairs compared and the '
+                     'discordant ones, nucleotide diversity pi and polymorphic sites per kb, from the read bases of the alignments '
+                     'stage C keeps (metalign_amd/variants.py is the definition). SAM / BAM input, one process only.'),
+    'variant_sites': dict(default='NONE', help='Also write every polymorphic site here (TSV): accession, position, depth, the '
+                          'reads\' A, C, G and T, the major allele and the variant alleles.'),
+    'variant_min_depth': dict(type=int, default=5, help='A site is callable from this many A / C / G / T reads on (default 5, at '
+                              'least 2).'),
+    'variant_min_count': dict(type=int, default=2, help='A variant allele has at least this many reads (default 2, at least 1).'),
+    'variant_min_freq': dict(type=float, default=0.05, help='... and at least this share of the site\'s depth (default 0.05, within '
+                             '0 to 0.5; compared in parts per thousand).'),
     'side_reads': dict(default='all', choices=['all', 'unique'],
                        help='Which alignments --coverage, --depth, --depth_windows and --identity count: "all" that pass --pct_id (the '
                             'default), or "unique": only those of reads the profile assigned uniquely, on an accession of the taxon '
@@ -90,7 +101,8 @@ _TOOLS = {
                  'low_mem', 'min_abundance', 'no_quantify_unmapped', 'output', 'pct_id', 'precise', 'rank_renormalize',
                  'read_cutoff', 'sampleID', 'sensitive', 'strain_level', 'temp_dir', 'threads', 'verbose',
                  'sketch_table', 'min_count', 'sketch_size', 'kmer_match', 'device_multimap', 'collate', 'read_assignments', 'coverage',
-                 'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size', 'identity', 'side_reads']),
+                 'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size', 'identity', 'side_reads',
+                 'variants', 'variant_sites', 'variant_min_depth', 'variant_min_count', 'variant_min_freq']),
     'select_db': dict(
         description='Run CMash and select a subset of the whole database to align to.',
         positionals=[('reads', dict(help='Reads file (FASTA / FASTQ, optionally .gz, or a BAM of reads).')),
@@ -106,7 +118,8 @@ _TOOLS = {
                  ('input_type', ['fastq', 'fasta', 'sam', 'AUTO']), 'length_normalize', 'low_mem', 'min_abundance',
                  'rank_renormalize', 'output', 'pct_id', 'no_quantify_unmapped', 'read_cutoff', 'sampleID', 'threads',
                  'verbose', 'device_multimap', 'collate', 'read_assignments', 'coverage',
-                 'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size', 'identity', 'side_reads']),
+                 'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size', 'identity', 'side_reads',
+                 'variants', 'variant_sites', 'variant_min_depth', 'variant_min_count', 'variant_min_freq']),
 }
 
 

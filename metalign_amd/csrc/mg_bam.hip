@@ -224,7 +224,7 @@ static int bam_chain_dev(const uint8_t* d_bytes, uint64_t nbytes, int32_t n_ref,
 
 int bam_tokenize_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* d_refmap, int32_t n_ref, const char* prev_qname,
                             bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec, bool keyed, bool named,
-                            bool placed, bool edited) {
+                            bool placed, bool edited, bool based) {
   MG_REQUIRE_READY();
   if (!out || !d_refmap) return fail(MG_ERR_ARG, "null argument");
   *out = nullptr;
@@ -243,6 +243,7 @@ int bam_tokenize_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32
     if (named) MG_TRY(names_empty(sb.get()));
     if (placed) MG_TRY(places_empty(sb.get()));
     if (edited) MG_TRY(edits_empty(sb.get()));
+    if (based) MG_TRY(bases_empty(sb.get()));
     *out = sb.release();
     return MG_OK;
   }
@@ -288,12 +289,14 @@ int bam_tokenize_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32
     }
     // (placed: pos and the ops M, D, N, X of the record body — k_bam_place, beside the other steps over the emitted records)
     MG_TRY(aln_emit_retained(d_bytes, d_lines, d_ret, d_rank, nrec, nret, d_prev, (uint32_t)plen, sb.get(), keyed, named,
-                             placed ? kPlaceBam : kPlaceNone, nullptr, edited ? kPlaceBam : kPlaceNone));
+                             placed ? kPlaceBam : kPlaceNone, nullptr, edited ? kPlaceBam : kPlaceNone, nullptr,
+                             based ? kPlaceBam : kPlaceNone));
   } else {
     MG_TRY(sb->recs.alloc(16));
     if (named) MG_TRY(names_empty(sb.get()));
     if (placed) MG_TRY(places_empty(sb.get()));
     if (edited) MG_TRY(edits_empty(sb.get()));
+    if (based) MG_TRY(bases_empty(sb.get()));
   }
   sb->nrecs = nret;
   *out = sb.release();
@@ -451,7 +454,7 @@ extern "C" {
 
 static int bam_tokenize_dev_impl(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* refmap, uint32_t nref, const mg_acc_index* ix,
                                 const char* prev_qname, int final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec,
-                                bool keyed, bool named = false, bool placed = false, bool edited = false) {
+                                bool keyed, bool named = false, bool placed = false, bool edited = false, bool based = false) {
   MG_REQUIRE_READY();
   if (!out || !ix || (nref && !refmap) || nref > 0x7fffffffu) return fail(MG_ERR_ARG, "null argument");
   std::vector<int32_t> m(nref + 1ull);
@@ -462,7 +465,7 @@ static int bam_tokenize_dev_impl(const uint8_t* d_bytes, uint64_t nbytes, const 
   MG_TRY(d_map.alloc(m.size() * sizeof(int32_t)));
   MG_TRY(mg_memcpy_h2d(d_map.p, m.data(), m.size() * sizeof(int32_t)));
   const int rc = bam_tokenize_prefix_dev(d_bytes, nbytes, d_map.as<int32_t>(), (int32_t)nref, prev_qname, final != 0, consumed, out,
-                                         err_kind, err_rec, keyed, named, placed, edited);
+                                         err_kind, err_rec, keyed, named, placed, edited, based);
   (void)hipStreamSynchronize(ctx().stream);  // (d_map is released here)
   return rc;
 }
@@ -485,13 +488,13 @@ int mg_bam_tokenize_named_dev(const uint8_t* d_bytes, uint64_t nbytes, const int
 int mg_bam_tokenize_dev_ex(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* refmap, uint32_t nref, const mg_acc_index* ix,
                            const char* prev_qname, int final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec,
                            unsigned want) {
-  if (want & ~(MG_BATCH_KEYS | MG_BATCH_NAMES | MG_BATCH_PLACES | MG_BATCH_COLLATE | MG_BATCH_EDITS)) return fail(MG_ERR_ARG, "unknown bits in want");
+  if (want & ~(MG_BATCH_KEYS | MG_BATCH_NAMES | MG_BATCH_PLACES | MG_BATCH_COLLATE | MG_BATCH_EDITS | MG_BATCH_BASES)) return fail(MG_ERR_ARG, "unknown bits in want");
   if ((want & MG_BATCH_NAMES) && (want & MG_BATCH_COLLATE))
     return fail(MG_ERR_STATE, "a named batch is not collated (its names are in the order the reads came in)");
   const bool collate = (want & MG_BATCH_COLLATE) != 0;
   MG_TRY(bam_tokenize_dev_impl(d_bytes, nbytes, refmap, nref, ix, prev_qname, final, consumed, out, err_kind, err_rec,
                                collate || (want & MG_BATCH_KEYS), (want & MG_BATCH_NAMES) != 0, (want & MG_BATCH_PLACES) != 0,
-                               (want & MG_BATCH_EDITS) != 0));
+                               (want & MG_BATCH_EDITS) != 0, (want & MG_BATCH_BASES) != 0));
   if (collate) {
     const int rc = collate_batch(*out, nullptr);
     if (rc != MG_OK) { delete *out; *out = nullptr; return rc; }

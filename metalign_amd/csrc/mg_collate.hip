@@ -93,6 +93,13 @@ __global__ __launch_bounds__(256) void k_collate_gather_edits(const mg_aln_edit*
   for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += stride) out[t] = edit[perm[t]];
 }
 
+// ... and its entries (MG_BATCH_BASES): 16 bytes each; the pool they point into stays where it is
+__global__ __launch_bounds__(256) void k_collate_gather_bases(const mg_aln_bases* __restrict__ ent, const uint64_t* __restrict__ perm,
+                                                              uint64_t n, mg_aln_bases* __restrict__ out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += stride) out[t] = ent[perm[t]];
+}
+
 // keys and flags -> d_perm[t] = the index of the record that comes t-th; *d_fkey (optional) = the sorted final keys (scratch:
 // valid until the next collation).  n > 0.
 static int collate_order(const uint64_t* d_keys2, const mg_aln_rec* d_recs, uint64_t n, uint64_t* d_perm, const uint64_t** d_fkey) {
@@ -152,6 +159,13 @@ int collate_batch(mg_sam_batch* b, uint64_t* d_perm_or_null) {
                          b->edits.as<mg_aln_edit>(), d_perm, n, out_edits.as<mg_aln_edit>());
       MG_HIP(hipGetLastError());
     }
+    DevBuf out_bases;
+    if (b->based) {
+      MG_TRY(out_bases.alloc((n + 1) * sizeof(mg_aln_bases)));
+      hipLaunchKernelGGL(k_collate_gather_bases, dim3(grid_for(n, 256, (unsigned)ctx().num_cus * 16)), dim3(256), 0, st,
+                         b->bases.as<mg_aln_bases>(), d_perm, n, out_bases.as<mg_aln_bases>());
+      MG_HIP(hipGetLastError());
+    }
     hipLaunchKernelGGL(k_collate_gather, dim3(grid_for(n, 256, (unsigned)ctx().num_cus * 16)), dim3(256), 0, st, b->recs.as<mg_aln_rec>(),
                        d_perm, d_fkey, n, out.as<mg_aln_rec>());
     MG_HIP(hipGetLastError());
@@ -159,6 +173,7 @@ int collate_batch(mg_sam_batch* b, uint64_t* d_perm_or_null) {
     b->recs = std::move(out);
     if (b->placed) b->places = std::move(out_places);
     if (b->edited) b->edits = std::move(out_edits);
+    if (b->based) b->bases = std::move(out_bases);
   }
   b->keys.release();
   b->keyed = false;

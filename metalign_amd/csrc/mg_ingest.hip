@@ -19,6 +19,7 @@
 #include "mg_collate_core.h"
 #include "mg_coverage_core.h"
 #include "mg_identity_core.h"
+#include "mg_variants_core.h"
 #include "mg_internal.h"
 
 namespace mg {
@@ -630,6 +631,86 @@ __global__ __launch_bounds__(256) void k_bam_edit(const uint8_t* __restrict__ by
   for (; r < nret; r += stride) edit[r] = mgi::edit_of_bam(bytes, lines[ret_line[r]].qbeg);
 }
 
+// BASED (--variants): record r is retained line ret_line[r]; its POS, CIGAR and SEQ -> entry[r] and the 4-bit codes of its pile
+// (mg_variants_core.h).  Two passes around a scan, as the named tokenisers size and then gather their names: k_*_bases_size leaves
+// every record's place and span in its entry and the bytes of its codes, k_*_bases_pack writes them at the scanned offset.  ONE LANE
+// PER RECORD, walking the core's scalar code: the CIGAR is a serial dependency (a base's reference position is the sum of the ops
+// in front of it), so the bytes are the core's by construction (DESIGN.md weighs it against a wavefront per record).  The parser
+// left the CIGAR's offset (fields[2 l]); SEQ is the fourth field behind it.
+__device__ __forceinline__ bool sam_cigar_seq(const uint8_t* text, uint64_t cig, uint64_t end, uint64_t* ce, uint64_t* sb, uint64_t* se) {
+  uint64_t b;
+  if (!mgv::field(text, cig, end, 0, &b, ce)) return false;
+  return mgv::field(text, *ce, end, 3, sb, se);  // (RNEXT, PNEXT, TLEN, then SEQ)
+}
+__global__ __launch_bounds__(256) void k_sam_bases_size(const uint8_t* __restrict__ text, const uint64_t* __restrict__ line_end,
+                                                        const uint64_t* __restrict__ fields, const uint64_t* __restrict__ ret_line,
+                                                        uint64_t nret, mg_aln_bases* __restrict__ entry, uint32_t* __restrict__ nbytes) {
+  uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (; r < nret; r += stride) {
+    const uint64_t l = ret_line[r], end = line_end[l], cig = fields[2 * l];
+    const mg_aln_place pl = mgv::place_of_line(text, l == 0 ? 0 : line_end[l - 1] + 1, end);
+    uint64_t ce, sb, se;
+    uint32_t span = 0;
+    if (pl.span && sam_cigar_seq(text, cig, end, &ce, &sb, &se)) span = mgvar::sam_pile_span(text, cig, ce, sb, se);
+    mg_aln_bases e;
+    e.off = 0;
+    e.pos0 = span ? pl.pos0 : 0u;
+    e.span = span;
+    entry[r] = e;
+    nbytes[r] = (span + 1) / 2;
+  }
+}
+__global__ __launch_bounds__(256) void k_sam_bases_pack(const uint8_t* __restrict__ text, const uint64_t* __restrict__ line_end,
+                                                        const uint64_t* __restrict__ fields, const uint64_t* __restrict__ ret_line,
+                                                        uint64_t nret, const uint64_t* __restrict__ boff, mg_aln_bases* __restrict__ entry,
+                                                        uint8_t* __restrict__ pool) {
+  uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (; r < nret; r += stride) {
+    if (entry[r].span == 0) continue;
+    const uint64_t l = ret_line[r], end = line_end[l], cig = fields[2 * l];
+    uint64_t ce, sb, se;
+    (void)sam_cigar_seq(text, cig, end, &ce, &sb, &se);
+    entry[r].off = boff[r];
+    mgvar::NibblePacker<uint8_t*> pk(pool, boff[r]);
+    mgvar::sam_pile_walk(text, cig, ce, sb, pk);
+    pk.flush();
+  }
+}
+// ... of a BAM record: packed ops and 4-bit SEQ behind the QNAME
+__global__ __launch_bounds__(256) void k_bam_bases_size(const uint8_t* __restrict__ bytes, const LineOut* __restrict__ lines,
+                                                        const uint64_t* __restrict__ ret_line, uint64_t nret,
+                                                        mg_aln_bases* __restrict__ entry, uint32_t* __restrict__ nbytes) {
+  uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (; r < nret; r += stride) {
+    const uint64_t qn = lines[ret_line[r]].qbeg;
+    const mg_aln_place pl = mgv::place_of_bam(bytes, qn);
+    const uint32_t span = pl.span ? mgvar::bam_pile_span(bytes, qn) : 0u;
+    mg_aln_bases e;
+    e.off = 0;
+    e.pos0 = span ? pl.pos0 : 0u;
+    e.span = span;
+    entry[r] = e;
+    nbytes[r] = (span + 1) / 2;
+  }
+}
+__global__ __launch_bounds__(256) void k_bam_bases_pack(const uint8_t* __restrict__ bytes, const LineOut* __restrict__ lines,
+                                                        const uint64_t* __restrict__ ret_line, uint64_t nret,
+                                                        const uint64_t* __restrict__ boff, mg_aln_bases* __restrict__ entry,
+                                                        uint8_t* __restrict__ pool) {
+  uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (; r < nret; r += stride) {
+    if (entry[r].span == 0) continue;
+    entry[r].off = boff[r];
+    mgvar::NibblePacker<uint8_t*> pk(pool, boff[r]);
+    mgvar::bam_pile_walk(bytes, lines[ret_line[r]].qbeg, pk);
+    pk.flush();
+  }
+}
+
 // Shared: build the line index of a text buffer.  If the text does not end in '\n' the last partial
 // line is terminated virtually.  -> d_line_end (scratch "ing_lines"), *nlines.
 // last_end (optional): the end of the last line, brought back in the same round trip as the marks' completion (a piece of a
@@ -930,9 +1011,11 @@ __global__ void k_sam_last_qname(const uint8_t* __restrict__ text, const LineOut
 // the byte after the last newline (what follows is carried to the next piece by the caller, mg_stream.hip).
 int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg_acc_index* ix, const char* prev_qname,
                                 bool paf, bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_line,
-                                bool thin, bool keyed, bool named, bool placed, bool edited) {
+                                bool thin, bool keyed, bool named, bool placed, bool edited, bool based) {
   MG_REQUIRE_READY();
   if (!out || !ix) return fail(MG_ERR_ARG, "null argument");
+  if (based && paf) return fail(MG_ERR_ARG, "a PAF line has no CIGAR and SEQ columns: no bases from PAF");
+  if (based && thin) return fail(MG_ERR_ARG, "no bases from thinned text (thinning drops SEQ)");
   if (placed && paf) return fail(MG_ERR_ARG, "a PAF line has no POS and CIGAR columns: no places from PAF");
   if (edited && paf) return fail(MG_ERR_ARG, "no edits from PAF (its NM:i: and cg:Z: tags are not read)");
   *out = nullptr;
@@ -955,6 +1038,7 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
     if (named) MG_TRY(names_empty(sb.get()));
     if (placed) MG_TRY(places_empty(sb.get()));
     if (edited) MG_TRY(edits_empty(sb.get()));
+    if (based) MG_TRY(bases_empty(sb.get()));
     *out = sb.release();
     return MG_OK;
   }
@@ -968,7 +1052,7 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
   uint8_t* d_prev = (uint8_t*)scratch("sam_prev", plen + 16);
   if (!d_lines || !d_ret || !d_rank || !d_kind || !d_err || !d_prev) return MG_ERR_NOMEM;
   uint64_t* d_fields = nullptr;
-  if (edited) {
+  if (edited || based) {
     d_fields = (uint64_t*)scratch("sam_fields", nlines * 2 * sizeof(uint64_t));
     if (!d_fields) return MG_ERR_NOMEM;
   }
@@ -982,7 +1066,7 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
     if (paf)
       hipLaunchKernelGGL(k_paf_parse, dim3(grid_for(nlines, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_text, d_le,
                          nlines, at, d_lines, d_ret, d_err, d_kind);
-    else if (edited)
+    else if (edited || based)
       hipLaunchKernelGGL(k_sam_parse<true>, dim3(grid_for(nlines, 256, (unsigned)c.num_cus * 16)), dim3(256), 0, st, d_text, d_le,
                          nlines, at, d_lines, d_ret, d_err, d_kind, thin ? 1u : 0u, d_fields);
     else
@@ -1002,7 +1086,7 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
       return fail(MG_ERR_ARG, "%s line %llu: parse error kind %u", paf ? "PAF" : "SAM", h_err, kind);
     }
     MG_TRY(aln_emit_retained(d_text, d_lines, d_ret, d_rank, nlines, nret, d_prev, (uint32_t)plen, sb.get(), keyed, named,
-                             placed ? kPlaceSam : kPlaceNone, d_le, edited ? kPlaceSam : kPlaceNone, d_fields));
+                             placed ? kPlaceSam : kPlaceNone, d_le, edited ? kPlaceSam : kPlaceNone, d_fields, based ? kPlaceSam : kPlaceNone));
   }
   sb->nrecs = nret;
   *out = sb.release();
@@ -1013,7 +1097,7 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
 // sb->last_qname.  The SAM / PAF tokeniser above and the BAM decoder (mg_bam.hip) end here.
 int mg::aln_emit_retained(const uint8_t* d_text, const LineOut* d_lines, const uint32_t* d_ret, const uint64_t* d_rank, uint64_t nlines,
                           uint64_t nret, const uint8_t* d_prev, uint32_t plen, mg_sam_batch* sb, bool keyed, bool named, int placed,
-                          const uint64_t* d_line_end, int edited, const uint64_t* d_fields) {
+                          const uint64_t* d_line_end, int edited, const uint64_t* d_fields, int based) {
   Context& c = ctx();
   hipStream_t st = c.stream;
   MG_TRY(sb->recs.alloc((nret + 1) * sizeof(mg_aln_rec)));
@@ -1028,6 +1112,13 @@ int mg::aln_emit_retained(const uint8_t* d_text, const LineOut* d_lines, const u
     if (edited == kPlaceSam && (!d_line_end || !d_fields)) return fail(MG_ERR_ARG, "edits from text need its line index and field offsets");
     MG_TRY(sb->edits.alloc((nret + 1) * sizeof(mg_aln_edit)));
     sb->edited = true;
+  }
+  if (based) {
+    if (based == kPlaceSam && (!d_line_end || !d_fields)) return fail(MG_ERR_ARG, "bases from text need its line index and field offsets");
+    MG_TRY(sb->bases.alloc((nret + 1) * sizeof(mg_aln_bases)));
+    if (!nret) MG_TRY(sb->pool.alloc(16));
+    sb->npool = 0;
+    sb->based = true;
   }
   if (nret) {
     uint64_t* d_list = (uint64_t*)scratch("sam_list", nret * sizeof(uint64_t));
@@ -1057,6 +1148,29 @@ int mg::aln_emit_retained(const uint8_t* d_text, const LineOut* d_lines, const u
         hipLaunchKernelGGL(k_sam_edit, dim3(grid), dim3(256), 0, st, d_text, d_line_end, d_fields, d_list, nret, sb->edits.as<mg_aln_edit>());
       else
         hipLaunchKernelGGL(k_bam_edit, dim3(grid), dim3(256), 0, st, d_text, d_lines, d_list, nret, sb->edits.as<mg_aln_edit>());
+      MG_HIP(hipGetLastError());
+    }
+    if (based) {  // (its pack launch is covered by the round trip below)
+      ProfScope ps("ingest_bases");
+      const unsigned grid = grid_for(nret, 256, (unsigned)c.num_cus * 16);
+      uint32_t* d_nb = (uint32_t*)scratch("bs_len", nret * sizeof(uint32_t));
+      uint64_t* d_boff = (uint64_t*)scratch("bs_off", (nret + 1) * sizeof(uint64_t));
+      if (!d_nb || !d_boff) return MG_ERR_NOMEM;
+      mg_aln_bases* ent = sb->bases.as<mg_aln_bases>();
+      if (based == kPlaceSam)
+        hipLaunchKernelGGL(k_sam_bases_size, dim3(grid), dim3(256), 0, st, d_text, d_line_end, d_fields, d_list, nret, ent, d_nb);
+      else
+        hipLaunchKernelGGL(k_bam_bases_size, dim3(grid), dim3(256), 0, st, d_text, d_lines, d_list, nret, ent, d_nb);
+      MG_HIP(hipGetLastError());
+      uint64_t npool = 0;
+      MG_TRY(exclusive_sum_u32_to_u64(d_nb, d_boff, nret, &npool));
+      MG_TRY(sb->pool.alloc(npool + 16));
+      sb->npool = npool;
+      if (based == kPlaceSam)
+        hipLaunchKernelGGL(k_sam_bases_pack, dim3(grid), dim3(256), 0, st, d_text, d_line_end, d_fields, d_list, nret, d_boff, ent,
+                           sb->pool.as<uint8_t>());
+      else
+        hipLaunchKernelGGL(k_bam_bases_pack, dim3(grid), dim3(256), 0, st, d_text, d_lines, d_list, nret, d_boff, ent, sb->pool.as<uint8_t>());
       MG_HIP(hipGetLastError());
     }
     // QNAME of the last retained line, for the next chunk: its span and its first kQnameInline bytes in ONE round trip
@@ -1126,6 +1240,14 @@ int mg::edits_empty(mg_sam_batch* sb) {
   return MG_OK;
 }
 
+int mg::bases_empty(mg_sam_batch* sb) {
+  MG_TRY(sb->bases.alloc(16));
+  MG_TRY(sb->pool.alloc(16));
+  sb->npool = 0;
+  sb->based = true;
+  return MG_OK;
+}
+
 int mg::names_empty(mg_sam_batch* sb) {
   MG_TRY(sb->name_off.alloc(2 * sizeof(uint64_t)));
   MG_TRY(sb->name_bytes.alloc(16));
@@ -1155,7 +1277,8 @@ int mg_sam_tokenize_named(const uint8_t* text, uint64_t nbytes, int paf, const m
 // The flag-taking family: what the plain, keyed, named and collated calls give, and the places, by one mask.
 int mg_sam_tokenize_dev_ex(const uint8_t* d_text, uint64_t nbytes, int paf, const mg_acc_index* ix, const char* prev_qname,
                            mg_sam_batch** out, int* err_kind, uint64_t* err_line, unsigned want) {
-  if (want & ~(MG_BATCH_KEYS | MG_BATCH_NAMES | MG_BATCH_PLACES | MG_BATCH_COLLATE | MG_BATCH_EDITS)) return fail(MG_ERR_ARG, "unknown bits in want");
+  if (want & ~(MG_BATCH_KEYS | MG_BATCH_NAMES | MG_BATCH_PLACES | MG_BATCH_COLLATE | MG_BATCH_EDITS | MG_BATCH_BASES)) return fail(MG_ERR_ARG, "unknown bits in want");
+  if ((want & MG_BATCH_BASES) && paf) return fail(MG_ERR_ARG, "a PAF line has no CIGAR and SEQ columns: no bases from PAF");
   if ((want & MG_BATCH_PLACES) && paf) return fail(MG_ERR_ARG, "a PAF line has no POS and CIGAR columns: no places from PAF");
   if ((want & MG_BATCH_EDITS) && paf) return fail(MG_ERR_ARG, "no edits from PAF (its NM:i: and cg:Z: tags are not read)");
   if ((want & MG_BATCH_NAMES) && (want & MG_BATCH_COLLATE))
@@ -1163,7 +1286,7 @@ int mg_sam_tokenize_dev_ex(const uint8_t* d_text, uint64_t nbytes, int paf, cons
   const bool collate = (want & MG_BATCH_COLLATE) != 0;
   MG_TRY(mg::aln_tokenize_prefix_dev(d_text, nbytes, ix, prev_qname, paf != 0, true, nullptr, out, err_kind, err_line, false,
                                      collate || (want & MG_BATCH_KEYS), (want & MG_BATCH_NAMES) != 0, (want & MG_BATCH_PLACES) != 0,
-                                     (want & MG_BATCH_EDITS) != 0));
+                                     (want & MG_BATCH_EDITS) != 0, (want & MG_BATCH_BASES) != 0));
   if (collate) {
     const int rc = mg::collate_batch(*out, nullptr);
     if (rc != MG_OK) { delete *out; *out = nullptr; return rc; }
@@ -1209,6 +1332,25 @@ int mg_sam_batch_edits_device_ptr(const mg_sam_batch* b, const mg_aln_edit** d_e
   if (!b || !d_edits) return fail(MG_ERR_ARG, "null argument");
   if (!b->edited) return fail(MG_ERR_STATE, "the batch carries no edits (tokenise it with MG_BATCH_EDITS)");
   *d_edits = b->edits.as<mg_aln_edit>();
+  return MG_OK;
+}
+
+int mg_sam_batch_bases_download(const mg_sam_batch* b, mg_aln_bases* entries, uint8_t* pool) {
+  MG_REQUIRE_READY();
+  if (!b) return fail(MG_ERR_ARG, "null batch");
+  if (!b->based) return fail(MG_ERR_STATE, "the batch carries no bases (tokenise it with MG_BATCH_BASES)");
+  if ((b->nrecs && !entries) || (b->npool && !pool)) return fail(MG_ERR_ARG, "null argument");
+  if (b->nrecs) MG_TRY(mg_memcpy_d2h(entries, b->bases.p, b->nrecs * sizeof(mg_aln_bases)));
+  if (b->npool) MG_TRY(mg_memcpy_d2h(pool, b->pool.p, b->npool));
+  return MG_OK;
+}
+
+int mg_sam_batch_bases_device_ptr(const mg_sam_batch* b, const mg_aln_bases** d_entries, const uint8_t** d_pool, uint64_t* pool_bytes) {
+  if (!b || !d_entries || !d_pool || !pool_bytes) return fail(MG_ERR_ARG, "null argument");
+  if (!b->based) return fail(MG_ERR_STATE, "the batch carries no bases (tokenise it with MG_BATCH_BASES)");
+  *d_entries = b->bases.as<mg_aln_bases>();
+  *d_pool = b->pool.as<uint8_t>();
+  *pool_bytes = b->npool;
   return MG_OK;
 }
 

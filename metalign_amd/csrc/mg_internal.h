@@ -350,6 +350,11 @@ struct mg_sam_batch {
   // the tokenisers asked for MG_BATCH_EDITS (--identity): mg_aln_edit[nrecs] in record order, permuted like the places
   mg::DevBuf edits;
   bool edited = false;
+  // ... MG_BATCH_BASES (--variants): mg_aln_bases[nrecs] in record order, permuted like the places, and the pool of 4-bit codes the
+  // entries point into (npool bytes), which a collation leaves where it is
+  mg::DevBuf bases, pool;
+  uint64_t npool = 0;
+  bool based = false;
 };
 
 namespace mg {
@@ -369,13 +374,17 @@ enum { kPlaceNone = 0, kPlaceSam = 1, kPlaceBam = 2 };
 int aln_emit_retained(const uint8_t* d_text, const LineOut* d_lines, const uint32_t* d_ret, const uint64_t* d_rank, uint64_t nlines,
                       uint64_t nret, const uint8_t* d_prev, uint32_t plen, mg_sam_batch* sb, bool keyed = false, bool named = false,
                       int placed = kPlaceNone, const uint64_t* d_line_end = nullptr, int edited = kPlaceNone,
-                      const uint64_t* d_fields = nullptr);
+                      const uint64_t* d_fields = nullptr, int based = kPlaceNone);
+// based (the same three values): the batch also gets every record's entry and the pool of its codes (mg_variants_core.h) — from the
+// SAM line (d_line_end and d_fields, as the edits) or from the BAM record body
 // a named batch without records: no names
 int names_empty(mg_sam_batch* sb);
 // a placed batch without records
 int places_empty(mg_sam_batch* sb);
 // ... with edits
 int edits_empty(mg_sam_batch* sb);
+// ... with bases
+int bases_empty(mg_sam_batch* sb);
 // BAM (mg_bam.hip): the header as zlib reads it from the file; a piece of the records behind it -> the batch, as
 // aln_tokenize_prefix_dev for text (d_refmap: int32[1 + n_ref], bam_refmap's); *consumed = the end of its last complete record.
 struct BamHeader {
@@ -387,7 +396,7 @@ int bam_read_header(const char* path, BamHeader* h);
 std::vector<int32_t> bam_refmap(const std::vector<std::string>& names, const mg_acc_index* ix);
 int bam_tokenize_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, const int32_t* d_refmap, int32_t n_ref, const char* prev_qname,
                             bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_rec, bool keyed = false,
-                            bool named = false, bool placed = false, bool edited = false);
+                            bool named = false, bool placed = false, bool edited = false, bool based = false);
 // The reads of a piece of BAM records (`samtools fastq -F 0x900`, mg_bam_core.h) -> *out, as mg_reads_parse_prefix_dev for text;
 // a break in the chain: MG_ERR_ARG, *err_at = its byte in the piece.
 int bam_reads_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, int32_t n_ref, bool final, uint64_t* consumed, mg_reads** out,
@@ -395,7 +404,7 @@ int bam_reads_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, int32_t n_ref,
 // thin: the piece comes from the file reader's thinning (mg_stream.hip: a SEQ field is MG_THIN_MARK + its length in decimal).
 int aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg_acc_index* ix, const char* prev_qname, bool paf,
                             bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_line, bool thin = false,
-                            bool keyed = false, bool named = false, bool placed = false, bool edited = false);
+                            bool keyed = false, bool named = false, bool placed = false, bool edited = false, bool based = false);
 // mg_collate.hip: a keyed batch -> its records regrouped by read (metalign_amd/collate.py is the definition), the keys freed.
 int collate_batch(mg_sam_batch* b, uint64_t* d_perm_or_null);
 }

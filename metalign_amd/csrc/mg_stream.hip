@@ -952,6 +952,16 @@ __global__ __launch_bounds__(256) void k_shift_offsets(const uint64_t* __restric
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = in[i] + add;
 }
 
+// a piece's entries behind the pieces before it: out[i] = in[i] with off moved up by `add` where the entry is piled
+__global__ __launch_bounds__(256) void k_shift_bases(const mg_aln_bases* __restrict__ in, uint64_t n, uint64_t add, mg_aln_bases* __restrict__ out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    mg_aln_bases e = in[i];
+    if (e.span) e.off += add;
+    out[i] = e;
+  }
+}
+
 }  // namespace mg
 
 using namespace mg;
@@ -1023,7 +1033,7 @@ int mg_reads_from_bam_file(const char* path, uint64_t chunk_bytes, int nthreads,
 // named pieces: their names appended, their offsets moved up by the bytes in front of them (a read that goes on into the next
 // piece opens no read there, so it is named once)
 static int concat_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uint64_t total, const std::string& prev, bool keyed,
-                          mg_sam_batch** out, bool named = false, bool placed = false, bool edited = false) {
+                          mg_sam_batch** out, bool named = false, bool placed = false, bool edited = false, bool based = false) {
   std::unique_ptr<mg_sam_batch> all(new mg_sam_batch());
   all->last_qname = prev;
   all->nrecs = total;
@@ -1031,6 +1041,7 @@ static int concat_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uin
   if (named && parts.empty()) MG_TRY(names_empty(all.get()));
   if (placed && parts.empty()) MG_TRY(places_empty(all.get()));
   if (edited && parts.empty()) MG_TRY(edits_empty(all.get()));
+  if (based && parts.empty()) MG_TRY(bases_empty(all.get()));
   if (parts.size() == 1) {
     all->recs = std::move(parts[0]->recs);
     all->keys = std::move(parts[0]->keys);
@@ -1043,6 +1054,10 @@ static int concat_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uin
     all->placed = parts[0]->placed;
     all->edits = std::move(parts[0]->edits);
     all->edited = parts[0]->edited;
+    all->bases = std::move(parts[0]->bases);
+    all->pool = std::move(parts[0]->pool);
+    all->npool = parts[0]->npool;
+    all->based = parts[0]->based;
   } else {
     MG_TRY(all->recs.alloc((total + 1) * sizeof(mg_aln_rec)));
     if (keyed) MG_TRY(all->keys.alloc((total + 1) * 2 * sizeof(uint64_t)));
@@ -1054,9 +1069,25 @@ static int concat_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uin
       MG_TRY(all->edits.alloc((total + 1) * sizeof(mg_aln_edit)));
       all->edited = true;
     }
-    uint64_t at = 0;
+    uint64_t at = 0, pool_at = 0;
     hipStream_t st = ctx().stream;
+    if (based && !parts.empty()) {  // ... and their entries, each piece's pool behind the pools before it
+      uint64_t npool = 0;
+      for (auto& p : parts) npool += p->npool;
+      MG_TRY(all->bases.alloc((total + 1) * sizeof(mg_aln_bases)));
+      MG_TRY(all->pool.alloc(npool + 16));
+      all->npool = npool;
+      all->based = true;
+    }
     for (auto& p : parts) {
+      if (based && p->nrecs) {
+        hipLaunchKernelGGL(k_shift_bases, dim3(grid_for(p->nrecs, 256, 1024)), dim3(256), 0, st, p->bases.as<mg_aln_bases>(), p->nrecs, pool_at,
+                           all->bases.as<mg_aln_bases>() + at);
+        MG_HIP(hipGetLastError());
+      }
+      if (based && p->npool)
+        MG_HIP(hipMemcpyAsync(all->pool.as<uint8_t>() + pool_at, p->pool.p, p->npool, hipMemcpyDeviceToDevice, st));
+      if (based) pool_at += p->npool;
       if (p->nrecs)
         MG_HIP(hipMemcpyAsync(all->recs.as<mg_aln_rec>() + at, p->recs.p, p->nrecs * sizeof(mg_aln_rec), hipMemcpyDeviceToDevice, st));
       if (p->nrecs && keyed)
@@ -1097,9 +1128,9 @@ static int concat_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uin
 // ... and, for the collated entry points, regrouped by read (mg_collate.hip).  The knob collate_defer (a test hook) leaves the
 // batch as it was tokenised, keys and all, for the caller to look at and collate (mg_sam_batch_collate_dev).
 static int finish_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uint64_t total, const std::string& prev, bool collate,
-                          mg_sam_batch** out, bool named = false, bool placed = false, bool edited = false) {
+                          mg_sam_batch** out, bool named = false, bool placed = false, bool edited = false, bool based = false) {
   mg_sam_batch* all = nullptr;
-  MG_TRY(concat_batches(parts, total, prev, collate, &all, named, placed, edited));
+  MG_TRY(concat_batches(parts, total, prev, collate, &all, named, placed, edited, based));
   if (collate && !dbg("collate_defer")) {
     parts.clear();  // (the pieces' buffers go back to the pool before the sort asks for its own)
     const int rc = collate_batch(all, nullptr);
@@ -1116,7 +1147,7 @@ static int finish_batches(std::vector<std::unique_ptr<mg_sam_batch>>& parts, uin
 // the file through the host tokeniser, which raises what the reference raises).
 static int sam_stream_file_impl(const char* path, int paf, const mg_acc_index* ix, uint64_t offset, uint64_t length,
                                 uint64_t chunk_bytes, int nthreads, mg_sam_batch** out, int* err_kind, uint64_t* err_line, bool collate,
-                                bool named = false, bool placed = false, bool edited = false) {
+                                bool named = false, bool placed = false, bool edited = false, bool based = false) {
   MG_REQUIRE_READY();
   if (!path || !ix || !out) return fail(MG_ERR_ARG, "null argument");
   *out = nullptr;
@@ -1124,25 +1155,27 @@ static int sam_stream_file_impl(const char* path, int paf, const mg_acc_index* i
   if (err_line) *err_line = 0;
   // (a BGZF file's host readers stay at the eight of a plain file)
   const StreamPlan plan{.offset = offset, .length = length, .chunk_bytes = chunk_bytes, .nthreads = nthreads,
-                        .thin_kind = paf ? -1 : (int)ThinSource::kSam, .bgzf_uses_all_cores = false};
+                        .thin_kind = (paf || based) ? -1 : (int)ThinSource::kSam,  // (thinning drops SEQ)
+                        .bgzf_uses_all_cores = false};
   bool thinned = false;
   std::vector<std::unique_ptr<mg_sam_batch>> parts;
   std::string prev;
   uint64_t total = 0;
   MG_TRY(stream_file(path, plan, [&](const uint8_t* d_text, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
     mg_sam_batch* b = nullptr;
-    MG_TRY(aln_tokenize_prefix_dev(d_text, nbytes, ix, prev.c_str(), paf != 0, final, consumed, &b, err_kind, err_line, thinned, collate, named, placed, edited));
+    MG_TRY(aln_tokenize_prefix_dev(d_text, nbytes, ix, prev.c_str(), paf != 0, final, consumed, &b, err_kind, err_line, thinned, collate, named, placed, edited, based));
     prev = b->last_qname;
     total += b->nrecs;
     parts.emplace_back(b);
     return MG_OK;
   }, &thinned));
-  return finish_batches(parts, total, prev, collate, out, named, placed, edited);
+  return finish_batches(parts, total, prev, collate, out, named, placed, edited, based);
 }
 
 // The flag-taking streams (MG_BATCH_*): KEYS alone keeps the keys on the batch (as the knob collate_defer does for a collated call).
 static int stream_want_check(unsigned want, int paf) {
-  if (want & ~(MG_BATCH_KEYS | MG_BATCH_NAMES | MG_BATCH_PLACES | MG_BATCH_COLLATE | MG_BATCH_EDITS)) return fail(MG_ERR_ARG, "unknown bits in want");
+  if (want & ~(MG_BATCH_KEYS | MG_BATCH_NAMES | MG_BATCH_PLACES | MG_BATCH_COLLATE | MG_BATCH_EDITS | MG_BATCH_BASES)) return fail(MG_ERR_ARG, "unknown bits in want");
+  if ((want & MG_BATCH_BASES) && paf) return fail(MG_ERR_ARG, "a PAF line has no CIGAR and SEQ columns: no bases from PAF");
   if ((want & MG_BATCH_PLACES) && paf) return fail(MG_ERR_ARG, "a PAF line has no POS and CIGAR columns: no places from PAF");
   if ((want & MG_BATCH_EDITS) && paf) return fail(MG_ERR_ARG, "no edits from PAF (its NM:i: and cg:Z: tags are not read)");
   if ((want & MG_BATCH_NAMES) && (want & MG_BATCH_COLLATE))
@@ -1157,7 +1190,7 @@ int mg_sam_stream_file_ex(const char* path, int paf, const mg_acc_index* ix, uin
   MG_TRY(stream_want_check(want, paf));
   return sam_stream_file_impl(path, paf, ix, offset, length, chunk_bytes, nthreads, out, err_kind, err_line,
                               (want & MG_BATCH_COLLATE) != 0, (want & MG_BATCH_NAMES) != 0, (want & MG_BATCH_PLACES) != 0,
-                              (want & MG_BATCH_EDITS) != 0);
+                              (want & MG_BATCH_EDITS) != 0, (want & MG_BATCH_BASES) != 0);
 }
 
 int mg_sam_stream_file_named(const char* path, int paf, const mg_acc_index* ix, uint64_t offset, uint64_t length,
@@ -1180,7 +1213,7 @@ int mg_sam_stream_file_collated(const char* path, int paf, const mg_acc_index* i
 // (mg_bam.hip).
 static int bam_stream_file_impl(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,
                                 int* err_kind, uint64_t* err_rec, bool collate, bool named = false, bool placed = false,
-                                bool edited = false) {
+                                bool edited = false, bool based = false) {
   MG_REQUIRE_READY();
   if (!path || !ix || !out) return fail(MG_ERR_ARG, "null argument");
   *out = nullptr;
@@ -1200,20 +1233,21 @@ static int bam_stream_file_impl(const char* path, const mg_acc_index* ix, uint64
   MG_TRY(stream_file(path, plan, skip_bam_header(hdr.bytes, path, [&](const uint8_t* d_recs, uint64_t nbytes, bool final, uint64_t* consumed) -> int {
     mg_sam_batch* b = nullptr;
     MG_TRY(bam_tokenize_prefix_dev(d_recs, nbytes, d_map.as<int32_t>(), (int32_t)hdr.names.size(), prev.c_str(), final, consumed, &b,
-                                   err_kind, err_rec, collate, named, placed, edited));
+                                   err_kind, err_rec, collate, named, placed, edited, based));
     prev = b->last_qname;
     total += b->nrecs;
     parts.emplace_back(b);
     return MG_OK;
   })));
-  return finish_batches(parts, total, prev, collate, out, named, placed, edited);
+  return finish_batches(parts, total, prev, collate, out, named, placed, edited, based);
 }
 
 int mg_bam_stream_file_ex(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,
                           int* err_kind, uint64_t* err_rec, unsigned want) {
   MG_TRY(stream_want_check(want, 0));
   return bam_stream_file_impl(path, ix, chunk_bytes, nthreads, out, err_kind, err_rec, (want & MG_BATCH_COLLATE) != 0,
-                              (want & MG_BATCH_NAMES) != 0, (want & MG_BATCH_PLACES) != 0, (want & MG_BATCH_EDITS) != 0);
+                              (want & MG_BATCH_NAMES) != 0, (want & MG_BATCH_PLACES) != 0, (want & MG_BATCH_EDITS) != 0,
+                              (want & MG_BATCH_BASES) != 0);
 }
 
 int mg_bam_stream_file_named(const char* path, const mg_acc_index* ix, uint64_t chunk_bytes, int nthreads, mg_sam_batch** out,

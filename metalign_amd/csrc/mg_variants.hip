@@ -1,0 +1,402 @@
+// mg_variants.hip — per-site allele counts and strain diversity per accession (--variants, --variant_sites;
+// metalign_amd/variants.py is the definition, mg_variants_core.h the per-site rule).
+//
+// Four u32 per reference base (the reads' A, C, G and T there), every accession at a 64-bit site offset.  Three kernels, one of
+// them in two forms:
+//
+//   k_var_add           records + entries + pool -> one add per code below 4 of every counting, piled record, clipped at the
+//                       accession's length; the accession's alignments and the unpiled counted as k_cov_add does (hashed LDS bins,
+//                       flushed with one global add per bin and workgroup).  Persistent grid-stride.  The work per record is its span
+//                       — 150 for a short read, 2^21 - 1 at most — so, as k_cov_add, every wavefront flattens the base lists of its 64
+//                       records (an inclusive scan of the clipped spans) and its lanes stride the total: neighbouring lanes take
+//                       neighbouring bases of one record, that is neighbouring 16-byte cells and the same or neighbouring pool bytes,
+//                       and no lane walks a long record alone.  The adds return nothing.
+//   k_var_sites<false>  the sums: every wavefront takes blocks of kStep sites, finds the accession of its first site in the offsets
+//                       (as k_cov_count) and judges the sites of accessions that have an alignment: callable, polymorphic, pairs and
+//                       discordant summed over the wavefront, one 64-bit add per block, accession and sum; the block's polymorphic
+//                       sites counted.
+//   k_var_scan          the exclusive scan of the blocks' counts by ONE workgroup (as k_mask_scan): nobody waits for another
+//                       workgroup.
+//   k_var_sites<true>   the sites: the same walk a second time; a polymorphic site goes to the block's base + the polymorphic sites
+//                       before it in the block (a ballot and mbcnt per 64 sites), so the sites come out ordered by (accession row,
+//                       pos0) whatever the grid.
+#include "mg_internal.h"
+#include "mg_variants_core.h"
+
+using namespace mg;
+
+struct mg_variants {
+  uint32_t* cnt = nullptr;  // u32[4 * nsites] (its own allocation, as the coverage bitmap)
+  uint64_t nsites = 0, nblocks = 0, npoly = 0;
+  uint32_t nacc = 0;
+  bool finished = false;
+  DevBuf off;    // u64[nacc + 1]: accession a's first site
+  DevBuf len;    // u64[nacc]
+  DevBuf sums;   // u64[5 nacc + 1]: alignments, callable, polymorphic, pairs, discordant, unpiled
+  DevBuf blk;    // u64[1 + nblocks]: the scan's carry, then the blocks' polymorphic sites / bases
+  DevBuf sites;  // mg_variant_site[npoly]
+  ~mg_variants() { if (cnt) (void)hipFree(cnt); }
+};
+
+namespace {
+
+constexpr unsigned kBlock = 256, kBins = 1024, kProbe = 8, kScanBlock = 256;
+constexpr uint32_t kEmpty = 0xffffffffu;
+constexpr uint64_t kStep = 1024;  // sites per wavefront and step of k_var_sites
+constexpr uint64_t kLaunchMax = 1ull << 31;
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+
+struct PoolView {
+  const uint8_t* p;
+  __device__ __forceinline__ uint32_t operator[](uint64_t i) const { return p[i]; }
+};
+
+__global__ __launch_bounds__(kBlock) void k_var_add(const mg_aln_rec* __restrict__ recs, const mg_aln_bases* __restrict__ bases,
+                                                    const uint8_t* __restrict__ pool, uint64_t n, double pct_id,
+                                                    const uint64_t* __restrict__ len, const uint64_t* __restrict__ off, uint32_t nacc,
+                                                    uint32_t* __restrict__ cnt, unsigned long long* __restrict__ aln,
+                                                    unsigned long long* __restrict__ unpiled) {
+  __shared__ uint32_t s_key[kBins];
+  __shared__ unsigned long long s_cnt[kBins];
+  __shared__ unsigned long long s_unpiled;
+  for (unsigned i = threadIdx.x; i < kBins; i += kBlock) { s_key[i] = kEmpty; s_cnt[i] = 0; }
+  if (threadIdx.x == 0) s_unpiled = 0;
+  __syncthreads();
+  const unsigned lane = threadIdx.x & 63u;
+  const PoolView pv{pool};
+  // (no workgroup barrier inside the loop: a wavefront works on its own 64 records)
+  for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < n; base += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t i = base + threadIdx.x;
+    uint32_t a = 0, clen = 0;
+    unsigned long long site0 = 0, poff = 0;
+    bool unp = false;
+    if (i < n) {
+      const mg_aln_rec r = recs[i];
+      if (mgv::counts(r, pct_id)) {
+        const mg_aln_bases e = bases[i];
+        a = r.ref_new & MG_REC_REF_MASK;
+        // (span <= kMaxPileSpan by the entry's definition: an entry that says more is cut there, so that 64 of them sum in 32 bits)
+        const uint32_t span = e.span < mgvar::kMaxPileSpan ? e.span : mgvar::kMaxPileSpan;
+        clen = a < nacc ? (uint32_t)mgv::clipped(e.pos0, span, len[a]) : 0u;
+        if (clen) {
+          site0 = off[a] + e.pos0;
+          poff = e.off;
+        } else {
+          unp = true;
+        }
+      }
+    }
+    // the unpiled: one LDS add per wavefront
+    const unsigned long long um = __ballot(unp);
+    if (um && lane == (unsigned)__builtin_ctzll(um)) atomicAdd(&s_unpiled, (unsigned long long)__builtin_popcountll(um));
+    const unsigned long long pm = __ballot(clen != 0);
+    if (!pm) continue;  // (uniform over the wavefront)
+    // alignments
+    {
+      const unsigned first = (unsigned)__builtin_ctzll(pm);
+      const uint32_t a_first = __shfl(a, (int)first, 64);
+      const bool uniform = __ballot(clen != 0 && a != a_first) == 0;
+      const unsigned long long add_cnt = uniform ? (unsigned long long)__builtin_popcountll(pm) : 1ull;
+      if (uniform ? lane == first : clen != 0) {
+        const uint32_t h = (a * 2654435761u) >> 22;
+        bool done = false;
+        for (unsigned p = 0; p < kProbe && !done; ++p) {
+          const uint32_t s = (h + p) & (kBins - 1);
+          const uint32_t k = atomicCAS(&s_key[s], kEmpty, a);
+          if (k == kEmpty || k == a) {
+            atomicAdd(&s_cnt[s], add_cnt);
+            done = true;
+          }
+        }
+        if (!done) atomicAdd(&aln[a], add_cnt);
+      }
+    }
+    // the bases: the wavefront's flattened list, its lanes striding it (64 * kMaxPileSpan < 2^32)
+    uint32_t incl = clen;
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t up = __shfl_up(incl, d, 64);
+      if (lane >= (unsigned)d) incl += up;
+    }
+    const uint32_t total = __shfl(incl, 63, 64);
+    for (uint32_t j0 = 0; j0 < total; j0 += 64) {  // (uniform: every lane takes part in the shuffles)
+      const uint32_t j = j0 + lane;
+      int lo = 0, hi = 63;  // the first record whose inclusive sum is above j
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const uint32_t v = __shfl(incl, mid, 64);  // (each lane asks for its own mid)
+        if (v > j) hi = mid; else lo = mid + 1;
+      }
+      const uint32_t r_incl = __shfl(incl, lo, 64), r_len = __shfl(clen, lo, 64);
+      const unsigned long long r_site = __shfl(site0, lo, 64), r_poff = __shfl(poff, lo, 64);
+      if (j < total) {
+        const uint32_t k = j - (r_incl - r_len);  // (< r_len: inside the entry's codes and the accession's sites)
+        const uint32_t code = mgvar::code_at(pv, r_poff, k);
+        if (code < 4) (void)__hip_atomic_fetch_add(cnt + ((r_site + k) * 4 + code), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+  __syncthreads();
+  for (unsigned s = threadIdx.x; s < kBins; s += kBlock) {
+    const uint32_t k = s_key[s];
+    if (k != kEmpty && s_cnt[s]) atomicAdd(&aln[k], s_cnt[s]);
+  }
+  if (threadIdx.x == 0 && s_unpiled) atomicAdd(unpiled, s_unpiled);
+}
+
+// The accession of site t: the last a with off[a] <= t < off[a + 1] (off[nacc] = nsites > t).
+__device__ __forceinline__ uint32_t acc_of_site(const uint64_t* __restrict__ off, uint32_t nacc, uint64_t t) {
+  uint32_t lo = 0, hi = nacc;  // the first index in [0, nacc] whose offset is above t
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (off[mid] > t) hi = mid; else lo = mid + 1;
+  }
+  return lo - 1;
+}
+
+// Both passes over the sites: kEmit = false sums and counts, kEmit = true writes the polymorphic sites.
+template <bool kEmit>
+__global__ __launch_bounds__(kBlock) void k_var_sites(const uint32_t* __restrict__ cnt, uint64_t nsites, uint64_t nblocks,
+                                                      const uint64_t* __restrict__ off, uint32_t nacc,
+                                                      const unsigned long long* __restrict__ aln, uint32_t min_depth, uint32_t min_count,
+                                                      uint32_t permille, unsigned long long* __restrict__ callable_,
+                                                      unsigned long long* __restrict__ poly, unsigned long long* __restrict__ pairs,
+                                                      unsigned long long* __restrict__ disc, unsigned long long* __restrict__ blk,
+                                                      mg_variant_site* __restrict__ out, uint64_t nout) {
+  const unsigned lane = threadIdx.x & 63u;
+  const uint64_t wave = (uint64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  const uint64_t nwaves = (uint64_t)gridDim.x * (kBlock / 64);
+  const uint4* cnt4 = reinterpret_cast<const uint4*>(cnt);
+  for (uint64_t b = wave; b < nblocks; b += nwaves) {
+    const uint64_t t0 = b * kStep, t1 = t0 + kStep < nsites ? t0 + kStep : nsites;
+    uint32_t a = acc_of_site(off, nacc, t0);
+    uint64_t s = t0;
+    unsigned long long at = kEmit ? blk[b] : 0ull;  // kEmit: where the block's next polymorphic site goes; else: their count
+    while (s < t1) {
+      const uint64_t e = off[a + 1] < t1 ? off[a + 1] : t1;
+      if (aln[a]) {  // (an accession without an alignment has no count)
+        unsigned long long c_call = 0, c_poly = 0, c_pairs = 0, c_disc = 0;
+        for (uint64_t w0 = s; w0 < e; w0 += 64) {  // (uniform: every lane takes part in the ballot)
+          const uint64_t w = w0 + lane;
+          bool is_poly = false;
+          uint32_t n4[4] = {0, 0, 0, 0};
+          if (w < e) {
+            const uint4 v = cnt4[w];
+            n4[0] = v.x; n4[1] = v.y; n4[2] = v.z; n4[3] = v.w;
+            const mgvar::Site st = mgvar::site_of(n4, min_depth, min_count, permille);
+            is_poly = st.polymorphic;
+            if (!kEmit) {
+              c_call += st.callable_ ? 1u : 0u;
+              c_poly += is_poly ? 1u : 0u;
+              c_pairs += st.pairs;
+              c_disc += st.discordant;
+            }
+          }
+          if (kEmit) {
+            const unsigned long long pm = __ballot(is_poly);
+            const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0u));
+            const unsigned long long o = at + below;
+            if (is_poly && o < nout) {
+              mg_variant_site vs;
+              vs.acc = a;
+              vs.pos0 = (uint32_t)(w - off[a]);
+              vs.n[0] = n4[0]; vs.n[1] = n4[1]; vs.n[2] = n4[2]; vs.n[3] = n4[3];
+              out[o] = vs;
+            }
+            at += (unsigned long long)__builtin_popcountll(pm);
+          }
+        }
+        if (!kEmit) {
+          c_call = wave_sum(c_call);
+          c_poly = wave_sum(c_poly);
+          c_pairs = wave_sum(c_pairs);
+          c_disc = wave_sum(c_disc);
+          if (lane == 0) {
+            if (c_call) atomicAdd(&callable_[a], c_call);
+            if (c_poly) atomicAdd(&poly[a], c_poly);
+            if (c_pairs) atomicAdd(&pairs[a], c_pairs);
+            if (c_disc) atomicAdd(&disc[a], c_disc);
+          }
+          at += c_poly;
+        }
+      }
+      s = e;
+      ++a;
+      while (a < nacc && off[a + 1] <= s) ++a;  // (accessions without sites)
+    }
+    if (!kEmit && lane == 0) blk[b] = at;
+  }
+}
+
+// t[i] = the counts before block i; *total = all of them (as k_mask_scan)
+__global__ __launch_bounds__(kScanBlock) void k_var_scan(unsigned long long* __restrict__ t, uint64_t nblocks,
+                                                         unsigned long long* __restrict__ total) {
+  __shared__ unsigned long long s_w[kScanBlock / 64];
+  const unsigned lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  unsigned long long carry = 0;  // (the same in every thread)
+  for (uint64_t base = 0; base < nblocks; base += kScanBlock) {
+    const uint64_t i = base + threadIdx.x;
+    const unsigned long long v = i < nblocks ? t[i] : 0ull;
+    unsigned long long incl = v;
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned long long up = (unsigned long long)__shfl_up((long long)incl, d, 64);
+      if (lane >= (unsigned)d) incl += up;
+    }
+    if (lane == 63) s_w[wv] = incl;
+    __syncthreads();
+    unsigned long long before = 0, all = 0;
+    for (unsigned w = 0; w < kScanBlock / 64; ++w) {
+      const unsigned long long x = s_w[w];
+      if (w < wv) before += x;
+      all += x;
+    }
+    if (i < nblocks) t[i] = carry + before + incl - v;
+    carry += all;
+    __syncthreads();  // (s_w is written again in the next step)
+  }
+  if (threadIdx.x == 0) *total = carry;
+}
+
+unsigned var_grid(uint64_t items, unsigned per_block) {
+  return grid_cap(grid_for(items, per_block, (unsigned)ctx().num_cus * 8), "var_grid");
+}
+
+}  // namespace
+
+extern "C" {
+
+int mg_variants_create(const uint64_t* lengths, uint32_t nacc, mg_variants** out) {
+  MG_REQUIRE_READY();
+  if (!out || (nacc && !lengths) || nacc > MG_REC_REF_MASK) return fail(MG_ERR_ARG, "null argument");
+  *out = nullptr;
+  hipStream_t st = ctx().stream;
+  std::unique_ptr<mg_variants> h(new mg_variants());
+  h->nacc = nacc;
+  std::vector<uint64_t> h_off(nacc + 1ull, 0);
+  for (uint32_t a = 0; a < nacc; ++a) {
+    if (lengths[a] >> 48) return fail(MG_ERR_ARG, "accession %u: length %llu", a, (unsigned long long)lengths[a]);
+    h_off[a + 1] = h_off[a] + lengths[a];
+  }
+  h->nsites = h_off[nacc];
+  h->nblocks = (h->nsites + kStep - 1) / kStep;
+  MG_TRY(h->off.alloc((nacc + 1ull) * sizeof(uint64_t)));
+  MG_TRY(h->len.alloc((nacc + 1ull) * sizeof(uint64_t)));
+  MG_TRY(h->sums.alloc((5ull * nacc + 1) * sizeof(uint64_t)));
+  MG_TRY(h->blk.alloc((h->nblocks + 1) * sizeof(uint64_t)));
+  const uint64_t bytes = h->nsites * 16 + 16;
+  hipError_t e = hipMalloc((void**)&h->cnt, bytes);
+  if (e != hipSuccess) {  // (as mg_coverage_create: the allocator's cached blocks back to the runtime, once)
+    (void)hipGetLastError();
+    h->cnt = nullptr;
+    (void)hipStreamSynchronize(st);
+    pool_release_all();
+    e = hipMalloc((void**)&h->cnt, bytes);
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    h->cnt = nullptr;
+    return fail(MG_ERR_NOMEM, "the allele counts (%llu bytes, sixteen per reference base) do not fit: %s", (unsigned long long)bytes,
+                hipGetErrorString(e));
+  }
+  MG_HIP(hipMemsetAsync(h->cnt, 0, bytes, st));
+  MG_HIP(hipMemsetAsync(h->sums.p, 0, (5ull * nacc + 1) * sizeof(uint64_t), st));
+  MG_HIP(hipMemcpyAsync(h->off.p, h_off.data(), (nacc + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  if (nacc) MG_HIP(hipMemcpyAsync(h->len.p, lengths, (uint64_t)nacc * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  MG_HIP(hipStreamSynchronize(st));  // (h_off and the caller's lengths are free from here)
+  *out = h.release();
+  return MG_OK;
+}
+
+int mg_variants_add_dev(mg_variants* h, const mg_aln_rec* d_recs, const mg_aln_bases* d_bases, const uint8_t* d_pool, uint64_t n,
+                        double pct_id) {
+  MG_REQUIRE_READY();
+  if (!h || (n && (!d_recs || !d_bases))) return fail(MG_ERR_ARG, "null argument");
+  if (n == 0) return MG_OK;
+  ProfScope ps("var_add");
+  unsigned long long* sums = h->sums.as<unsigned long long>();
+  for (uint64_t at = 0; at < n; at += kLaunchMax) {
+    const uint64_t m = n - at < kLaunchMax ? n - at : kLaunchMax;
+    hipLaunchKernelGGL(k_var_add, dim3(var_grid(m, kBlock)), dim3(kBlock), 0, ctx().stream, d_recs + at, d_bases + at, d_pool, m, pct_id,
+                       h->len.as<uint64_t>(), h->off.as<uint64_t>(), h->nacc, h->cnt, sums, sums + 5ull * h->nacc);
+    MG_HIP(hipGetLastError());
+  }
+  return MG_OK;
+}
+
+int mg_variants_finish(mg_variants* h, uint32_t min_depth, uint32_t min_count, uint32_t freq_permille, uint64_t* alignments,
+                       uint64_t* callable_sites, uint64_t* polymorphic_sites, uint64_t* pairs, uint64_t* discordant, uint64_t* unpiled,
+                       uint64_t* nsites) {
+  MG_REQUIRE_READY();
+  if (!h || !unpiled || !nsites || (h->nacc && (!alignments || !callable_sites || !polymorphic_sites || !pairs || !discordant)))
+    return fail(MG_ERR_ARG, "null argument");
+  if (min_depth < 2 || min_count < 1 || freq_permille > 500)
+    return fail(MG_ERR_ARG, "min_depth %u (at least 2), min_count %u (at least 1), freq_permille %u (at most 500)", min_depth, min_count,
+                freq_permille);
+  hipStream_t st = ctx().stream;
+  const uint64_t nacc = h->nacc;
+  unsigned long long* sums = h->sums.as<unsigned long long>();
+  unsigned long long* blk = h->blk.as<unsigned long long>();
+  h->sites.release();
+  h->npoly = 0;
+  h->finished = false;
+  if (nacc) MG_HIP(hipMemsetAsync(sums + nacc, 0, 4 * nacc * sizeof(uint64_t), st));
+  if (h->nblocks) {
+    const unsigned grid = var_grid(h->nblocks, kBlock / 64);
+    {
+      ProfScope ps("var_sums");
+      hipLaunchKernelGGL(k_var_sites<false>, dim3(grid), dim3(kBlock), 0, st, h->cnt, h->nsites, h->nblocks, h->off.as<uint64_t>(), h->nacc,
+                         sums, min_depth, min_count, freq_permille, sums + nacc, sums + 2 * nacc, sums + 3 * nacc, sums + 4 * nacc,
+                         blk + 1, (mg_variant_site*)nullptr, (uint64_t)0);
+      MG_HIP(hipGetLastError());
+    }
+    {
+      ProfScope ps("var_scan");
+      hipLaunchKernelGGL(k_var_scan, dim3(1), dim3(kScanBlock), 0, st, blk + 1, h->nblocks, blk);
+      MG_HIP(hipGetLastError());
+    }
+    MG_HIP(hipMemcpyAsync(&h->npoly, blk, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    MG_HIP(hipStreamSynchronize(st));
+    if (h->npoly) {
+      ProfScope ps("var_emit");
+      MG_TRY(h->sites.alloc(h->npoly * sizeof(mg_variant_site)));
+      hipLaunchKernelGGL(k_var_sites<true>, dim3(grid), dim3(kBlock), 0, st, h->cnt, h->nsites, h->nblocks, h->off.as<uint64_t>(), h->nacc,
+                         sums, min_depth, min_count, freq_permille, sums + nacc, sums + 2 * nacc, sums + 3 * nacc, sums + 4 * nacc,
+                         blk + 1, h->sites.as<mg_variant_site>(), h->npoly);
+      MG_HIP(hipGetLastError());
+    }
+  }
+  std::vector<uint64_t> s(5 * nacc + 1);
+  MG_HIP(hipMemcpyAsync(s.data(), sums, s.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  MG_HIP(hipStreamSynchronize(st));
+  for (uint64_t a = 0; a < nacc; ++a) {
+    alignments[a] = s[a];
+    callable_sites[a] = s[nacc + a];
+    polymorphic_sites[a] = s[2 * nacc + a];
+    pairs[a] = s[3 * nacc + a];
+    discordant[a] = s[4 * nacc + a];
+  }
+  *unpiled = s[5 * nacc];
+  *nsites = h->npoly;
+  h->finished = true;
+  return MG_OK;
+}
+
+int mg_variants_fetch_sites(mg_variants* h, mg_variant_site* out) {
+  MG_REQUIRE_READY();
+  if (!h) return fail(MG_ERR_ARG, "null argument");
+  if (!h->finished) return fail(MG_ERR_STATE, "the sites are fetched after mg_variants_finish");
+  if (h->npoly && !out) return fail(MG_ERR_ARG, "null argument");
+  if (h->npoly) {
+    hipStream_t st = ctx().stream;
+    MG_HIP(hipMemcpyAsync(out, h->sites.p, h->npoly * sizeof(mg_variant_site), hipMemcpyDeviceToHost, st));
+    MG_HIP(hipStreamSynchronize(st));
+  }
+  return MG_OK;
+}
+
+void mg_variants_free(mg_variants* h) { delete h; }
+
+}  // extern "C"

@@ -29,7 +29,7 @@ import time
 
 import numpy as np
 
-from . import _hip, assignments, bam, cli, collate, coverage, identity, side_reads
+from . import _hip, assignments, bam, cli, collate, coverage, identity, side_reads, variants
 from .side_outputs import ASSIGNMENTS, COVERAGE, DEPTH, IDENTITY, FAMILIES, SideOutputs, check_flags, write_headers
 
 start = time.time()
@@ -286,6 +286,24 @@ def _host_side(lines, of, dtype):
     return np.array(out, dtype=dtype) if out else np.zeros(0, dtype=dtype)
 
 
+def _host_bases(lines):
+    """_host_side for the bases: (entries BASES_DTYPE[], the pool's bytes) of the lines the host tokeniser retains."""
+    ent, pool = variants.entries_and_pool(f for f in map(coverage.retained_fields, lines) if f is not None)
+    return (np.array(ent, dtype=_hip.BASES_DTYPE) if ent else np.zeros(0, dtype=_hip.BASES_DTYPE)), pool
+
+
+def _join_bases(parts):
+    """Every chunk's (entries, pool) -> one: the pools joined, a piled entry's offset moved up by the pools before it."""
+    ents, pools, at = [], [], 0
+    for ent, pool in parts:
+        ent = ent.copy()
+        ent['off'][ent['span'] > 0] += np.uint64(at)
+        ents.append(ent)
+        pools.append(pool)
+        at += len(pool)
+    return (np.concatenate(ents) if ents else np.zeros(0, dtype=_hip.BASES_DTYPE)), b''.join(pools)
+
+
 def _leading_header(chunk, header, state):
     """--coverage on the chunked path: the stream's leading '@' lines -> header, scanned only while lines start with '@'."""
     if not state['leading']:
@@ -316,14 +334,16 @@ def _acc_index_of(hip, acc_index):
     return hip.acc_index(names)
 
 
-def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names=None, places=None, header=None, edits=None):
+def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names=None, places=None, header=None, edits=None,
+                        bases=None):
     """SAM (paf=True: PAF) stream -> records on the MI355X (mg_sam_tokenize / mg_paf_tokenize).  A line the reference
     cannot parse is re-run through the host tokeniser so that the very same exception (type and message) surfaces.
     read_names (--read_assignments): a list that takes every chunk's read names, (bytes, offsets) from mg_sam_tokenize_named — a read that
     goes on from the chunk before is named there.
     places (--coverage): a list that takes every chunk's places (PLACE_DTYPE[], beside its records); header: a list that takes the
     stream's leading '@' lines as the chunks pass.
-    edits (--identity): a list that takes every chunk's edits (EDIT_DTYPE[], beside its records)."""
+    edits (--identity): a list that takes every chunk's edits (EDIT_DTYPE[], beside its records).
+    bases (--variants): a list that takes every chunk's (entries BASES_DTYPE[], pool bytes); _join_bases makes them one."""
     hip = _hip.Hip.get()
     hstate = {'leading': True}
     index = _acc_index_of(hip, acc_index)
@@ -333,10 +353,11 @@ def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names
             if header is not None:
                 _leading_header(chunk, header, hstate)
             try:
-                # -> records, last QNAME, then what was asked for: the names, the places, the edits, in that order
+                # -> records, last QNAME, then what was asked for: the names, the places, the edits, the bases, in that order
                 recs, prev, *sides = hip.sam_tokenize(chunk, index, prev, paf=paf, named=read_names is not None,
-                                                      placed=places is not None, edited=edits is not None)
-                for into, got in zip([x for x in (read_names, places, edits) if x is not None], sides):
+                                                      placed=places is not None, edited=edits is not None,
+                                                      **({'based': True} if bases is not None else {}))
+                for into, got in zip([x for x in (read_names, places, edits, bases) if x is not None], sides):
                     into.append(got)
             except _hip.SamParseError as e:
                 lines = bytes(chunk).split(b'\n')
@@ -365,6 +386,8 @@ def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names
                     places.append(_host_side((ln.decode('utf-8') for ln in lines), coverage.placement, _hip.PLACE_DTYPE))
                 if edits is not None:
                     edits.append(_host_side((ln.decode('utf-8') for ln in lines), identity.edit_of, _hip.EDIT_DTYPE))
+                if bases is not None:
+                    bases.append(_host_bases(ln.decode('utf-8') for ln in lines))
             parts.append(recs)
     finally:
         index.free()
@@ -484,12 +507,12 @@ def assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=True):
     return taxids2abs, multimapped, {}
 
 
-def _unique_feed(sides, hip, d_places, d_edits, pct_id):
+def _unique_feed(sides, hip, d_places, d_edits, pct_id, d_bases=None):
     """The on_verdicts hook of Hip.profile_assign_dev_records under --side_reads unique: the records, masked by their reads'
-    verdicts, go to the accumulators beside the side arrays at d_places / d_edits."""
+    verdicts, go to the accumulators beside the side arrays at d_places / d_edits / d_bases (entries, pool)."""
     def feed(d_recs, n, d_words, nreads, d_ref2tax, nref):
         if n:  # (as add_batch: an empty stream adds nothing)
-            sides.add_unique_ptrs(hip, d_recs, d_places, d_edits, n, pct_id, d_words, nreads, d_ref2tax, nref)
+            sides.add_unique_ptrs(hip, d_recs, d_places, d_edits, n, pct_id, d_words, nreads, d_ref2tax, nref, d_bases)
     return feed
 
 
@@ -535,25 +558,26 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
         if _assignments:
             # per read 16 B of verdict words, 8 B of name offset and the name itself (~40 B); a read is at least one record
             need += 64 * nrec
-        if sides.placed:
+        if sides.sized:
             lengths = coverage.lengths_of(sides.header, acc2info)
         need += sides.need_bytes(lengths, len(acc_index), nrec)
         if need > free + pooled:
             return None
         chunk_bytes = int(os.environ.get('MG_STREAM_CHUNK_BYTES', 0))
+        based = {'based': True} if sides.based else {}  # (without --variants the calls are what they were)
         try:
             if not streamed and not _bam and not _collate:  # the whole text up, then one tokeniser call
                 d_text, nbytes = hip.upload_file(path)
                 batch = hip.sam_tokenize_dev_batch(d_text.ptr, nbytes, index, '', paf=_paf, named=_assignments, placed=sides.placed,
-                                                   edited=sides.edited)
+                                                   edited=sides.edited, **based)
             elif _bam:  # (a BAM is always streamed: ~16 B of records per ~60 B of the compressed file stay resident)
                 batch = hip.bam_stream_file(path, index, chunk_bytes=chunk_bytes, collate=_collate, named=_assignments,
-                                            placed=sides.placed, edited=sides.edited)
+                                            placed=sides.placed, edited=sides.edited, **based)
             else:
                 # reader threads -> page-locked chunks -> HBM -> tokeniser, chunk i + 1 in flight while chunk i is tokenised
                 # (a collation is always streamed: the keys ride on the stream's batches)
                 batch = hip.sam_stream_file(path, index, paf=_paf, chunk_bytes=chunk_bytes, collate=_collate, named=_assignments,
-                                            placed=sides.placed, edited=sides.edited)
+                                            placed=sides.placed, edited=sides.edited, **based)
         except _hip.SamParseError:
             return None
         except _hip.HipError as e:
@@ -570,7 +594,8 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
             # --side_reads unique: the records are fed from inside stage C, where every read's verdict is known and the batch
             # (the collated one, with its permuted side arrays, where it was collated) is still alive
             feed = _unique_feed(sides, hip, batch.places_ptr if sides.placed and batch.count else None,
-                                batch.edits_ptr if sides.edited and batch.count else None, float(args.pct_id))
+                                batch.edits_ptr if sides.edited and batch.count else None, float(args.pct_id),
+                                (batch.bases_ptr, batch.pool_ptr) if sides.based and batch.count else None)
             res = hip.profile_assign_dev_records(batch.ptr, batch.count, ref2tax, len(taxids), float(args.pct_id), [batch],
                                                  resident=_resident, assign=_assignments, on_verdicts=feed)
         else:
@@ -822,28 +847,33 @@ def _map_and_process_sided(args, instream, acc2info, taxid2info, _want_lists, _r
     acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
     _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
     names, header = ([] if _assignments else None), []
-    places, edits = ([] if sides.placed else None), ([] if sides.edited else None)
+    places, edits, bases = ([] if sides.placed else None), ([] if sides.edited else None), ([] if sides.based else None)
     recs = _device_tokenise(instream, acc_index, decode=(args.input_type != 'sam'), read_names=names, places=places, header=header,
-                            edits=edits)
+                            edits=edits, bases=bases)
     place = np.concatenate(places) if places else np.zeros(0, dtype=_hip.PLACE_DTYPE)
     edit = np.concatenate(edits) if edits else np.zeros(0, dtype=_hip.EDIT_DTYPE)
     assert places is None or len(place) == len(recs)
     assert edits is None or len(edit) == len(recs)
+    entry, pool = _join_bases(bases or [])
+    assert bases is None or len(entry) == len(recs)
     hip = _hip.Hip.get()
     d_recs = hip.array(recs if len(recs) else np.zeros(1, _hip.REC_DTYPE))
     if sides.unique:  # (--side_reads unique: the uploaded places and edits live until stage C has fed the accumulators)
-        d_place = d_edit = None
+        d_place = d_edit = d_entry = d_pool = None
         try:
             try:
                 sides.open(hip, coverage.lengths_of(header, acc2info), acc_index)
                 if len(recs):
                     d_place = hip.array(place.view(np.uint8)) if sides.placed else None
                     d_edit = hip.array(edit.view(np.uint8)) if sides.edited else None
+                    if sides.based:
+                        d_entry = hip.array(entry.view(np.uint8))
+                        d_pool = hip.array(np.frombuffer(pool, dtype=np.uint8) if pool else np.zeros(16, np.uint8))
             except BaseException:
                 d_recs.free()  # (stage C has not taken the records over yet)
                 raise
             feed = _unique_feed(sides, hip, d_place.ptr if d_place is not None else None, d_edit.ptr if d_edit is not None else None,
-                                float(args.pct_id))
+                                float(args.pct_id), (d_entry.ptr, d_pool.ptr) if d_pool is not None else None)
             res = hip.profile_assign_dev_records(d_recs.ptr, len(recs), ref2tax, len(taxids), float(args.pct_id), [d_recs],
                                                  resident=_resident, assign=_assignments, on_verdicts=feed)
         except BaseException:
@@ -854,23 +884,32 @@ def _map_and_process_sided(args, instream, acc2info, taxid2info, _want_lists, _r
                 d_place.free()
             if d_edit is not None:
                 d_edit.free()
+            for d in (d_entry, d_pool):
+                if d is not None:
+                    d.free()
         sides.close(acc2info, taxid2info)
         return _sided_tail(args, res, names, taxids, taxid2info, _want_lists, _assignments)
     try:
         sides.open(hip, coverage.lengths_of(header, acc2info), acc_index)
         if len(recs):
-            d_place = d_edit = None
+            d_place = d_edit = d_entry = d_pool = None
             try:
                 d_place = hip.array(place.view(np.uint8)) if sides.placed else None
                 d_edit = hip.array(edit.view(np.uint8)) if sides.edited else None
+                if sides.based:
+                    d_entry = hip.array(entry.view(np.uint8))
+                    d_pool = hip.array(np.frombuffer(pool, dtype=np.uint8) if pool else np.zeros(16, np.uint8))
                 sides.add_ptrs(d_recs.ptr, d_place.ptr if sides.placed else None, d_edit.ptr if sides.edited else None, len(recs),
-                               float(args.pct_id))
+                               float(args.pct_id), (d_entry.ptr, d_pool.ptr) if sides.based else None)
                 hip.sync()
             finally:
                 if d_place is not None:
                     d_place.free()
                 if d_edit is not None:
                     d_edit.free()
+                for d in (d_entry, d_pool):
+                    if d is not None:
+                        d.free()
         sides.close(acc2info, taxid2info)
     except BaseException:
         sides.free()
@@ -1109,7 +1148,7 @@ def compute_abundances(args, infile, acc2info, tax2info):
             seams_untouched = seams_untouched and done is not None  # (None: rank 0 streams the file, alone)
     if args.input_type == 'sam' and seams_untouched and done is None:
         # a plain file (SAM, or a PAF replay): all the way on the device
-        sides.header = _sam_header_lines(infile) if sides.placed else None
+        sides.header = _sam_header_lines(infile) if sides.sized else None
         done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _paf=paf,
                                     _assignments=want_rows, _sides=sides)
     if done is None:
@@ -1168,7 +1207,7 @@ def _compute_abundances_regrouped(args, infile, acc2info, tax2info, on_device, s
     sides = SideOutputs.of(args, infile, enabled=seams_untouched)
     if seams_untouched:
         # (a BAM's reference list's l_ref equals the header's @SQ text: the text is what gives the lengths)
-        sides.header = header_of(infile) if sides.placed else None
+        sides.header = header_of(infile) if sides.sized else None
         done = map_and_process_file(args, infile, acc2info, tax2info, _want_lists=False, _resident=on_device, _bam=is_bam,
                                     _collate=collating, _assignments=want_rows and not collating, _sides=sides)
     if done is None:

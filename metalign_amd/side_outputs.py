@@ -1,11 +1,11 @@
 """Stage C's side outputs: what is filled from the tokenised records beside the profile.
 
-A family (COVERAGE, DEPTH, IDENTITY) is a descriptor: its flags, the side array of a batch it reads, its refusals, its header,
+A family (COVERAGE, DEPTH, IDENTITY, VARIANTS) is a descriptor: its flags, the side array of a batch it reads, its refusals, its header,
 what it holds on the device, and how its device accumulator is opened and turned into the file's block.  ASSIGNMENTS
 (--read_assignments) shares only the flag test, the refusal and the header: its rows come from stage C itself.
 
 SideOutputs is the families wanted for ONE input file.  map_and_profile opens it, feeds it the records and closes it; the
-order is always coverage, depth, identity, and whatever was opened is freed on every way out.
+order is always coverage, depth, identity, variants, and whatever was opened is freed on every way out.
 
 --side_reads unique (metalign_amd/side_reads.py is the definition): the accumulators are fed a copy of the records in which every
 record that is not unique evidence for its taxon carries FLAG 2048 (mg_records_mask_unique_dev), the bit by which none of them
@@ -16,7 +16,7 @@ import sys
 
 import numpy as np
 
-from . import _hip, assignments, coverage, depth, identity, side_reads
+from . import _hip, assignments, coverage, depth, identity, side_reads, variants
 
 
 def _flag(args, name):
@@ -60,7 +60,7 @@ class _Assignments(_Flags):
 
 
 class _Family(_Flags):
-    """side: the side array of a batch it reads ('places' / 'edits').  nomem: the exit text when the device refuses the memory,
+    """side: the side array of a batch it reads ('places' / 'edits' / 'bases': the entries and their pool).  nomem: the exit text when the device refuses the memory,
     with the MB figure of nomem_mb."""
     side = nomem = None
 
@@ -204,8 +204,65 @@ class _Identity(_Family):
         self.append(args, path, identity.identity(lines, acc2info, args.pct_id), acc2info, taxid2info)
 
 
-ASSIGNMENTS, COVERAGE, DEPTH, IDENTITY = _Assignments(), _Coverage(), _Depth(), _Identity()
-FAMILIES = (COVERAGE, DEPTH, IDENTITY)  # (the order of every open, add and close)
+class _Variants(_Family):
+    """--variants or --variant_sites: either one asks for the per-site allele counts."""
+    flags, side = ('variants', 'variant_sites'), 'bases'
+    refuse_world = 'Error: --variants and --variant_sites run in one process on one GPU; start it without torch.distributed.run.'
+    refuse_paf = 'Error: --variants and --variant_sites need SAM or BAM alignments: a PAF line has no CIGAR and SEQ columns.'
+    nomem = 'Error: --variants keeps sixteen bytes per reference base on the GPU; %d MB for this database do not fit.'
+
+    @staticmethod
+    def params(args):
+        return variants.params(getattr(args, 'variant_min_depth', 5), getattr(args, 'variant_min_count', 2),
+                               getattr(args, 'variant_min_freq', 0.05))
+
+    def write_header(self, args):
+        p = self.params(args)
+        if _flag(args, 'variants'):
+            variants.write_variants(args.variants, p)
+        if _flag(args, 'variant_sites'):
+            variants.write_sites(args.variant_sites, p)
+
+    def device_bytes(self, args, lengths, nacc, nrec):
+        """16 B per reference base and five sums per accession; per record a 16 B entry (and as much again where a collation
+        permutes them) and the pool's 4-bit codes — 75 B for a 150-base read, reckoned as 80 B with the entry."""
+        return 16 * sum(lengths.values()) + 40 * nacc + 16 * nrec + 80 * nrec
+
+    def nomem_mb(self, args, lengths, acc_index):
+        return self.device_bytes(args, lengths, len(acc_index), 0) >> 20
+
+    def _open(self, args, hip, lengths, acc_index):
+        return hip.variants(lengths_array(lengths, acc_index))
+
+    def close(self, args, source, lengths, dev, acc_index, acc2info, taxid2info):
+        """The device's sums and polymorphic sites -> the files' blocks."""
+        p = self.params(args)
+        try:
+            aln, call, poly, pairs, disc, unpiled, sites = dev.result(*p)
+        finally:
+            dev.free()
+        names = {i: a for a, i in acc_index.items()}
+        per = {a: [int(aln[i]), int(call[i]), int(poly[i]), int(pairs[i]), int(disc[i])] for a, i in acc_index.items() if aln[i]}
+        # (the device orders the sites by accession row; the file by db_info's order, which is the rows' where db_info has no
+        # accession twice)
+        order = {a: k for k, a in enumerate(acc2info)}
+        rows = sorted(((names[int(s['acc'])], int(s['pos0']), tuple(int(x) for x in s['n'])) for s in sites),
+                      key=lambda s: (order[s[0]], s[1]))
+        self.append(args, source, variants.Variants(lengths, per, rows, unpiled), acc2info, taxid2info)
+
+    def append(self, args, source, var, acc2info, taxid2info):
+        p, source = self.params(args), source_label(args, source)
+        if _flag(args, 'variants'):
+            variants.write_variants(args.variants, p, variants.rows(var, acc2info, taxid2info), var.unpiled, source=source, append=True)
+        if _flag(args, 'variant_sites'):
+            variants.write_sites(args.variant_sites, p, var.sites, source=source, append=True)
+
+    def append_from_definition(self, args, path, lines, acc2info, taxid2info):
+        self.append(args, path, variants.variants(lines, acc2info, args.pct_id, self.params(args)), acc2info, taxid2info)
+
+
+ASSIGNMENTS, COVERAGE, DEPTH, IDENTITY, VARIANTS = _Assignments(), _Coverage(), _Depth(), _Identity(), _Variants()
+FAMILIES = (COVERAGE, DEPTH, IDENTITY, VARIANTS)  # (the order of every open, add and close)
 
 
 def check_flags(args):
@@ -221,6 +278,10 @@ def check_flags(args):
             sys.exit(fam.refuse_paf)
     if int(getattr(args, 'depth_window_size', 1000)) < 1:
         sys.exit('Error: --depth_window_size must be at least 1.')
+    try:
+        VARIANTS.params(args)
+    except ValueError as e:
+        sys.exit('Error: %s' % e)
     if reads_mode(args) == 'unique' and not any(fam.wanted(args) for fam in FAMILIES):
         sys.exit('Error: --side_reads unique needs one of --coverage, --depth, --depth_windows, --identity.')
 
@@ -245,6 +306,8 @@ class SideOutputs:
         self.families = tuple(f for f in FAMILIES if f in families)
         self.placed = any(f.side == 'places' for f in self.families)
         self.edited = any(f.side == 'edits' for f in self.families)
+        self.based = any(f.side == 'bases' for f in self.families)
+        self.sized = self.placed or self.based  # (the families that need the accessions' lengths)
         self.reads = reads_mode(args)
         self.unique = bool(self.families) and self.reads == 'unique'
         self._open = []  # (family, accumulator) of what is open
@@ -254,7 +317,7 @@ class SideOutputs:
     def of(cls, args, source, header=None, enabled=True):
         """What args asks for (enabled=False: nothing).  header: a callable, called where an output needs the lengths."""
         sides = cls(args, [f for f in FAMILIES if enabled and f.wanted(args)], source)
-        if header is not None and sides.placed:
+        if header is not None and sides.sized:
             sides.header = header()
         return sides
 
@@ -287,23 +350,25 @@ class SideOutputs:
             self.free()
             raise
 
-    def add_ptrs(self, d_recs, d_places, d_edits, n, pct_id):
-        """n records and their side arrays at device pointers (asynchronous, as the accumulators' add_ptr)."""
+    def add_ptrs(self, d_recs, d_places, d_edits, n, pct_id, d_bases=None):
+        """n records and their side arrays at device pointers (asynchronous, as the accumulators' add_ptr).  d_bases: the pair
+        (entries, pool)."""
+        side = {'places': d_places, 'edits': d_edits, 'bases': d_bases}
         try:
             for fam, dev in self._open:
-                dev.add_ptr(d_recs, d_places if fam.side == 'places' else d_edits, n, pct_id)
+                dev.add_ptr(d_recs, side[fam.side], n, pct_id)
         except BaseException:
             self.free()
             raise
 
-    def add_unique_ptrs(self, hip, d_recs, d_places, d_edits, n, pct_id, d_words, nreads, d_ref2tax, nref):
+    def add_unique_ptrs(self, hip, d_recs, d_places, d_edits, n, pct_id, d_words, nreads, d_ref2tax, nref, d_bases=None):
         """add_ptrs under --side_reads unique, from inside stage C: the records go through mg_records_mask_unique_dev into a copy,
         which is what the accumulators read.  Returns with the work done: the copy is freed on every way out."""
         copy = None
         try:
             copy = hip.empty(16 * max(int(n), 1), np.uint8)
             hip.records_mask_unique(d_recs, n, d_words, nreads, d_ref2tax, nref, copy.ptr)
-            self.add_ptrs(copy.ptr, d_places, d_edits, n, pct_id)
+            self.add_ptrs(copy.ptr, d_places, d_edits, n, pct_id, d_bases)  # (the masked records beside the untouched entries)
             hip.sync()
         except BaseException:
             self.free()
