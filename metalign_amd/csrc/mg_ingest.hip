@@ -357,10 +357,13 @@ __global__ void k_sam_parse(const uint8_t* __restrict__ text, const uint64_t* __
               if (!tok) kind = kErrValue;
             }
             if (kind == kErrNone && total == 0) kind = kErrZeroDiv;
-            uint64_t slen = (fe[9] - fb[9] == 1 && text[fb[9]] == '*') ? 0 : fe[9] - fb[9];
-            if (thin && text[fb[9]] == MG_THIN_MARK) {  // a line thinned by the file reader (mg_stream.hip): SEQ = mark + its length in decimal
-              slen = 0;
-              for (uint64_t c = fb[9] + 1; c < fe[9]; ++c) slen = slen * 10 + (uint64_t)(text[c] - '0');
+            uint64_t slen = 0;
+            if (kind == kErrNone) {  // (so nf >= 12: a line of 6 to 9 fields never set fb[9], fe[9])
+              slen = (fe[9] - fb[9] == 1 && text[fb[9]] == '*') ? 0 : fe[9] - fb[9];
+              if (thin && text[fb[9]] == MG_THIN_MARK) {  // a line thinned by the file reader (mg_stream.hip): SEQ = mark + its length in decimal
+                slen = 0;
+                for (uint64_t c = fb[9] + 1; c < fe[9]; ++c) slen = slen * 10 + (uint64_t)(text[c] - '0');
+              }
             }
             if (kind == kErrNone && (slen > MG_REC_MAX_SEQLEN || matched > 0xffffffffull || total > 0xffffffffull))
               kind = kErrOverflow;
