@@ -180,15 +180,20 @@ def coverage(lines, acc2info, pct_id):
 
 def coverage_of_records(recs, places, accessions, lengths, pct_id):
     """The same from (record, place) pairs: recs with the fields of mg_aln_rec (ref_new, matched, total, flag_len), places
-    (pos0, span) per record, accessions[row] the name of accession row `ref_new & 0x7fffffff` -> Coverage."""
-    placed = []
+    (pos0, span) per record, accessions[row] the name of accession row `ref_new & 0x7fffffff` -> Coverage.  A counting record whose row is at or beyond the
+    accessions is unplaced, as on the device."""
+    placed, no_row = [], 0
     for r, (pos0, span) in zip(recs, places):
         flag = int(r['flag_len']) & FLAG_MASK
         if not counts(flag, int(r['matched']), int(r['total']), pct_id):
             continue
-        placed.append((accessions[int(r['ref_new']) & 0x7FFFFFFF], int(pos0), int(span)))
+        row = int(r['ref_new']) & 0x7FFFFFFF
+        if row >= len(accessions):  # (no such accession: the device counts the record as unplaced)
+            no_row += 1
+            continue
+        placed.append((accessions[row], int(pos0), int(span)))
     per, unplaced = accumulate(placed, lengths)
-    return Coverage(lengths, per, unplaced)
+    return Coverage(lengths, per, unplaced + no_row)
 
 
 def rows(cov, acc2info, taxid2info):

@@ -78,6 +78,33 @@ void* pool_alloc(uint64_t bytes, uint64_t* got) {
   return p;
 }
 
+int own_alloc(void** p, uint64_t bytes, const char* fmt, uint64_t said) {
+  hipError_t e = hipMalloc(p, bytes);
+  if (e != hipSuccess) {  // (as pool_alloc: the cached blocks back to the runtime, once)
+    (void)hipGetLastError();
+    *p = nullptr;
+    (void)hipStreamSynchronize(ctx().stream);
+    pool_release_all();
+    e = hipMalloc(p, bytes);
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    *p = nullptr;
+    return fail(MG_ERR_NOMEM, fmt, (unsigned long long)said, hipGetErrorString(e));
+  }
+  return MG_OK;
+}
+
+int fetch_sums(const void* d_sums, uint64_t nacc, uint64_t* const* out, unsigned nvals, uint64_t* miss) {
+  std::vector<uint64_t> h(nvals * nacc + 1);
+  MG_HIP(hipMemcpyAsync(h.data(), d_sums, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx().stream));
+  MG_HIP(hipStreamSynchronize(ctx().stream));
+  for (unsigned k = 0; k < nvals; ++k)
+    for (uint64_t a = 0; a < nacc; ++a) out[k][a] = h[k * nacc + a];
+  *miss = h[nvals * nacc];
+  return MG_OK;
+}
+
 // With the library's side streams in use (stage A x2, stage C) a block freed by the host may still be read or written
 // by a kernel queued on ANOTHER stream than the one that will reuse it — the free list knows nothing about streams, and
 // a handle destructor (an exception in the middle of a pipelined run, a __del__) does not synchronise.  Such blocks

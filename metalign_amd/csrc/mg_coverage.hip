@@ -9,13 +9,13 @@
 //                   the total, so neighbouring lanes take neighbouring words of a long record and no lane walks one alone.
 //                 * Bits are only ever set: a relaxed load that finds them set skips the atomic (a stale load costs one atomic
 //                   that was not needed).  At depth 40 that is most of them.
-//                 * Most records of a sample hit a few accessions: the sums go to hashed LDS bins (a wavefront whose records
-//                   share one accession adds once), flushed with one global add per bin and workgroup when it ends; a bin
-//                   that finds no slot within kCovProbe adds to memory directly.
+//                 * Most records of a sample hit a few accessions: the sums go to hashed LDS bins.
 //   k_cov_count   the set bits per accession: every wavefront takes blocks of kCountWords words, finds the accession of its
 //                 first word in the offsets, and gives one 64-bit add per block and accession.
+// The flattened list, the bins and the wavefront's sum are mg_side_dev.h's (WaveList, AccBins, wave_sum).
 #include "mg_internal.h"
 #include "mg_coverage_core.h"
+#include "mg_side_dev.h"
 
 using namespace mg;
 
@@ -31,32 +31,23 @@ struct mg_coverage {
 
 namespace {
 
-constexpr unsigned kCovBlock = 256, kCovBins = 1024, kCovProbe = 8;
-constexpr uint32_t kCovEmpty = 0xffffffffu;
+constexpr unsigned kCovBlock = 256, kCovBins = 1024;
 constexpr uint64_t kCountWords = 1024;  // per wavefront and step of k_cov_count
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(kCovBlock) void k_cov_add(const mg_aln_rec* __restrict__ recs, const mg_aln_place* __restrict__ place,
                                                        uint64_t n, double pct_id, const uint64_t* __restrict__ len,
                                                        const uint64_t* __restrict__ off, uint32_t nacc, uint32_t* __restrict__ bits,
                                                        unsigned long long* __restrict__ aln, unsigned long long* __restrict__ bases,
                                                        unsigned long long* __restrict__ unplaced) {
-  __shared__ uint32_t s_key[kCovBins];
-  __shared__ unsigned long long s_cnt[kCovBins], s_len[kCovBins];
-  __shared__ unsigned long long s_unplaced;
-  for (unsigned i = threadIdx.x; i < kCovBins; i += kCovBlock) { s_key[i] = kCovEmpty; s_cnt[i] = 0; s_len[i] = 0; }
-  if (threadIdx.x == 0) s_unplaced = 0;
-  __syncthreads();
+  __shared__ AccBins<kCovBins, 2, kCovBlock> bins;
+  unsigned long long* const sums[2] = {aln, bases};
+  bins.init();
   const unsigned lane = threadIdx.x & 63u;
   // (no workgroup barrier inside the loop: a wavefront works on its own 64 records)
   for (uint64_t base = (uint64_t)blockIdx.x * kCovBlock; base < n; base += (uint64_t)gridDim.x * kCovBlock) {
     const uint64_t i = base + threadIdx.x;
     uint32_t a = 0, m0 = 0, m1 = 0;
-    uint64_t clen = 0, gw0 = 0, nw = 0;
+    unsigned long long clen = 0, gw0 = 0, nw = 0;
     bool unp = false;
     if (i < n) {
       const mg_aln_rec r = recs[i];
@@ -74,77 +65,26 @@ __global__ __launch_bounds__(kCovBlock) void k_cov_add(const mg_aln_rec* __restr
         }
       }
     }
-    // the unplaced: one LDS add per wavefront
-    const unsigned long long um = __ballot(unp);
-    if (um && lane == (unsigned)__builtin_ctzll(um)) atomicAdd(&s_unplaced, (unsigned long long)__builtin_popcountll(um));
-    // alignments and aligned bases
-    const unsigned long long pm = __ballot(clen != 0);
-    if (pm) {
-      const unsigned first = (unsigned)__builtin_ctzll(pm);
-      const uint32_t a_first = __shfl(a, (int)first, 64);
-      const bool uniform = __ballot(clen != 0 && a != a_first) == 0;
-      unsigned long long add_cnt = clen ? 1ull : 0ull, add_len = clen;
-      if (uniform) {
-        add_len = wave_sum(add_len);
-        add_cnt = (unsigned long long)__builtin_popcountll(pm);
-      }
-      if (uniform ? lane == first : clen != 0) {
-        const uint32_t h = (a * 2654435761u) >> 22;
-        bool done = false;
-        for (unsigned p = 0; p < kCovProbe && !done; ++p) {
-          const uint32_t s = (h + p) & (kCovBins - 1);
-          const uint32_t k = atomicCAS(&s_key[s], kCovEmpty, a);
-          if (k == kCovEmpty || k == a) {
-            atomicAdd(&s_cnt[s], add_cnt);
-            atomicAdd(&s_len[s], add_len);
-            done = true;
-          }
-        }
-        if (!done) {
-          atomicAdd(&aln[a], add_cnt);
-          atomicAdd(&bases[a], add_len);
-        }
-      }
-    }
+    bins.count_one(unp);                  // the unplaced
+    bins.add(clen != 0, a, &clen, sums);  // alignments and aligned bases
     // the bits: the wavefront's flattened word list, its lanes striding it
-    unsigned long long incl = nw;
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned long long up = __shfl_up(incl, d, 64);
-      if (lane >= (unsigned)d) incl += up;
-    }
-    const unsigned long long total = __shfl(incl, 63, 64);
-    for (unsigned long long j0 = 0; j0 < total; j0 += 64) {  // (uniform: every lane takes part in the shuffles)
+    const WaveList<unsigned long long> words(nw);
+    for (unsigned long long j0 = 0; j0 < words.total; j0 += 64) {  // (uniform: every lane takes part in the shuffles)
       const unsigned long long j = j0 + lane;
-      int lo = 0, hi = 63;  // the first record whose inclusive sum is above j
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        // (each lane asks for its own mid: __shfl reads another lane's value by index)
-        const unsigned long long v = __shfl(incl, mid, 64);
-        if (v > j) hi = mid; else lo = mid + 1;
-      }
-      const unsigned long long r_incl = __shfl(incl, lo, 64), r_nw = __shfl((unsigned long long)nw, lo, 64);
-      const unsigned long long r_gw0 = __shfl((unsigned long long)gw0, lo, 64);
-      const uint32_t r_m0 = __shfl(m0, lo, 64), r_m1 = __shfl(m1, lo, 64);
-      if (j < total) {
-        const unsigned long long k = j - (r_incl - r_nw);
+      const auto it = words.find(j);
+      const unsigned long long r_gw0 = __shfl(gw0, it.lane, 64);
+      const uint32_t r_m0 = __shfl(m0, it.lane, 64), r_m1 = __shfl(m1, it.lane, 64);
+      if (j < words.total) {
         uint32_t mask = 0xffffffffu;
-        if (k == 0) mask &= r_m0;
-        if (k == r_nw - 1) mask &= r_m1;
-        uint32_t* w = bits + (r_gw0 + k);
+        if (it.at == 0) mask &= r_m0;
+        if (it.at == it.len - 1) mask &= r_m1;
+        uint32_t* w = bits + (r_gw0 + it.at);
         const uint32_t old = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if ((old & mask) != mask) (void)__hip_atomic_fetch_or(w, mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
   }
-  __syncthreads();
-  for (unsigned s = threadIdx.x; s < kCovBins; s += kCovBlock) {
-    const uint32_t k = s_key[s];
-    if (k != kCovEmpty && s_cnt[s]) {
-      atomicAdd(&aln[k], s_cnt[s]);
-      atomicAdd(&bases[k], s_len[s]);
-    }
-  }
-  if (threadIdx.x == 0 && s_unplaced) atomicAdd(unplaced, s_unplaced);
+  bins.flush(sums, unplaced);
 }
 
 __global__ __launch_bounds__(kCovBlock) void k_cov_count(const uint32_t* __restrict__ bits, uint64_t nwords,
@@ -155,13 +95,7 @@ __global__ __launch_bounds__(kCovBlock) void k_cov_count(const uint32_t* __restr
   const uint64_t nwaves = (uint64_t)gridDim.x * (kCovBlock / 64);
   for (uint64_t t0 = wave * kCountWords; t0 < nwords; t0 += nwaves * kCountWords) {
     const uint64_t t1 = t0 + kCountWords < nwords ? t0 + kCountWords : nwords;
-    // the accession of word t0: the last a with off[a] <= t0 < off[a + 1] (off[nacc] = nwords > t0)
-    uint32_t lo = 0, hi = nacc;  // the first index in [0, nacc] whose offset is above t0
-    while (lo < hi) {
-      const uint32_t mid = lo + ((hi - lo) >> 1);
-      if (off[mid] > t0) hi = mid; else lo = mid + 1;
-    }
-    uint32_t a = lo - 1;
+    uint32_t a = mgv::owner_of(off, nacc, t0);  // (off[nacc] = nwords > t0)
     uint64_t s = t0;
     while (s < t1) {
       const uint64_t e = off[a + 1] < t1 ? off[a + 1] : t1;
@@ -170,8 +104,7 @@ __global__ __launch_bounds__(kCovBlock) void k_cov_count(const uint32_t* __restr
       sum = wave_sum(sum);
       if (lane == 0 && sum) atomicAdd(&cov[a], sum);
       s = e;
-      ++a;
-      while (a < nacc && off[a + 1] <= s) ++a;  // (accessions without words)
+      a = mgv::owner_from(off, nacc, a, s);  // (over the accessions without words)
     }
   }
 }
@@ -196,20 +129,8 @@ int mg_coverage_create(const uint64_t* lengths, uint32_t nacc, mg_coverage** out
   MG_TRY(c->off.alloc((nacc + 1ull) * sizeof(uint64_t)));
   MG_TRY(c->len.alloc((nacc + 1ull) * sizeof(uint64_t)));
   MG_TRY(c->sums.alloc((3ull * nacc + 1) * sizeof(uint64_t)));
-  hipError_t e = hipMalloc((void**)&c->bits, c->nwords * sizeof(uint32_t) + 16);
-  if (e != hipSuccess) {  // (as pool_alloc: the allocator's cached blocks — a tokenised file's chunks and scratch — back to the runtime, once)
-    (void)hipGetLastError();
-    c->bits = nullptr;
-    (void)hipStreamSynchronize(st);
-    pool_release_all();
-    e = hipMalloc((void**)&c->bits, c->nwords * sizeof(uint32_t) + 16);
-  }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    c->bits = nullptr;
-    return fail(MG_ERR_NOMEM, "the coverage bitmap (%llu bytes, one bit per reference base) does not fit: %s",
-                (unsigned long long)(c->nwords * sizeof(uint32_t)), hipGetErrorString(e));
-  }
+  MG_TRY(own_alloc((void**)&c->bits, c->nwords * sizeof(uint32_t) + 16,
+                   "the coverage bitmap (%llu bytes, one bit per reference base) does not fit: %s", c->nwords * sizeof(uint32_t)));
   MG_HIP(hipMemsetAsync(c->bits, 0, c->nwords * sizeof(uint32_t) + 16, st));
   MG_HIP(hipMemsetAsync(c->sums.p, 0, (3ull * nacc + 1) * sizeof(uint64_t), st));
   MG_HIP(hipMemcpyAsync(c->off.p, h_off.data(), (nacc + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
@@ -225,8 +146,7 @@ int mg_coverage_add_dev(mg_coverage* c, const mg_aln_rec* d_recs, const mg_aln_p
   if (n == 0) return MG_OK;
   ProfScope ps("cov_add");
   unsigned long long* sums = c->sums.as<unsigned long long>();
-  const unsigned grid = grid_cap(grid_for(n, kCovBlock, (unsigned)ctx().num_cus * 8), "cov_grid");
-  hipLaunchKernelGGL(k_cov_add, dim3(grid), dim3(kCovBlock), 0, ctx().stream, d_recs, d_place, n, pct_id, c->len.as<uint64_t>(),
+  hipLaunchKernelGGL(k_cov_add, dim3(side_grid(n, kCovBlock, "cov_grid")), dim3(kCovBlock), 0, ctx().stream, d_recs, d_place, n, pct_id, c->len.as<uint64_t>(),
                      c->off.as<uint64_t>(), c->nacc, c->bits, sums, sums + c->nacc, sums + 3ull * c->nacc);
   MG_HIP(hipGetLastError());
   return MG_OK;
@@ -242,21 +162,12 @@ int mg_coverage_result(mg_coverage* c, uint64_t* alignments, uint64_t* aligned_b
   if (c->nwords) {
     ProfScope ps("cov_count");
     const uint64_t steps = (c->nwords + kCountWords - 1) / kCountWords;
-    const unsigned grid = grid_cap(grid_for(steps, kCovBlock / 64, (unsigned)ctx().num_cus * 8), "cov_grid");
-    hipLaunchKernelGGL(k_cov_count, dim3(grid), dim3(kCovBlock), 0, st, c->bits, c->nwords, c->off.as<uint64_t>(), c->nacc,
-                       sums + 2 * nacc);
+    hipLaunchKernelGGL(k_cov_count, dim3(side_grid(steps, kCovBlock / 64, "cov_grid")), dim3(kCovBlock), 0, st, c->bits, c->nwords,
+                       c->off.as<uint64_t>(), c->nacc, sums + 2 * nacc);
     MG_HIP(hipGetLastError());
   }
-  std::vector<uint64_t> h(3 * nacc + 1);
-  MG_HIP(hipMemcpyAsync(h.data(), sums, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  MG_HIP(hipStreamSynchronize(st));
-  for (uint64_t a = 0; a < nacc; ++a) {
-    alignments[a] = h[a];
-    aligned_bases[a] = h[nacc + a];
-    covered_bases[a] = h[2 * nacc + a];
-  }
-  *unplaced = h[3 * nacc];
-  return MG_OK;
+  uint64_t* const out[3] = {alignments, aligned_bases, covered_bases};
+  return fetch_sums(sums, nacc, out, 3, unplaced);
 }
 
 void mg_coverage_free(mg_coverage* c) { delete c; }

@@ -13,6 +13,8 @@
 //   clipped()      the length of [pos0, min(pos0 + span, L)); 0: not placed (span 0, or pos0 >= L)
 //   interval()     bits [b, e) of an accession's bitmap, e > b, in 32-bit words: first word, its mask, last word, its mask
 //   word_mask()    the mask of word w of that interval
+//   owner_of()     the accession that owns an offset, by binary search in the accessions' ascending offsets (the coverage, depth and
+//                  variants kernels); owner_from(): the same by walking on from an accession before it
 //
 // Written so that the SAME code compiles for the host (tests/host_coverage_check.cpp) and for gfx950.  Memory is reached through
 // an accessor (`m[i]` = byte i).
@@ -125,6 +127,22 @@ MGV_HD uint64_t clipped(uint32_t pos0, uint32_t span, uint64_t L) {
   if (span == 0 || (uint64_t)pos0 >= L) return 0;
   const uint64_t e = (uint64_t)pos0 + span;
   return (e < L ? e : L) - pos0;
+}
+
+// The accession of offset t (a bitmap word, a depth slot or window, a site): the last a with off[a] <= t < off[a + 1]; off has
+// n + 1 ascending entries, off[n] > t.
+template <class O> MGV_HD uint32_t owner_of(const O& off, uint32_t n, uint64_t t) {
+  uint32_t lo = 0, hi = n;  // the first index in [0, n] whose offset is above t
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (off[mid] > t) hi = mid; else lo = mid + 1;
+  }
+  return lo - 1;
+}
+// The same for a walk: a owned an offset at or below t; steps over the accessions that own nothing.  n when t = off[n].
+template <class O> MGV_HD uint32_t owner_from(const O& off, uint32_t n, uint32_t a, uint64_t t) {
+  while (a < n && off[a + 1] <= t) ++a;
+  return a;
 }
 
 MGV_HD void interval(uint64_t b, uint64_t e, uint64_t* w0, uint32_t* m0, uint64_t* w1, uint32_t* m1) {

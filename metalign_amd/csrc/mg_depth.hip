@@ -3,12 +3,12 @@
 // One int32 slot per reference base plus one per accession, at 64-bit offsets (mg_depth_core.h).  Five kernels:
 //
 //   k_depth_add         records + places -> +1 at the first slot of every counting, placed record's clipped interval, -1 at the slot
-//                       behind its last; the accession's alignments and the unplaced counted as k_cov_add does (hashed LDS bins).
+//                       behind its last; the accession's alignments and the unplaced counted in hashed LDS bins (mg_side_dev.h: AccBins).
 //                       The -1 lands inside the accession's own slots, so every accession's slots sum to zero.
 //   k_depth_tile_sums   the sum of every kTile slots (64-bit), one wavefront per tile; a tile in which no accession with an alignment
 //                       owns a slot is all zero and is not read (by this pass or by k_depth_hist).
-//   k_depth_scan_tiles  the exclusive scan of the tile sums in place, by ONE workgroup walking them 4096 at a time: nobody waits
-//                       for another workgroup.
+//   k_depth_scan_tiles  the exclusive scan of the tile sums in place, by ONE workgroup walking them 4096 at a time
+//                       (mg_side_dev.h: block_scan_excl).
 //   k_depth_hist        reads the slots a second time: tile carry + scan within the tile = depth[p], never written back.  Every
 //                       workgroup takes chunks of 64 tiles, four tiles behind one barrier, keeps a 4096-bin LDS histogram of the accession it is in and
 //                       flushes the non-empty bins into that accession's row (64-bit adds) when the accession changes and at the
@@ -21,6 +21,7 @@
 
 #include "mg_internal.h"
 #include "mg_depth_core.h"
+#include "mg_side_dev.h"
 
 using namespace mg;
 
@@ -45,16 +46,11 @@ struct mg_depth {
 
 namespace {
 
-constexpr unsigned kBlock = 256, kBins = 1024, kProbe = 8, kScanBlock = 1024, kScanPer = 4;
+constexpr unsigned kBlock = 256, kBins = 1024, kScanBlock = 1024, kScanPer = 4;
 constexpr unsigned kHistBatch = 4;
 constexpr uint64_t kHistChunk = 64;  // tiles (a multiple of kHistBatch)
 constexpr uint32_t kEmpty = 0xffffffffu;
 constexpr uint64_t kFlushTiles = 1ull << 21;  // an LDS bin counts at most 2^21 tiles of 2^10 slots
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
 
 struct OffView {
   const uint64_t* p;
@@ -69,13 +65,9 @@ __global__ __launch_bounds__(kBlock) void k_depth_add(const mg_aln_rec* __restri
                                                       uint64_t n, double pct_id, const uint64_t* __restrict__ off, uint32_t nacc,
                                                       int32_t* __restrict__ slots, unsigned long long* __restrict__ aln,
                                                       unsigned long long* __restrict__ unplaced) {
-  __shared__ uint32_t s_key[kBins];
-  __shared__ unsigned long long s_cnt[kBins];
-  __shared__ unsigned long long s_unplaced;
-  for (unsigned i = threadIdx.x; i < kBins; i += kBlock) { s_key[i] = kEmpty; s_cnt[i] = 0; }
-  if (threadIdx.x == 0) s_unplaced = 0;
-  __syncthreads();
-  const unsigned lane = threadIdx.x & 63u;
+  __shared__ AccBins<kBins, 1, kBlock> bins;
+  unsigned long long* const sums[1] = {aln};
+  bins.init();
   for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < n; base += (uint64_t)gridDim.x * kBlock) {
     const uint64_t i = base + threadIdx.x;
     uint32_t a = 0;
@@ -101,35 +93,10 @@ __global__ __launch_bounds__(kBlock) void k_depth_add(const mg_aln_rec* __restri
         }
       }
     }
-    const unsigned long long um = __ballot(unp);
-    if (um && lane == (unsigned)__builtin_ctzll(um)) atomicAdd(&s_unplaced, (unsigned long long)__builtin_popcountll(um));
-    const unsigned long long pm = __ballot(placed);
-    if (pm) {
-      const unsigned first = (unsigned)__builtin_ctzll(pm);
-      const uint32_t a_first = __shfl(a, (int)first, 64);
-      const bool uniform = __ballot(placed && a != a_first) == 0;
-      const unsigned long long add_cnt = uniform ? (unsigned long long)__builtin_popcountll(pm) : 1ull;
-      if (uniform ? lane == first : placed) {
-        const uint32_t h = (a * 2654435761u) >> 22;
-        bool done = false;
-        for (unsigned p = 0; p < kProbe && !done; ++p) {
-          const uint32_t s = (h + p) & (kBins - 1);
-          const uint32_t k = atomicCAS(&s_key[s], kEmpty, a);
-          if (k == kEmpty || k == a) {
-            atomicAdd(&s_cnt[s], add_cnt);
-            done = true;
-          }
-        }
-        if (!done) atomicAdd(&aln[a], add_cnt);
-      }
-    }
+    bins.count_one(unp);
+    bins.add(placed, a, nullptr, sums);
   }
-  __syncthreads();
-  for (unsigned s = threadIdx.x; s < kBins; s += kBlock) {
-    const uint32_t k = s_key[s];
-    if (k != kEmpty && s_cnt[s]) atomicAdd(&aln[k], s_cnt[s]);
-  }
-  if (threadIdx.x == 0 && s_unplaced) atomicAdd(unplaced, s_unplaced);
+  bins.flush(sums, unplaced);
 }
 
 __global__ __launch_bounds__(kBlock) void k_depth_tile_sums(const int32_t* __restrict__ slots, uint64_t nslots, uint64_t ntiles,
@@ -142,7 +109,7 @@ __global__ __launch_bounds__(kBlock) void k_depth_tile_sums(const int32_t* __res
   const uint64_t per = (ntiles + nwaves - 1) / nwaves;
   const uint64_t t_beg = wave * per, t_end = t_beg + per < ntiles ? t_beg + per : ntiles;
   if (t_beg >= t_end) return;
-  uint32_t a = mgd::owner_of(OffView{off}, nacc, t_beg * mgd::kTile);
+  uint32_t a = mgv::owner_of(OffView{off}, nacc, t_beg * mgd::kTile);
   for (uint64_t t = t_beg; t < t_end; ++t) {
     const uint64_t s0 = t * mgd::kTile, s_end = s0 + mgd::kTile < nslots ? s0 + mgd::kTile : nslots;
     while (off[a + 1] <= s0) ++a;
@@ -162,37 +129,7 @@ __global__ __launch_bounds__(kBlock) void k_depth_tile_sums(const int32_t* __res
 }
 
 __global__ __launch_bounds__(kScanBlock) void k_depth_scan_tiles(long long* __restrict__ t, uint64_t n) {
-  __shared__ long long s_w[kScanBlock / 64];
-  const unsigned lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  long long carry = 0;  // (the same in every thread)
-  for (uint64_t base = 0; base < n; base += (uint64_t)kScanPer * kScanBlock) {
-    const uint64_t i = base + (uint64_t)kScanPer * threadIdx.x;
-    long long v[kScanPer], tot = 0;
-    for (unsigned k = 0; k < kScanPer; ++k) {
-      v[k] = i + k < n ? t[i + k] : 0;
-      tot += v[k];
-    }
-    long long incl = tot;
-    for (int d = 1; d < 64; d <<= 1) {
-      const long long up = __shfl_up(incl, d, 64);
-      if (lane >= (unsigned)d) incl += up;
-    }
-    if (lane == 63) s_w[wv] = incl;
-    __syncthreads();
-    long long before = 0, all = 0;
-    for (unsigned w = 0; w < kScanBlock / 64; ++w) {
-      const long long x = s_w[w];
-      if (w < wv) before += x;
-      all += x;
-    }
-    long long ex = carry + before + incl - tot;
-    for (unsigned k = 0; k < kScanPer; ++k) {
-      if (i + k < n) t[i + k] = ex;
-      ex += v[k];
-    }
-    carry += all;
-    __syncthreads();  // (s_w is written again in the next step)
-  }
+  (void)block_scan_excl<long long, kScanBlock, kScanPer>(t, n, 0ll);
 }
 
 __global__ __launch_bounds__(kBlock) void k_depth_hist(const int32_t* __restrict__ slots, uint64_t nslots, uint64_t ntiles,
@@ -329,7 +266,7 @@ __global__ __launch_bounds__(kBlock) void k_depth_hist(const int32_t* __restrict
   const uint64_t nchunks = (ntiles + kHistChunk - 1) / kHistChunk;
   for (uint64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
     const uint64_t t1 = (chunk + 1) * kHistChunk < ntiles ? (chunk + 1) * kHistChunk : ntiles;
-    uint32_t a = mgd::owner_of(OffView{off}, nacc, chunk * kHistChunk * mgd::kTile);  // (the chunk's first slot is below nslots)
+    uint32_t a = mgv::owner_of(OffView{off}, nacc, chunk * kHistChunk * mgd::kTile);  // (the chunk's first slot is below nslots)
     for (uint64_t tb = chunk * kHistChunk; tb < t1; tb += kHistBatch) {
       bool hit[kHistBatch];
       uint32_t a_of[kHistBatch];
@@ -405,7 +342,7 @@ __global__ __launch_bounds__(kBlock) void k_depth_win_compact(const unsigned lon
     if (ws && out) {
       const uint64_t r = at + (uint64_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
       if (r < cap) {
-        const uint32_t a = mgd::owner_of(OffView{woff}, nacc, g);
+        const uint32_t a = mgv::owner_of(OffView{woff}, nacc, g);
         mg_depth_window w;
         w.index = g - woff[a];
         w.depth_sum = ws;
@@ -417,27 +354,7 @@ __global__ __launch_bounds__(kBlock) void k_depth_win_compact(const unsigned lon
   }
 }
 
-int own_alloc(void** p, uint64_t bytes, hipStream_t st) {
-  hipError_t e = hipMalloc(p, bytes);
-  if (e != hipSuccess) {  // (as mg_coverage_create: the allocator's cached blocks back to the runtime, once)
-    (void)hipGetLastError();
-    *p = nullptr;
-    (void)hipStreamSynchronize(st);
-    pool_release_all();
-    e = hipMalloc(p, bytes);
-  }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    *p = nullptr;
-    return fail(MG_ERR_NOMEM, "the depth slots (%llu bytes, four per reference base) do not fit: %s", (unsigned long long)bytes,
-                hipGetErrorString(e));
-  }
-  return MG_OK;
-}
-
-unsigned depth_grid(uint64_t items, unsigned per_block) {
-  return grid_cap(grid_for(items, per_block, (unsigned)ctx().num_cus * 8), "depth_grid");
-}
+unsigned depth_grid(uint64_t items, unsigned per_block) { return side_grid(items, per_block, "depth_grid"); }
 
 }  // namespace
 
@@ -469,7 +386,7 @@ int mg_depth_create(const uint64_t* lengths, uint32_t nacc, uint32_t window, mg_
   MG_TRY(d->wsum.alloc((d->nwin + 1) * sizeof(uint64_t)));
   MG_TRY(d->wcov.alloc((d->nwin + 1) * sizeof(uint32_t)));
   const uint64_t slot_bytes = d->ntiles * mgd::kTile * sizeof(int32_t) + 16;
-  MG_TRY(own_alloc((void**)&d->slots, slot_bytes, st));
+  MG_TRY(own_alloc((void**)&d->slots, slot_bytes, "the depth slots (%llu bytes, four per reference base) do not fit: %s", slot_bytes));
   MG_HIP(hipMemsetAsync(d->slots, 0, slot_bytes, st));
   MG_HIP(hipMemsetAsync(d->sums.p, 0, (nacc + 1ull) * sizeof(uint64_t), st));
   MG_HIP(hipMemsetAsync(d->wsum.p, 0, (d->nwin + 1) * sizeof(uint64_t), st));
@@ -501,19 +418,15 @@ int mg_depth_finish(mg_depth* d, uint64_t* alignments, uint64_t* unplaced, uint6
   hipStream_t st = ctx().stream;
   const uint64_t nacc = d->nacc;
   // the alignments first: only accessions that have one get a histogram row
-  std::vector<uint64_t> h(nacc + 1);
-  MG_HIP(hipMemcpyAsync(h.data(), d->sums.p, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  MG_HIP(hipStreamSynchronize(st));
+  MG_TRY(fetch_sums(d->sums.p, nacc, &alignments, 1, unplaced));
   std::vector<int32_t> h_map(nacc + 1, -1);
   d->row_acc.clear();
   for (uint64_t a = 0; a < nacc; ++a) {
-    alignments[a] = h[a];
-    if (h[a]) {
+    if (alignments[a]) {
       h_map[a] = (int32_t)d->row_acc.size();
       d->row_acc.push_back((uint32_t)a);
     }
   }
-  *unplaced = h[nacc];
   d->nrows = d->row_acc.size();
   MG_TRY(d->rows.alloc((d->nrows * mgd::kDepthBins + 1) * sizeof(uint64_t)));
   MG_HIP(hipMemsetAsync(d->rows.p, 0, (d->nrows * mgd::kDepthBins + 1) * sizeof(uint64_t), st));

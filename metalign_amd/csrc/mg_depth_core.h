@@ -11,6 +11,7 @@
 //   clamp()        min(depth, kDepthCap): the histogram's bin
 //   window_of()    the window of position p at width W; windows_of_length(): ceil(L / W)
 //   tiles_of()     the scan's tiles over n slots; tile_has_row(): must the passes read this tile at all
+// The accession of a slot or window is mgv::owner_of / mgv::owner_from (mg_coverage_core.h).
 //
 // Written so that the SAME code compiles for the host (tests/host_depth_check.cpp) and for gfx950.
 #pragma once
@@ -23,6 +24,8 @@ namespace mgd {
 constexpr uint32_t kDepthCap = 4095, kDepthBins = kDepthCap + 1;
 constexpr uint32_t kTile = 1024;  // slots per scan tile: 256 threads, one int4 each
 
+using mgv::owner_of;  // the accession of a slot or window (moved to mg_coverage_core.h for the coverage and variants kernels)
+
 MGV_HD uint64_t slots_of(uint64_t L) { return L + 1; }
 MGV_HD void diff_slots(uint64_t off, uint32_t pos0, uint64_t clen, uint64_t* plus, uint64_t* minus) {
   *plus = off + pos0;
@@ -33,16 +36,6 @@ MGV_HD uint32_t clamp(uint32_t depth) { return depth < kDepthCap ? depth : kDept
 MGV_HD uint64_t window_of(uint64_t p, uint32_t W) { return p / W; }
 MGV_HD uint64_t windows_of_length(uint64_t L, uint32_t W) { return W ? (L + W - 1) / W : 0; }
 MGV_HD uint64_t tiles_of(uint64_t nslots) { return (nslots + kTile - 1) / kTile; }
-
-// The accession of slot (or window) t: the last a with off[a] <= t < off[a + 1]; off has n + 1 ascending entries, off[n] > t.
-template <class O> MGV_HD uint32_t owner_of(const O& off, uint32_t n, uint64_t t) {
-  uint32_t lo = 0, hi = n;  // the first index in [0, n] whose offset is above t
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (off[mid] > t) hi = mid; else lo = mid + 1;
-  }
-  return lo - 1;
-}
 
 // Does an accession with a histogram row (rowmap >= 0) own a slot of the tile that ends at s_end?  a = the accession of the tile's
 // first slot.  Without one, every slot of the tile is zero and so is every depth in it: neither pass has to read it.

@@ -5,16 +5,17 @@
 //
 //   k_ident_add   records + edits -> the sums and bins of every counting, scored record, the unscored counted.  Persistent
 //                 grid-stride, one record per lane.  The load is the worst case for global atomics: most records of a sample hit a
-//                 handful of accessions and a few dozen bins near 1000, so plain adds pile onto a few cache lines.  As k_cov_add:
-//                 * (accession, bin) -> a hashed LDS table of 32-bit counts; accession -> a second one with the three 64-bit sums;
-//                 * lanes of a wavefront that share a key add once: the sums when the wavefront's scored records share one
-//                   accession, the bins by up to kRounds elected leaders (a ballot each), the rest one by one;
-//                 * a key that finds no slot within kProbe adds to memory directly;
-//                 * one global add per occupied slot when the workgroup ends.
+//                 handful of accessions and a few dozen bins near 1000, so plain adds pile onto a few cache lines.
+//                 * accession -> the three 64-bit sums in hashed LDS bins (mg_side_dev.h: AccBins);
+//                 * (accession, bin) -> a second hashed LDS table, of 32-bit counts, kept here (it has this one user): lanes of a
+//                   wavefront that share a key add once, by up to kRounds elected leaders (a ballot each), the rest one by one; a
+//                   key that finds no slot within kProbe (mg_side_dev.h: lds_probe) adds to memory directly; one global add per
+//                   occupied slot when the workgroup ends.
 //                 A launch takes at most 2^31 records, so no 32-bit count can wrap.
 //   k_ident_rows  the histogram rows a caller asks for, gathered for one download.
 #include "mg_internal.h"
 #include "mg_identity_core.h"
+#include "mg_side_dev.h"
 
 using namespace mg;
 
@@ -27,34 +28,30 @@ struct mg_identity {
 
 namespace {
 
-constexpr unsigned kBlock = 256, kHistSlots = 2048, kAccSlots = 512, kProbe = 8, kRounds = 4;
+constexpr unsigned kBlock = 256, kHistSlots = 2048, kAccSlots = 512, kRounds = 4;
 constexpr unsigned long long kEmptyKey = ~0ull;
-constexpr uint32_t kEmptyAcc = 0xffffffffu;
-constexpr uint64_t kLaunchMax = 1ull << 31;
 #ifdef MG_IDENT_NO_LDS  // (measurements only: every scored record adds to memory directly)
 constexpr bool kUseLds = false;
 #else
 constexpr bool kUseLds = true;
 #endif
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(kBlock) void k_ident_add(const mg_aln_rec* __restrict__ recs, const mg_aln_edit* __restrict__ edit, uint64_t n,
                                                       double pct_id, uint32_t nacc, unsigned long long* __restrict__ hist,
                                                       unsigned long long* __restrict__ aln, unsigned long long* __restrict__ cols,
                                                       unsigned long long* __restrict__ eds, unsigned long long* __restrict__ unscored) {
-  __shared__ unsigned long long s_hkey[kHistSlots];
-  __shared__ uint32_t s_hcnt[kHistSlots];
-  __shared__ uint32_t s_akey[kAccSlots];
-  __shared__ unsigned long long s_acnt[kAccSlots], s_acol[kAccSlots], s_aed[kAccSlots];
-  __shared__ unsigned long long s_unscored;
+  // (ONE object: on their own the bins, 8 bytes short of a multiple of 16, would cost the workgroup 8 bytes of padding)
+  __shared__ struct {
+    unsigned long long hkey[kHistSlots];
+    uint32_t hcnt[kHistSlots];
+    AccBins<kAccSlots, 3, kBlock> acc;
+  } s_lds;
+  unsigned long long* const s_hkey = s_lds.hkey;
+  uint32_t* const s_hcnt = s_lds.hcnt;
+  auto& bins = s_lds.acc;
+  unsigned long long* const sums[3] = {aln, cols, eds};
   for (unsigned i = threadIdx.x; i < kHistSlots; i += kBlock) { s_hkey[i] = kEmptyKey; s_hcnt[i] = 0; }
-  for (unsigned i = threadIdx.x; i < kAccSlots; i += kBlock) { s_akey[i] = kEmptyAcc; s_acnt[i] = 0; s_acol[i] = 0; s_aed[i] = 0; }
-  if (threadIdx.x == 0) s_unscored = 0;
-  __syncthreads();
+  bins.init();  // (and the barrier behind both tables)
   const unsigned lane = threadIdx.x & 63u;
   // (no workgroup barrier inside the loop: a wavefront works on its own 64 records)
   for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < n; base += (uint64_t)gridDim.x * kBlock) {
@@ -77,9 +74,7 @@ __global__ __launch_bounds__(kBlock) void k_ident_add(const mg_aln_rec* __restri
         }
       }
     }
-    // the unscored: one LDS add per wavefront
-    const unsigned long long um = __ballot(uns);
-    if (um && lane == (unsigned)__builtin_ctzll(um)) atomicAdd(&s_unscored, (unsigned long long)__builtin_popcountll(um));
+    bins.count_one(uns);
     const unsigned long long sm = __ballot(scored);
     if (!sm) continue;  // (uniform over the wavefront)
     if (!kUseLds) {
@@ -92,36 +87,8 @@ __global__ __launch_bounds__(kBlock) void k_ident_add(const mg_aln_rec* __restri
       continue;
     }
     // alignments, columns and edits per accession
-    {
-      const unsigned first = (unsigned)__builtin_ctzll(sm);
-      const uint32_t a_first = __shfl(a, (int)first, 64);
-      const bool uniform = __ballot(scored && a != a_first) == 0;
-      unsigned long long add_cnt = scored ? 1ull : 0ull, add_col = scored ? c : 0u, add_ed = scored ? e : 0u;
-      if (uniform) {
-        add_col = wave_sum(add_col);
-        add_ed = wave_sum(add_ed);
-        add_cnt = (unsigned long long)__builtin_popcountll(sm);
-      }
-      if (uniform ? lane == first : scored) {
-        const uint32_t h = (a * 2654435761u) >> 23;
-        bool done = false;
-        for (unsigned p = 0; p < kProbe && !done; ++p) {
-          const uint32_t s = (h + p) & (kAccSlots - 1);
-          const uint32_t k = atomicCAS(&s_akey[s], kEmptyAcc, a);
-          if (k == kEmptyAcc || k == a) {
-            atomicAdd(&s_acnt[s], add_cnt);
-            atomicAdd(&s_acol[s], add_col);
-            atomicAdd(&s_aed[s], add_ed);
-            done = true;
-          }
-        }
-        if (!done) {
-          atomicAdd(&aln[a], add_cnt);
-          atomicAdd(&cols[a], add_col);
-          atomicAdd(&eds[a], add_ed);
-        }
-      }
-    }
+    const unsigned long long col_ed[2] = {c, e};
+    bins.add(scored, a, col_ed, sums);
     // the bins: leaders add for the lanes that share their key, the lanes left after kRounds add for themselves
     {
       unsigned long long rest = sm, mine_key = key;
@@ -135,34 +102,17 @@ __global__ __launch_bounds__(kBlock) void k_ident_add(const mg_aln_rec* __restri
       }
       if ((rest >> lane) & 1ull) mine_cnt = 1;
       if (mine_cnt) {
-        const uint32_t h = (uint32_t)((mine_key * 0x9e3779b97f4a7c15ull) >> 53);
-        bool done = false;
-        for (unsigned p = 0; p < kProbe && !done; ++p) {
-          const uint32_t s = (h + p) & (kHistSlots - 1);
-          const unsigned long long k = atomicCAS(&s_hkey[s], kEmptyKey, mine_key);
-          if (k == kEmptyKey || k == mine_key) {
-            atomicAdd(&s_hcnt[s], mine_cnt);
-            done = true;
-          }
-        }
-        if (!done) atomicAdd(&hist[mine_key], (unsigned long long)mine_cnt);
+        const int s = lds_probe<kHistSlots, kProbe>(s_hkey, kEmptyKey, mine_key, (uint32_t)((mine_key * 0x9e3779b97f4a7c15ull) >> 53));
+        if (s >= 0) atomicAdd(&s_hcnt[s], mine_cnt);
+        else atomicAdd(&hist[mine_key], (unsigned long long)mine_cnt);
       }
     }
   }
-  __syncthreads();
+  bins.flush(sums, unscored);  // (behind the barrier that ends the loop for both tables)
   for (unsigned s = threadIdx.x; s < kHistSlots; s += kBlock) {
     const unsigned long long k = s_hkey[s];
     if (k != kEmptyKey && s_hcnt[s]) atomicAdd(&hist[k], (unsigned long long)s_hcnt[s]);
   }
-  for (unsigned s = threadIdx.x; s < kAccSlots; s += kBlock) {
-    const uint32_t k = s_akey[s];
-    if (k != kEmptyAcc && s_acnt[s]) {
-      atomicAdd(&aln[k], s_acnt[s]);
-      atomicAdd(&cols[k], s_acol[s]);
-      atomicAdd(&eds[k], s_aed[s]);
-    }
-  }
-  if (threadIdx.x == 0 && s_unscored) atomicAdd(unscored, s_unscored);
 }
 
 // out[r * 1001 + b] = hist[rows[r] * 1001 + b]
@@ -188,20 +138,8 @@ int mg_identity_create(uint32_t nacc, mg_identity** out) {
   h->nacc = nacc;
   const uint64_t hist_bytes = (uint64_t)nacc * mgi::kBins * sizeof(uint64_t), sums_bytes = (3ull * nacc + 1) * sizeof(uint64_t);
   MG_TRY(h->sums.alloc(sums_bytes));
-  hipError_t e = hipMalloc((void**)&h->hist, hist_bytes + 16);
-  if (e != hipSuccess) {  // (as mg_coverage_create: the allocator's cached blocks back to the runtime, once)
-    (void)hipGetLastError();
-    h->hist = nullptr;
-    (void)hipStreamSynchronize(st);
-    pool_release_all();
-    e = hipMalloc((void**)&h->hist, hist_bytes + 16);
-  }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    h->hist = nullptr;
-    return fail(MG_ERR_NOMEM, "the identity histograms (%llu bytes, 1001 bins of 8 bytes per accession) do not fit: %s",
-                (unsigned long long)(hist_bytes + sums_bytes), hipGetErrorString(e));
-  }
+  MG_TRY(own_alloc((void**)&h->hist, hist_bytes + 16,
+                   "the identity histograms (%llu bytes, 1001 bins of 8 bytes per accession) do not fit: %s", hist_bytes + sums_bytes));
   MG_HIP(hipMemsetAsync(h->hist, 0, hist_bytes + 16, st));
   MG_HIP(hipMemsetAsync(h->sums.p, 0, sums_bytes, st));
   MG_HIP(hipStreamSynchronize(st));
@@ -217,9 +155,8 @@ int mg_identity_add_dev(mg_identity* h, const mg_aln_rec* d_recs, const mg_aln_e
   unsigned long long* sums = h->sums.as<unsigned long long>();
   for (uint64_t at = 0; at < n; at += kLaunchMax) {
     const uint64_t m = n - at < kLaunchMax ? n - at : kLaunchMax;
-    const unsigned grid = grid_cap(grid_for(m, kBlock, (unsigned)ctx().num_cus * 8), "ident_grid");
-    hipLaunchKernelGGL(k_ident_add, dim3(grid), dim3(kBlock), 0, ctx().stream, d_recs + at, d_edit + at, m, pct_id, h->nacc, h->hist, sums,
-                       sums + h->nacc, sums + 2ull * h->nacc, sums + 3ull * h->nacc);
+    hipLaunchKernelGGL(k_ident_add, dim3(side_grid(m, kBlock, "ident_grid")), dim3(kBlock), 0, ctx().stream, d_recs + at, d_edit + at, m,
+                       pct_id, h->nacc, h->hist, sums, sums + h->nacc, sums + 2ull * h->nacc, sums + 3ull * h->nacc);
     MG_HIP(hipGetLastError());
   }
   return MG_OK;
@@ -228,18 +165,8 @@ int mg_identity_add_dev(mg_identity* h, const mg_aln_rec* d_recs, const mg_aln_e
 int mg_identity_result(mg_identity* h, uint64_t* alignments, uint64_t* columns, uint64_t* edits, uint64_t* unscored) {
   MG_REQUIRE_READY();
   if (!h || !unscored || (h->nacc && (!alignments || !columns || !edits))) return fail(MG_ERR_ARG, "null argument");
-  hipStream_t st = ctx().stream;
-  const uint64_t nacc = h->nacc;
-  std::vector<uint64_t> s(3 * nacc + 1);
-  MG_HIP(hipMemcpyAsync(s.data(), h->sums.p, s.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  MG_HIP(hipStreamSynchronize(st));
-  for (uint64_t a = 0; a < nacc; ++a) {
-    alignments[a] = s[a];
-    columns[a] = s[nacc + a];
-    edits[a] = s[2 * nacc + a];
-  }
-  *unscored = s[3 * nacc];
-  return MG_OK;
+  uint64_t* const out[3] = {alignments, columns, edits};
+  return fetch_sums(h->sums.p, h->nacc, out, 3, unscored);
 }
 
 int mg_identity_fetch_hist(mg_identity* h, const uint32_t* rows, uint32_t nrows, uint64_t* hist) {

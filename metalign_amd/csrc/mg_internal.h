@@ -125,6 +125,13 @@ inline uint32_t stage_a_cs_word() {
 void* pool_alloc(uint64_t bytes, uint64_t* got);
 void pool_free(void* p, uint64_t bytes);
 void pool_release_all();
+// An allocation of its own for an array of up to gigabytes (not worth a size class's slack in the pool): hipMalloc, once more after
+// the pool's cached blocks — a tokenised file's chunks and scratch — went back to the runtime.  On failure *p = nullptr and
+// MG_ERR_NOMEM with the caller's text: fmt takes `said` (%llu, the bytes to name) and the runtime's error string (%s).
+int own_alloc(void** p, uint64_t bytes, const char* fmt, uint64_t said);
+// The sums of a side output, u64[nvals * nacc + 1] on the device (value k of accession a at k * nacc + a, then the records that
+// belong to no accession), downloaded on the library stream: out[k][a] for the nvals arrays of out, and *miss.
+int fetch_sums(const void* d_sums, uint64_t nacc, uint64_t* const* out, unsigned nvals, uint64_t* miss);
 // Pinned host words for small read-backs (index < 64).  Who owns which (a new user takes free words and adds itself here):
 //   [0, 16)   the sort and scan services and the passes of mg_sketch, mg_refpipe, mg_contain and mg_ingest; each synchronises
 //             and reads its words before it returns
@@ -206,6 +213,12 @@ inline unsigned grid_cap(unsigned grid, const char* key) {
   const int64_t v = dbg(key);
   return v > 0 && (uint64_t)v < grid ? (unsigned)v : grid;
 }
+// The grid of a side output's persistent kernels: eight workgroups per CU at the most, fewer under the family's knob `key`.
+inline unsigned side_grid(uint64_t items, unsigned per_block, const char* key) {
+  return grid_cap(grid_for(items, per_block, (unsigned)ctx().num_cus * 8), key);
+}
+// The most records one launch of a side output's kernels takes (their 32-bit counts cannot wrap); a multiple of every tile.
+constexpr uint64_t kLaunchMax = 1ull << 31;
 
 // mg_multimap.hip: the iterated multimapped-read reassignment over a multimapped CSR in device memory (mg_profile_mm_iterate_dev).
 int mm_iterate_dev(const uint64_t* mm_offsets, const uint32_t* mm_tax, const uint64_t* mm_hitlen, uint64_t nreads, uint64_t nent,

@@ -5,7 +5,7 @@
 // sum over the stream.  Three launches, none of which waits on another workgroup:
 //
 //   k_mask_count   NEW bits per tile of mgs::kTile records: a ballot and a popcount per wavefront and 64 records.
-//   k_mask_scan    the exclusive scan of the tile counts by one workgroup (a loop when there are more tiles than threads), in 64 bits,
+//   k_mask_scan    the exclusive scan of the tile counts by one workgroup (mg_side_dev.h: block_scan_excl), in 64 bits,
 //                  on top of the carry of the launches before it (a call above 2^31 records is cut into several).
 //   k_mask_apply   a workgroup per tile, a wavefront per quarter of it, the records held in registers: the ordinal is the tile's base,
 //                  the wavefronts before it, the 64-record steps before it and mbcnt over the step's ballot; then word 0 of the read
@@ -16,13 +16,13 @@
 // Per record: 16 B read twice, 16 B written, and 8 to 16 B of verdict words (mostly shared between the lanes of a wavefront).
 #include "mg_internal.h"
 #include "mg_sidemask_core.h"
+#include "mg_side_dev.h"
 
 using namespace mg;
 
 namespace {
 
 constexpr unsigned kBlock = 256, kWaves = kBlock / 64, kPerWave = mgs::kTile / kWaves, kSteps = kPerWave / 64, kScanBlock = 256;
-constexpr uint64_t kLaunchMax = 1ull << 31;  // (a multiple of the tile)
 static_assert(kSteps * 64 * kWaves == mgs::kTile && kLaunchMax % mgs::kTile == 0, "tile shape");
 
 struct Word0 {  // word 0 of read r
@@ -54,29 +54,8 @@ __global__ __launch_bounds__(kBlock) void k_mask_count(const mg_aln_rec* __restr
 // t[i] = *carry + the counts before tile i; *carry += all of them
 __global__ __launch_bounds__(kScanBlock) void k_mask_scan(unsigned long long* __restrict__ t, uint64_t ntiles,
                                                           unsigned long long* __restrict__ carry_io) {
-  __shared__ unsigned long long s_w[kScanBlock / 64];
-  const unsigned lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  unsigned long long carry = *carry_io;  // (the same in every thread; written back behind the loop's barriers)
-  for (uint64_t base = 0; base < ntiles; base += kScanBlock) {
-    const uint64_t i = base + threadIdx.x;
-    const unsigned long long v = i < ntiles ? t[i] : 0ull;
-    unsigned long long incl = v;
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned long long up = (unsigned long long)__shfl_up((long long)incl, d, 64);
-      if (lane >= (unsigned)d) incl += up;
-    }
-    if (lane == 63) s_w[wv] = incl;
-    __syncthreads();
-    unsigned long long before = 0, all = 0;
-    for (unsigned w = 0; w < kScanBlock / 64; ++w) {
-      const unsigned long long x = s_w[w];
-      if (w < wv) before += x;
-      all += x;
-    }
-    if (i < ntiles) t[i] = carry + before + incl - v;
-    carry += all;
-    __syncthreads();  // (s_w is written again in the next step)
-  }
+  // (every thread reads the carry; it is written back behind the scan's barriers)
+  const unsigned long long carry = block_scan_excl<unsigned long long, kScanBlock, 1>(t, ntiles, *carry_io);
   if (threadIdx.x == 0) *carry_io = carry;
 }
 

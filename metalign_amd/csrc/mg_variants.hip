@@ -5,23 +5,24 @@
 // them in two forms:
 //
 //   k_var_add           records + entries + pool -> one add per code below 4 of every counting, piled record, clipped at the
-//                       accession's length; the accession's alignments and the unpiled counted as k_cov_add does (hashed LDS bins,
-//                       flushed with one global add per bin and workgroup).  Persistent grid-stride.  The work per record is its span
-//                       — 150 for a short read, 2^21 - 1 at most — so, as k_cov_add, every wavefront flattens the base lists of its 64
-//                       records (an inclusive scan of the clipped spans) and its lanes stride the total: neighbouring lanes take
+//                       accession's length; the accession's alignments and the unpiled counted in hashed LDS bins (mg_side_dev.h:
+//                       AccBins).  Persistent grid-stride.  The work per record is its span — 150 for a short read, 2^21 - 1 at
+//                       most — so every wavefront flattens the base lists of its 64 records (mg_side_dev.h: WaveList, an inclusive
+//                       scan of the clipped spans) and its lanes stride the total: neighbouring lanes take
 //                       neighbouring bases of one record, that is neighbouring 16-byte cells and the same or neighbouring pool bytes,
 //                       and no lane walks a long record alone.  The adds return nothing.
 //   k_var_sites<false>  the sums: every wavefront takes blocks of kStep sites, finds the accession of its first site in the offsets
-//                       (as k_cov_count) and judges the sites of accessions that have an alignment: callable, polymorphic, pairs and
+//                       (mgv::owner_of) and judges the sites of accessions that have an alignment: callable, polymorphic, pairs and
 //                       discordant summed over the wavefront, one 64-bit add per block, accession and sum; the block's polymorphic
 //                       sites counted.
-//   k_var_scan          the exclusive scan of the blocks' counts by ONE workgroup (as k_mask_scan): nobody waits for another
-//                       workgroup.
+//   k_var_scan          the exclusive scan of the blocks' counts by ONE workgroup (mg_side_dev.h: block_scan_excl): nobody waits
+//                       for another workgroup.
 //   k_var_sites<true>   the sites: the same walk a second time; a polymorphic site goes to the block's base + the polymorphic sites
 //                       before it in the block (a ballot and mbcnt per 64 sites), so the sites come out ordered by (accession row,
 //                       pos0) whatever the grid.
 #include "mg_internal.h"
 #include "mg_variants_core.h"
+#include "mg_side_dev.h"
 
 using namespace mg;
 
@@ -40,15 +41,8 @@ struct mg_variants {
 
 namespace {
 
-constexpr unsigned kBlock = 256, kBins = 1024, kProbe = 8, kScanBlock = 256;
-constexpr uint32_t kEmpty = 0xffffffffu;
+constexpr unsigned kBlock = 256, kBins = 1024, kScanBlock = 256;
 constexpr uint64_t kStep = 1024;  // sites per wavefront and step of k_var_sites
-constexpr uint64_t kLaunchMax = 1ull << 31;
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
 
 struct PoolView {
   const uint8_t* p;
@@ -60,12 +54,9 @@ __global__ __launch_bounds__(kBlock) void k_var_add(const mg_aln_rec* __restrict
                                                     const uint64_t* __restrict__ len, const uint64_t* __restrict__ off, uint32_t nacc,
                                                     uint32_t* __restrict__ cnt, unsigned long long* __restrict__ aln,
                                                     unsigned long long* __restrict__ unpiled) {
-  __shared__ uint32_t s_key[kBins];
-  __shared__ unsigned long long s_cnt[kBins];
-  __shared__ unsigned long long s_unpiled;
-  for (unsigned i = threadIdx.x; i < kBins; i += kBlock) { s_key[i] = kEmpty; s_cnt[i] = 0; }
-  if (threadIdx.x == 0) s_unpiled = 0;
-  __syncthreads();
+  __shared__ AccBins<kBins, 1, kBlock> bins;
+  unsigned long long* const sums[1] = {aln};
+  bins.init();
   const unsigned lane = threadIdx.x & 63u;
   const PoolView pv{pool};
   // (no workgroup barrier inside the loop: a wavefront works on its own 64 records)
@@ -90,71 +81,24 @@ __global__ __launch_bounds__(kBlock) void k_var_add(const mg_aln_rec* __restrict
         }
       }
     }
-    // the unpiled: one LDS add per wavefront
-    const unsigned long long um = __ballot(unp);
-    if (um && lane == (unsigned)__builtin_ctzll(um)) atomicAdd(&s_unpiled, (unsigned long long)__builtin_popcountll(um));
-    const unsigned long long pm = __ballot(clen != 0);
-    if (!pm) continue;  // (uniform over the wavefront)
-    // alignments
-    {
-      const unsigned first = (unsigned)__builtin_ctzll(pm);
-      const uint32_t a_first = __shfl(a, (int)first, 64);
-      const bool uniform = __ballot(clen != 0 && a != a_first) == 0;
-      const unsigned long long add_cnt = uniform ? (unsigned long long)__builtin_popcountll(pm) : 1ull;
-      if (uniform ? lane == first : clen != 0) {
-        const uint32_t h = (a * 2654435761u) >> 22;
-        bool done = false;
-        for (unsigned p = 0; p < kProbe && !done; ++p) {
-          const uint32_t s = (h + p) & (kBins - 1);
-          const uint32_t k = atomicCAS(&s_key[s], kEmpty, a);
-          if (k == kEmpty || k == a) {
-            atomicAdd(&s_cnt[s], add_cnt);
-            done = true;
-          }
-        }
-        if (!done) atomicAdd(&aln[a], add_cnt);
-      }
-    }
+    bins.count_one(unp);                    // the unpiled
+    bins.add(clen != 0, a, nullptr, sums);  // alignments
+    // (a wavefront without a piled record skips the list's six-step scan: this kernel always had that exit and keeps it, k_cov_add
+    // never had one — each stays as it was measured)
+    if (!__ballot(clen != 0)) continue;  // (uniform over the wavefront)
     // the bases: the wavefront's flattened list, its lanes striding it (64 * kMaxPileSpan < 2^32)
-    uint32_t incl = clen;
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t up = __shfl_up(incl, d, 64);
-      if (lane >= (unsigned)d) incl += up;
-    }
-    const uint32_t total = __shfl(incl, 63, 64);
-    for (uint32_t j0 = 0; j0 < total; j0 += 64) {  // (uniform: every lane takes part in the shuffles)
+    const WaveList<uint32_t> codes(clen);
+    for (uint32_t j0 = 0; j0 < codes.total; j0 += 64) {  // (uniform: every lane takes part in the shuffles)
       const uint32_t j = j0 + lane;
-      int lo = 0, hi = 63;  // the first record whose inclusive sum is above j
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        const uint32_t v = __shfl(incl, mid, 64);  // (each lane asks for its own mid)
-        if (v > j) hi = mid; else lo = mid + 1;
-      }
-      const uint32_t r_incl = __shfl(incl, lo, 64), r_len = __shfl(clen, lo, 64);
-      const unsigned long long r_site = __shfl(site0, lo, 64), r_poff = __shfl(poff, lo, 64);
-      if (j < total) {
-        const uint32_t k = j - (r_incl - r_len);  // (< r_len: inside the entry's codes and the accession's sites)
-        const uint32_t code = mgvar::code_at(pv, r_poff, k);
-        if (code < 4) (void)__hip_atomic_fetch_add(cnt + ((r_site + k) * 4 + code), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const auto it = codes.find(j);
+      const unsigned long long r_site = __shfl(site0, it.lane, 64), r_poff = __shfl(poff, it.lane, 64);
+      if (j < codes.total) {  // (it.at < it.len: inside the entry's codes and the accession's sites)
+        const uint32_t code = mgvar::code_at(pv, r_poff, it.at);
+        if (code < 4) (void)__hip_atomic_fetch_add(cnt + ((r_site + it.at) * 4 + code), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
   }
-  __syncthreads();
-  for (unsigned s = threadIdx.x; s < kBins; s += kBlock) {
-    const uint32_t k = s_key[s];
-    if (k != kEmpty && s_cnt[s]) atomicAdd(&aln[k], s_cnt[s]);
-  }
-  if (threadIdx.x == 0 && s_unpiled) atomicAdd(unpiled, s_unpiled);
-}
-
-// The accession of site t: the last a with off[a] <= t < off[a + 1] (off[nacc] = nsites > t).
-__device__ __forceinline__ uint32_t acc_of_site(const uint64_t* __restrict__ off, uint32_t nacc, uint64_t t) {
-  uint32_t lo = 0, hi = nacc;  // the first index in [0, nacc] whose offset is above t
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (off[mid] > t) hi = mid; else lo = mid + 1;
-  }
-  return lo - 1;
+  bins.flush(sums, unpiled);
 }
 
 // Both passes over the sites: kEmit = false sums and counts, kEmit = true writes the polymorphic sites.
@@ -172,7 +116,7 @@ __global__ __launch_bounds__(kBlock) void k_var_sites(const uint32_t* __restrict
   const uint4* cnt4 = reinterpret_cast<const uint4*>(cnt);
   for (uint64_t b = wave; b < nblocks; b += nwaves) {
     const uint64_t t0 = b * kStep, t1 = t0 + kStep < nsites ? t0 + kStep : nsites;
-    uint32_t a = acc_of_site(off, nacc, t0);
+    uint32_t a = mgv::owner_of(off, nacc, t0);  // (off[nacc] = nsites > t0)
     uint64_t s = t0;
     unsigned long long at = kEmit ? blk[b] : 0ull;  // kEmit: where the block's next polymorphic site goes; else: their count
     while (s < t1) {
@@ -224,45 +168,20 @@ __global__ __launch_bounds__(kBlock) void k_var_sites(const uint32_t* __restrict
         }
       }
       s = e;
-      ++a;
-      while (a < nacc && off[a + 1] <= s) ++a;  // (accessions without sites)
+      a = mgv::owner_from(off, nacc, a, s);  // (over the accessions without sites)
     }
     if (!kEmit && lane == 0) blk[b] = at;
   }
 }
 
-// t[i] = the counts before block i; *total = all of them (as k_mask_scan)
+// t[i] = the counts before block i; *total = all of them
 __global__ __launch_bounds__(kScanBlock) void k_var_scan(unsigned long long* __restrict__ t, uint64_t nblocks,
                                                          unsigned long long* __restrict__ total) {
-  __shared__ unsigned long long s_w[kScanBlock / 64];
-  const unsigned lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  unsigned long long carry = 0;  // (the same in every thread)
-  for (uint64_t base = 0; base < nblocks; base += kScanBlock) {
-    const uint64_t i = base + threadIdx.x;
-    const unsigned long long v = i < nblocks ? t[i] : 0ull;
-    unsigned long long incl = v;
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned long long up = (unsigned long long)__shfl_up((long long)incl, d, 64);
-      if (lane >= (unsigned)d) incl += up;
-    }
-    if (lane == 63) s_w[wv] = incl;
-    __syncthreads();
-    unsigned long long before = 0, all = 0;
-    for (unsigned w = 0; w < kScanBlock / 64; ++w) {
-      const unsigned long long x = s_w[w];
-      if (w < wv) before += x;
-      all += x;
-    }
-    if (i < nblocks) t[i] = carry + before + incl - v;
-    carry += all;
-    __syncthreads();  // (s_w is written again in the next step)
-  }
-  if (threadIdx.x == 0) *total = carry;
+  const unsigned long long all = block_scan_excl<unsigned long long, kScanBlock, 1>(t, nblocks, 0ull);
+  if (threadIdx.x == 0) *total = all;
 }
 
-unsigned var_grid(uint64_t items, unsigned per_block) {
-  return grid_cap(grid_for(items, per_block, (unsigned)ctx().num_cus * 8), "var_grid");
-}
+unsigned var_grid(uint64_t items, unsigned per_block) { return side_grid(items, per_block, "var_grid"); }
 
 }  // namespace
 
@@ -287,20 +206,7 @@ int mg_variants_create(const uint64_t* lengths, uint32_t nacc, mg_variants** out
   MG_TRY(h->sums.alloc((5ull * nacc + 1) * sizeof(uint64_t)));
   MG_TRY(h->blk.alloc((h->nblocks + 1) * sizeof(uint64_t)));
   const uint64_t bytes = h->nsites * 16 + 16;
-  hipError_t e = hipMalloc((void**)&h->cnt, bytes);
-  if (e != hipSuccess) {  // (as mg_coverage_create: the allocator's cached blocks back to the runtime, once)
-    (void)hipGetLastError();
-    h->cnt = nullptr;
-    (void)hipStreamSynchronize(st);
-    pool_release_all();
-    e = hipMalloc((void**)&h->cnt, bytes);
-  }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    h->cnt = nullptr;
-    return fail(MG_ERR_NOMEM, "the allele counts (%llu bytes, sixteen per reference base) do not fit: %s", (unsigned long long)bytes,
-                hipGetErrorString(e));
-  }
+  MG_TRY(own_alloc((void**)&h->cnt, bytes, "the allele counts (%llu bytes, sixteen per reference base) do not fit: %s", bytes));
   MG_HIP(hipMemsetAsync(h->cnt, 0, bytes, st));
   MG_HIP(hipMemsetAsync(h->sums.p, 0, (5ull * nacc + 1) * sizeof(uint64_t), st));
   MG_HIP(hipMemcpyAsync(h->off.p, h_off.data(), (nacc + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
@@ -368,17 +274,8 @@ int mg_variants_finish(mg_variants* h, uint32_t min_depth, uint32_t min_count, u
       MG_HIP(hipGetLastError());
     }
   }
-  std::vector<uint64_t> s(5 * nacc + 1);
-  MG_HIP(hipMemcpyAsync(s.data(), sums, s.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  MG_HIP(hipStreamSynchronize(st));
-  for (uint64_t a = 0; a < nacc; ++a) {
-    alignments[a] = s[a];
-    callable_sites[a] = s[nacc + a];
-    polymorphic_sites[a] = s[2 * nacc + a];
-    pairs[a] = s[3 * nacc + a];
-    discordant[a] = s[4 * nacc + a];
-  }
-  *unpiled = s[5 * nacc];
+  uint64_t* const out[5] = {alignments, callable_sites, polymorphic_sites, pairs, discordant};
+  MG_TRY(fetch_sums(sums, nacc, out, 5, unpiled));
   *nsites = h->npoly;
   h->finished = true;
   return MG_OK;

@@ -68,7 +68,7 @@ int main(int argc, char** argv) {
   for (uint64_t t = 0; t < mgd::tiles_of(off[nacc]); ++t) {
     uint64_t s = t * mgd::kTile;
     const uint64_t s_end = s + mgd::kTile < off[nacc] ? s + mgd::kTile : off[nacc];
-    uint32_t a = mgd::owner_of(off, nacc, s);
+    uint32_t a = mgv::owner_of(off, nacc, s);
     if (!(off[a] <= s && s < off[a + 1])) { printf("owner_of is wrong at slot %llu\n", (unsigned long long)s); return 2; }
     if (!mgd::tile_has_row(off, rowmap, nacc, a, s_end)) {  // (the device reads no slot of such a tile)
       for (; s < s_end; ++s)
@@ -76,7 +76,7 @@ int main(int argc, char** argv) {
       continue;
     }
     for (; s < s_end; ++s) {
-      while (off[a + 1] <= s) ++a;
+      a = mgv::owner_from(off, nacc, a, s);
       carry += slots[s];
       if (carry < 0) { printf("negative depth\n"); return 2; }
       if (!mgd::is_base(s, off[a], len[a])) {

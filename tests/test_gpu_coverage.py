@@ -11,6 +11,7 @@ import pytest
 import bamgen
 import collate_cases
 import coverage_cases as cc
+import side_bins_cases as sb
 import stage_c_checks as sc
 from metalign_amd import _hip
 from metalign_amd import collate
@@ -81,9 +82,9 @@ def _guarded_result(hip, dev):
     return [a[:n] for a in out], int(unplaced.value)
 
 
-def _check(hip, calls, names=NAMES, pct=PCT):
+def _check(hip, calls, names=NAMES, pct=PCT, lengths=LENGTHS):
     """The device over `calls` (lists of pairs, one add_dev each) against the definition over all of them."""
-    lengths = {a: LENGTHS[a] for a in names}
+    lengths = {a: lengths[a] for a in names}
     dev = hip.coverage([lengths[a] for a in names])
     try:
         for pairs in calls:
@@ -132,6 +133,38 @@ def test_one_long_alignment_among_short_ones(hip, grid):
     finally:
         _hip.debug_set("cov_grid", 0)
     assert want.per["huge"][0] == 4001 and want.per["huge"][2] > (1 << 20)
+
+
+@pytest.mark.parametrize("grid", [1, 3])
+def test_more_accessions_than_lds_bins_add_to_memory_directly(hip, grid):
+    """3000 accessions through the 1024 bins of one workgroup (and of three): at least 1976 of them find no slot, whatever the hash
+    does, and add their alignments and bases to memory directly — in the launch that counts the unplaced."""
+    assert sb.overflows("mg_coverage.hip", "kCovBins") >= 1000
+    rng = np.random.default_rng(12)
+    pairs = [(_rec(row, 10, 10), (sb.LENGTH, 9) if i % 97 == 5 else (int(rng.integers(0, 60)), int(rng.integers(1, 40))))
+             for i, row in enumerate(sb.rows())]
+    _hip.debug_set("cov_grid", grid)
+    try:
+        assert _hip.debug_get("cov_grid") == grid
+        want = _check(hip, [pairs], names=sb.NAMES, lengths=dict.fromkeys(sb.NAMES, sb.LENGTH))
+    finally:
+        _hip.debug_set("cov_grid", 0)
+    assert len(want.per) > sb.NACC - 70 and want.unplaced >= 2 * len(sb.BEYOND) + 50  # (some accessions' only record is unplaced)
+
+
+def test_a_wavefront_without_words_between_two_busy_ones_and_lane_63_alone(hip):
+    """The four wavefronts of one workgroup: 64 placed records, 64 without a word (unplaced, or not counting), 64 placed ones, and
+    one placed record behind 63 without a word."""
+    rng = np.random.default_rng(13)
+    big = 3
+
+    def busy(n):
+        return [(_rec(big, 10, 10), (int(rng.integers(0, 90000)), int(rng.choice([1, 31, 33, 150, 5000])))) for _ in range(n)]
+    idle = [(_rec(big, 10, 10), (LENGTHS["big"], 5)) if i % 2 else (_rec(big, 2, 10), (100, 50)) for i in range(64)]
+    pairs = busy(64) + idle + busy(64) + idle[:63] + [(_rec(big, 10, 10), (70000, 2000))]
+    want = _check(hip, [pairs], names=NAMES[:4])
+    assert want.per["big"][0] == 129 and want.unplaced == 32 + 31
+    assert _check(hip, [pairs[192:]], names=NAMES[:4]).per == {"big": [1, 2000, 2000]}
 
 
 def test_two_calls_sum_to_one(hip):

@@ -10,6 +10,7 @@ import pytest
 import bamgen
 import collate_cases
 import coverage_cases as cc
+import side_bins_cases as sb
 import stage_c_checks as sc
 from metalign_amd import _hip
 from metalign_amd import coverage as cv
@@ -167,6 +168,36 @@ def test_one_long_alignment_among_short_ones_few_workgroups(hip, grid):
         _hip.debug_set("depth_grid", 0)
     assert want.per["huge"][0] == 4001 and sum(k for c, k in want.per["huge"][1].items() if c) > (1 << 20)
     assert len(want.windows["huge"]) > 1048
+
+
+@pytest.mark.parametrize("grid", [1, 3])
+def test_more_accessions_than_lds_bins_add_to_memory_directly(hip, grid):
+    """3000 accessions through the 1024 bins of one workgroup (and of three): at least 1976 of them find no slot, whatever the hash
+    does, and add their alignments to memory directly — in the launch that counts the unplaced."""
+    assert sb.overflows("mg_depth.hip", "kBins") >= 1000
+    rng = np.random.default_rng(12)
+    pairs = [(_rec(row, 10, 10), (sb.LENGTH, 9) if i % 97 == 5 else (int(rng.integers(0, 60)), int(rng.integers(1, 40))))
+             for i, row in enumerate(sb.rows())]
+    _hip.debug_set("depth_grid", grid)
+    try:
+        assert _hip.debug_get("depth_grid") == grid
+        want = _check(hip, [pairs], names=sb.NAMES, windows=(16,), lengths=dict.fromkeys(sb.NAMES, sb.LENGTH))
+    finally:
+        _hip.debug_set("depth_grid", 0)
+    assert len(want.per) > sb.NACC - 70 and want.unplaced >= 2 * len(sb.BEYOND) + 50  # (some accessions' only record is unplaced)
+
+
+def test_intervals_on_both_sides_of_a_step_of_the_tile_scan(hip):
+    """One accession of 4 300 000 bases: 4200 tiles for the one workgroup that scans 4096 tile sums in a step, so the depth behind
+    slot 4096 * 1024 comes out right only with the carry across the step."""
+    L, edge = 4300000, 4096 * TILE
+    assert (L + 1 + TILE - 1) // TILE > 4096
+    pairs = [(_rec(0, 10, 10), place) for place in
+             [(100, 50), (edge - 3000, 2000), (edge - 20, 40), (edge - 1, 1), (edge, 5), (edge, 1), (edge + 1, 2000),
+              (edge - 200000, 300000), (L - 10, 100), (L - 1, 1), (0, 1)] + [(edge - 7, 14)] * 5]
+    want = _check(hip, [pairs], names=["long"], windows=(1000,), lengths={"long": L})
+    assert want.per["long"][0] == 16 and max(want.per["long"][1]) == 9 and want.unplaced == 0  # (nine deep at slot `edge`)
+    assert {j for j, _, _ in want.windows["long"]} >= {0, edge // 1000 - 1, edge // 1000, edge // 1000 + 1, (L - 1) // 1000}
 
 
 def test_identical_intervals_contend_and_cross_the_clamp(hip):

@@ -10,6 +10,7 @@ import pytest
 import bamgen
 import collate_cases
 import identity_cases as ic
+import side_bins_cases as sb
 import stage_c_checks as sc
 from metalign_amd import _hip
 from metalign_amd import bam
@@ -139,6 +140,23 @@ def test_more_keys_than_lds_slots_add_to_memory_directly(hip, grid):
     finally:
         _hip.debug_set("ident_grid", 0)
     assert len(want.per) == 40 and all(len(st[3]) == 1001 for st in want.per.values())
+
+
+@pytest.mark.parametrize("grid", [1, 3])
+def test_more_accessions_than_lds_bins_add_to_memory_directly(hip, grid):
+    """3000 accessions through the 512 per-accession bins of one workgroup (and of three): at least 2488 of them find no slot,
+    whatever the hash does, and add their three sums to memory directly — in the launch that counts the unscored."""
+    assert sb.overflows("mg_identity.hip", "kAccSlots") >= 1000
+    rng = np.random.default_rng(12)
+    pairs = [(_rec(row, 10, 10), (NONE, 100) if i % 97 == 5 else (int(rng.integers(0, 30)), int(rng.integers(30, 300))))
+             for i, row in enumerate(sb.rows())]
+    _hip.debug_set("ident_grid", grid)
+    try:
+        assert _hip.debug_get("ident_grid") == grid
+        want = _check(hip, [pairs], names=sb.NAMES)
+    finally:
+        _hip.debug_set("ident_grid", 0)
+    assert len(want.per) > sb.NACC - 70 and want.unscored >= 2 * len(sb.BEYOND) + 50  # (some accessions' only record is unscored)
 
 
 @pytest.mark.parametrize("grid", [1, 3])

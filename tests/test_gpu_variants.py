@@ -10,6 +10,7 @@ import pytest
 import bamgen
 import collate_cases
 import identity_cases as ic
+import side_bins_cases as sb
 import stage_c_checks as sc
 import variants_cases as vc
 from metalign_amd import _hip
@@ -150,6 +151,50 @@ def test_the_grid_cut_to_a_few_workgroups(hip, grid):
     finally:
         _hip.debug_set("var_grid", 0)
     assert cut == _check(hip, [_generated(4097, seed=8)]) and len(cut.sites) > 20
+
+
+@pytest.mark.parametrize("grid", [1, 3])
+def test_more_accessions_than_lds_bins_add_to_memory_directly(hip, grid):
+    """3000 accessions through the 1024 bins of one workgroup (and of three): at least 1976 of them find no slot, whatever the hash
+    does, and add their alignments to memory directly — in the launch that counts the unpiled."""
+    assert sb.overflows("mg_variants.hip", "kBins") >= 1000
+    rng = np.random.default_rng(12)
+    items = [(_rec(row), sb.LENGTH, [1, 2]) if i % 97 == 5 else
+             (_rec(row), int(rng.integers(0, 60)), [int(c) for c in rng.integers(0, 4, int(rng.integers(1, 9)))])
+             for i, row in enumerate(sb.rows())]
+    _hip.debug_set("var_grid", grid)
+    try:
+        assert _hip.debug_get("var_grid") == grid
+        want = _check(hip, [items], names=sb.NAMES, lengths=[sb.LENGTH] * sb.NACC)
+    finally:
+        _hip.debug_set("var_grid", 0)
+    assert len(want.per) > sb.NACC - 70 and want.unpiled >= 2 * len(sb.BEYOND) + 50  # (some accessions' only record is unpiled)
+
+
+def test_polymorphic_sites_on_both_sides_of_a_step_of_the_block_scan(hip):
+    """One accession of 300 000 bases: 293 blocks of 1024 sites for the one workgroup that scans 256 block counts in a step, so the
+    sites behind site 256 * 1024 land in their places only with the carry across the step."""
+    L, edge = 300000, 256 * 1024
+    poly = [5, 1000, 1023, 1024, edge - 1, edge, edge + 7, edge + 1023, edge + 1024, L - 1000, L - 1]
+    items = [(_rec(0), p, [k % 2]) for p in poly for k in range(6)]
+    items += [(_rec(0), p, [3] * 40) for p in (100, 2000, edge - 200, edge + 5000, L - 300) for _ in range(6)]  # (callable, one allele)
+    want = _check(hip, [items], names=["long"], lengths=[L])
+    assert [p for _, p, _ in want.sites] == poly and want.per["long"][2] == len(poly) and want.per["long"][1] > len(poly) + 150
+
+
+def test_a_wavefront_without_bases_between_two_busy_ones_and_lane_63_alone(hip):
+    """The four wavefronts of one workgroup: 64 piled records, 64 without a base (unpiled, or not counting), 64 piled ones, and one
+    piled record behind 63 without a base."""
+    rng = np.random.default_rng(13)
+
+    def busy(n):
+        return [(_rec(4), int(rng.integers(0, 4000)), [int(c) for c in rng.integers(0, 4, int(rng.choice([1, 2, 3, 40, 151])))])
+                for _ in range(n)]
+    idle = [(_rec(4), LENGTHS[4], [1, 2]) if i % 2 else (_rec(4, matched=2), 100, [1, 2, 3]) for i in range(64)]
+    items = busy(64) + idle + busy(64) + idle[:63] + [(_rec(4), 4000, [2] * 151)]
+    want = _check(hip, [items])
+    assert want.per["l4097"][0] == 129 and want.unpiled == 32 + 31
+    assert _check(hip, [items[192:]]).per == {"l4097": [1, 0, 0, 0, 0]}
 
 
 def test_two_and_three_calls_sum_to_one(hip):
