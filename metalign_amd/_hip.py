@@ -1121,6 +1121,52 @@ class SamBatch:
             self.handle = None
 
 
+class UploadedBatch:
+    """Host arrays uploaded, behind what stage C reads of a SamBatch: ptr, count, the side pointers, names() and free().  recs:
+    REC_DTYPE[]; places: PLACE_DTYPE[]; edits: EDIT_DTYPE[]; bases: (entries BASES_DTYPE[], the pool's bytes); names: (bytes, offsets).
+    An empty stream uploads one zero record (a handle needs a valid pointer) and no side array; an empty pool goes up as 16 bytes.
+    A side array that was not handed in answers as a SamBatch tokenised without it: HipError with code ERR_STATE."""
+
+    def __init__(self, hip, recs, places=None, edits=None, bases=None, names=None):
+        self.count, self._names, self._arrays = len(recs), names, []
+        sides = {"places": places, "edits": edits}
+        if bases is not None:
+            sides["bases"], pool = bases
+            sides["pool"] = np.frombuffer(pool, dtype=np.uint8) if len(pool) else np.zeros(16, np.uint8)
+        self._side = {k: 0 for k, host in sides.items() if host is not None}
+        try:
+            self.ptr = self._upload(hip, recs if self.count else np.zeros(1, REC_DTYPE))
+            for k in (self._side if self.count else ()):
+                assert k == "pool" or len(sides[k]) == self.count, (k, len(sides[k]), self.count)
+                self._side[k] = self._upload(hip, sides[k].view(np.uint8))
+        except BaseException:
+            self.free()
+            raise
+
+    def _upload(self, hip, host):
+        self._arrays.append(hip.array(host))
+        return self._arrays[-1].ptr
+
+    def _side_ptr(self, side):
+        if side not in self._side:
+            raise HipError("the batch carries no %s" % side, ERR_STATE)
+        return self._side[side]
+
+    places_ptr = property(lambda self: self._side_ptr("places"))
+    edits_ptr = property(lambda self: self._side_ptr("edits"))
+    bases_ptr = property(lambda self: self._side_ptr("bases"))
+    pool_ptr = property(lambda self: self._side_ptr("pool"))
+
+    def names(self):
+        if self._names is None:
+            raise HipError("the batch carries no names", ERR_STATE)
+        return self._names
+
+    def free(self):
+        while self._arrays:
+            self._arrays.pop().free()
+
+
 class _SideAccumulator:
     """What Coverage, Depth and IdentityAcc share: a handle that takes records beside one side array of their batch.  _add / _free: the
     library functions; _side_ptr: the SamBatch pointer that holds the side array; _side_dtype: its host form."""
@@ -2239,26 +2285,12 @@ class Hip:
     def profile_assign_resident(self, recs, ref2tax, ntax, pct_id):
         """As profile_assign, but the multimapped CSR STAYS on the device: -> (dict without the mm_* arrays, plus
         'mm_nreads' / 'mm_nentries', and 'resident' = a ResidentProfile to resolve the multimapped reads with)."""
-        recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
-        ref2tax = np.ascontiguousarray(ref2tax, dtype=np.uint32)
-        T = max(int(ntax), 1)
-        d_recs = self.array(recs if len(recs) else np.zeros(1, REC_DTYPE))
-        d_r2t = self.array(ref2tax if ref2tax.size else np.zeros(1, np.uint32))
-        d_acc = self.empty(3 * T + 2, np.uint64)
-        shard = self.profile_begin_dev(d_recs.ptr, len(recs), False, d_r2t.ptr, len(ref2tax), ntax, pct_id)
-        base = d_acc.ptr
-        if len(recs):
-            shard.commit(True, True, 0, base, base + 8 * T, base + 16 * T, base + 24 * T, reset=True)
-            acc = d_acc.download()
-            nr, ne = shard.multimapped_size()
-        else:  # nothing to run: an empty stream has no boundary at all
-            shard.commit(True, True, 0, base, base + 8 * T, base + 16 * T, base + 24 * T, reset=True)
-            acc = d_acc.download()
-            nr = ne = 0
-        res = dict(count=acc[:ntax].copy(), bases=acc[T:T + ntax].copy(), first_seen=acc[2 * T:2 * T + ntax].copy(),
-                   tot_rds=int(acc[3 * T]), n_ambig=int(acc[3 * T + 1]), mm_nreads=nr, mm_nentries=ne)
-        res['resident'] = ResidentProfile(shard, [d_recs, d_r2t, d_acc])
-        return res
+        batch = UploadedBatch(self, np.ascontiguousarray(recs, dtype=REC_DTYPE))
+        try:
+            return self.profile_assign_dev_records(batch.ptr, batch.count, ref2tax, ntax, pct_id, [batch], resident=True)
+        except BaseException:
+            batch.free()
+            raise
 
     def records_mask_unique(self, d_recs, n, d_words, nreads, d_ref2tax, nref, d_out, check=True):
         """mg_records_mask_unique_dev (--side_reads unique; metalign_amd/side_reads.py: unique_mask_of_records): n records at d_recs
@@ -2282,7 +2314,7 @@ class Hip:
         result (they hold the records).  resident=False: the multimapped CSR is downloaded (same dict as
         profile_assign); True: it stays on the device (same dict as profile_assign_resident).
         assign=True (--read_assignments): also res['assign'] = uint64[2 * reads], every read's verdict words
-        (mg_profile_commit_assign_dev), res['names'] = (bytes, offsets) when the first owner is a named SamBatch, and the
+        (mg_profile_commit_assign_dev), res['names'] = (bytes, offsets) when the first owner offers names(), and the
         multimapped CSR downloaded whatever `resident` says (the rows of the multimapped reads are read from it).
         on_verdicts (--side_reads unique): called once, behind the commit, as on_verdicts(d_recs_ptr, n, d_words_ptr, nreads,
         d_ref2tax_ptr, nref) while the records, the verdict words and ref2tax are all still on the device.  It runs the same
@@ -2319,7 +2351,7 @@ class Hip:
                    tot_rds=int(acc[3 * T]), n_ambig=int(acc[3 * T + 1]))
         if assign:
             res['assign'] = words
-            if owners and isinstance(owners[0], SamBatch):
+            if owners and hasattr(owners[0], 'names'):
                 res['names'] = owners[0].names()
         keep = list(owners) + [d_r2t, d_acc] + ([pad] if pad is not None else [])
         if resident:

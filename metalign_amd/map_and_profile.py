@@ -265,16 +265,6 @@ def _pack_names(names):
     return b''.join(enc), off
 
 
-def _join_names(parts):
-    """The (bytes, offsets) of consecutive chunks -> those of the whole stream."""
-    blobs, offs, at = [], [np.zeros(1, dtype=np.uint64)], 0
-    for blob, off in parts:
-        blobs.append(blob)
-        offs.append(off[1:] + np.uint64(at))
-        at += len(blob)
-    return b''.join(blobs), np.concatenate(offs)
-
-
 def _host_side(lines, of, dtype):
     """A side array of the lines the host tokeniser retains, dtype[] in record order; of: a retained line's fields -> its entry
     (coverage.placement for the places, identity.edit_of for the edits)."""
@@ -292,16 +282,61 @@ def _host_bases(lines):
     return (np.array(ent, dtype=_hip.BASES_DTYPE) if ent else np.zeros(0, dtype=_hip.BASES_DTYPE)), pool
 
 
-def _join_bases(parts):
-    """Every chunk's (entries, pool) -> one: the pools joined, a piled entry's offset moved up by the pools before it."""
-    ents, pools, at = [], [], 0
-    for ent, pool in parts:
-        ent = ent.copy()
-        ent['off'][ent['span'] > 0] += np.uint64(at)
-        ents.append(ent)
-        pools.append(pool)
-        at += len(pool)
-    return (np.concatenate(ents) if ents else np.zeros(0, dtype=_hip.BASES_DTYPE)), b''.join(pools)
+class TokenisedChunks:
+    """What the chunked tokeniser collects, chunk by chunk: the records, whichever of the reads' names (named: --read_assignments),
+    the records' places (placed: --coverage, --depth), their edits (edited: --identity) and their bases (based: --variants) were asked
+    for, and the stream's leading '@' lines (header).  want: the keywords of Hip.sam_tokenize that ask for the same."""
+    # a side -> what the host tokeniser's chunk gives for it (text: the chunk's lines; names: the QNAMEs that open a read there)
+    HOST = {'named': lambda text, names: _pack_names(names),
+            'placed': lambda text, names: _host_side(text, coverage.placement, _hip.PLACE_DTYPE),
+            'edited': lambda text, names: _host_side(text, identity.edit_of, _hip.EDIT_DTYPE),
+            'based': lambda text, names: _host_bases(text)}
+
+    def __init__(self, named=False, placed=False, edited=False, based=False):
+        asked = dict(named=named, placed=placed, edited=edited, based=based)
+        self.want = {k: True for k, on in asked.items() if on}  # (without --variants the calls are what they were)
+        self.sides = {k: [] for k in self.want}  # (in the order Hip.sam_tokenize returns them)
+        self.recs, self.header, self.hstate = [], [], {'leading': True}
+
+    def add(self, recs, sides):
+        """One chunk: its records and, in order, what was asked for beside them."""
+        self.recs.append(recs)
+        for into, got in zip(self.sides.values(), sides):
+            into.append(got)
+
+    def add_from_host(self, recs, text, names):
+        """add() for a chunk the host tokeniser took."""
+        self.add(recs, [self.HOST[k](text, names) for k in self.sides])
+
+    def records(self):
+        if not self.recs:
+            return np.zeros(0, dtype=_hip.REC_DTYPE)
+        return self.recs[0] if len(self.recs) == 1 else np.concatenate(self.recs)
+
+    def joined(self):
+        """The chunks as one stream: the keyword arguments of _hip.UploadedBatch.  The names' blobs and the bases' pools are joined;
+        a name's offset, and a piled entry's, moves up by the blobs / pools before it."""
+        out = dict(recs=self.records())
+        for k, key, dtype in (('placed', 'places', _hip.PLACE_DTYPE), ('edited', 'edits', _hip.EDIT_DTYPE)):
+            if k in self.sides:
+                out[key] = np.concatenate(self.sides[k]) if self.sides[k] else np.zeros(0, dtype=dtype)
+        if 'named' in self.sides:
+            blobs, offs, at = [], [np.zeros(1, dtype=np.uint64)], 0
+            for blob, off in self.sides['named']:
+                blobs.append(blob)
+                offs.append(off[1:] + np.uint64(at))
+                at += len(blob)
+            out['names'] = b''.join(blobs), np.concatenate(offs)
+        if 'based' in self.sides:
+            ents, pools, at = [], [], 0
+            for ent, pool in self.sides['based']:
+                ent = ent.copy()
+                ent['off'][ent['span'] > 0] += np.uint64(at)
+                ents.append(ent)
+                pools.append(pool)
+                at += len(pool)
+            out['bases'] = (np.concatenate(ents) if ents else np.zeros(0, dtype=_hip.BASES_DTYPE)), b''.join(pools)
+        return out
 
 
 def _leading_header(chunk, header, state):
@@ -334,31 +369,24 @@ def _acc_index_of(hip, acc_index):
     return hip.acc_index(names)
 
 
-def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names=None, places=None, header=None, edits=None,
-                        bases=None):
+def tokenise_sam_device(instream, acc_index, decode=False, paf=False, collect=None):
     """SAM (paf=True: PAF) stream -> records on the MI355X (mg_sam_tokenize / mg_paf_tokenize).  A line the reference
     cannot parse is re-run through the host tokeniser so that the very same exception (type and message) surfaces.
-    read_names (--read_assignments): a list that takes every chunk's read names, (bytes, offsets) from mg_sam_tokenize_named — a read that
-    goes on from the chunk before is named there.
-    places (--coverage): a list that takes every chunk's places (PLACE_DTYPE[], beside its records); header: a list that takes the
-    stream's leading '@' lines as the chunks pass.
-    edits (--identity): a list that takes every chunk's edits (EDIT_DTYPE[], beside its records).
-    bases (--variants): a list that takes every chunk's (entries BASES_DTYPE[], pool bytes); _join_bases makes them one."""
+    collect: a TokenisedChunks that takes every chunk's records and what it asks for beside them — the reads' names ((bytes, offsets)
+    from mg_sam_tokenize_named; a read that goes on from the chunk before is named there), the records' places, edits and bases —
+    and the stream's leading '@' lines as the chunks pass."""
     hip = _hip.Hip.get()
-    hstate = {'leading': True}
+    col = collect if collect is not None else TokenisedChunks()
     index = _acc_index_of(hip, acc_index)
-    parts, prev = [], ''
+    prev = ''
     try:
         for chunk in _line_chunks(instream, decode):
-            if header is not None:
-                _leading_header(chunk, header, hstate)
+            if collect is not None:
+                _leading_header(chunk, col.header, col.hstate)
             try:
                 # -> records, last QNAME, then what was asked for: the names, the places, the edits, the bases, in that order
-                recs, prev, *sides = hip.sam_tokenize(chunk, index, prev, paf=paf, named=read_names is not None,
-                                                      placed=places is not None, edited=edits is not None,
-                                                      **({'based': True} if bases is not None else {}))
-                for into, got in zip([x for x in (read_names, places, edits, bases) if x is not None], sides):
-                    into.append(got)
+                recs, prev, *sides = hip.sam_tokenize(chunk, index, prev, paf=paf, **col.want)
+                col.add(recs, sides)
             except _hip.SamParseError as e:
                 lines = bytes(chunk).split(b'\n')
                 bad = lines[e.line].decode('utf-8', 'replace')
@@ -371,37 +399,27 @@ def tokenise_sam_device(instream, acc_index, decode=False, paf=False, read_names
                 # tokeniser is the definition — this chunk goes through it, carrying the previous QNAME in and out.
                 if lines and not lines[-1]:
                     lines.pop()  # (the chunk ends in a newline)
-                host_names = []
+                text, host_names = [ln.decode('utf-8') for ln in lines], []
                 if paf:
-                    recs, prev = _tokenise_paf_from(lines, acc_index, prev, names=host_names)
+                    recs, prev = _tokenise_paf_from(text, acc_index, prev, names=host_names)
                 else:
                     tk = _Tokeniser(acc_index)
                     tk.prev = prev
-                    for ln in lines:
-                        tk.feed(ln.decode('utf-8'))
+                    for ln in text:
+                        tk.feed(ln)
                     recs, prev, host_names = tk.records(), tk.prev, tk.names
-                if read_names is not None:
-                    read_names.append(_pack_names(host_names))
-                if places is not None:
-                    places.append(_host_side((ln.decode('utf-8') for ln in lines), coverage.placement, _hip.PLACE_DTYPE))
-                if edits is not None:
-                    edits.append(_host_side((ln.decode('utf-8') for ln in lines), identity.edit_of, _hip.EDIT_DTYPE))
-                if bases is not None:
-                    bases.append(_host_bases(ln.decode('utf-8') for ln in lines))
-            parts.append(recs)
+                col.add_from_host(recs, text, host_names)
     finally:
         index.free()
-    if not parts:
-        return np.zeros(0, dtype=_hip.REC_DTYPE)
-    return parts[0] if len(parts) == 1 else np.concatenate(parts)
+    return col.records()
 
 
 _device_tokenise = tokenise_sam_device
 
 
-def tokenise_paf_device(instream, acc_index, decode=False, read_names=None):
+def tokenise_paf_device(instream, acc_index, decode=False, collect=None):
     """PAF replay on the device (mg_paf_tokenize): the same records as tokenise_paf."""
-    return tokenise_sam_device(instream, acc_index, decode=decode, paf=True, read_names=read_names)
+    return tokenise_sam_device(instream, acc_index, decode=decode, paf=True, collect=collect)
 
 
 _device_tokenise_paf = tokenise_paf_device
@@ -480,7 +498,7 @@ def _append_assignments(args, rows):
 
 def assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=True):
     """Kernel outputs -> the (taxids2abs, multimapped, low_mem_mmap) triple of the reference (:193-264).
-    want_lists=False leaves `multimapped` as the CSR dict for the vectorised tail (compute_abundances)."""
+    want_lists=False leaves `multimapped` as the CSR dict, with the taxids beside it, for the vectorised tail (compute_abundances)."""
     taxids2abs = {'Unmapped': [0.0, 0.0] + taxid2info['Unmapped']}
     tot_rds, n_ambig = int(res['tot_rds']), int(res['n_ambig'])
     if not args.no_quantify_unmapped:
@@ -499,7 +517,7 @@ def assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=True):
             taxids2abs[taxid] = [nreads, nbases] + taxid2info[taxid]
     if args.low_mem and (res['mm_nreads'] if 'resident' in res else len(res['mm_hitlen'])) > 0:
         raise TypeError("object of type 'int' has no len()")  # what the reference does at :253,255
-    multimapped = multimapped_lists(res, taxids) if want_lists else res
+    multimapped = multimapped_lists(res, taxids) if want_lists else dict(res, taxids=taxids)
     if not args.no_quantify_unmapped:
         if tot_rds == 0:
             sys.exit('No reads mapped. Aborting...')
@@ -507,13 +525,37 @@ def assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=True):
     return taxids2abs, multimapped, {}
 
 
-def _unique_feed(sides, hip, d_places, d_edits, pct_id, d_bases=None):
-    """The on_verdicts hook of Hip.profile_assign_dev_records under --side_reads unique: the records, masked by their reads'
-    verdicts, go to the accumulators beside the side arrays at d_places / d_edits / d_bases (entries, pool)."""
-    def feed(d_recs, n, d_words, nreads, d_ref2tax, nref):
-        if n:  # (as add_batch: an empty stream adds nothing)
-            sides.add_unique_ptrs(hip, d_recs, d_places, d_edits, n, pct_id, d_words, nreads, d_ref2tax, nref, d_bases)
-    return feed
+def _stage_c(args, batch, sides, lengths, tables, acc2info, taxid2info, resident=False, assignments=False, want_lists=True):
+    """Stage C over a batch of records in HBM — a SamBatch the tokeniser left there, an UploadedBatch, the ranks' gathered records —
+    with its side outputs: what every entry point ends in.  sides: a SideOutputs (possibly empty) whose side arrays the batch carries;
+    lengths: what its accumulators are opened with; tables: dense_tables().  The accumulators are closed — their blocks appended to
+    the outputs, their memory freed — as soon as they have been fed: before stage C allocates, or, under --side_reads unique, where
+    stage C itself feeds them through its on_verdicts hook, directly after it.  assignments (--read_assignments): stage C also
+    writes every read's verdict and the rows are appended to args.read_assignments.
+    The batch is taken over: freed here on every way out until stage C's result owns it; the accumulators on every failure."""
+    acc_index, taxids, ref2tax = tables
+    hip, pct_id = _hip.Hip.get(), float(args.pct_id)
+    try:
+        sides.open(hip, lengths, acc_index)
+        hook = sides.on_verdicts(hip, batch, pct_id)
+        if hook is None:
+            sides.add_batch(batch, pct_id)
+            sides.close(acc2info, taxid2info)
+        res = hip.profile_assign_dev_records(batch.ptr, batch.count, ref2tax, len(taxids), pct_id, [batch], resident=resident,
+                                             assign=assignments, **({} if hook is None else {'on_verdicts': hook}))
+    except BaseException:
+        sides.free()
+        batch.free()
+        raise
+    try:
+        sides.close(acc2info, taxid2info)  # (--side_reads unique; otherwise nothing is open any more)
+        if assignments:
+            _append_assignments(args, assignment_rows(res, taxids))
+        return assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=want_lists)
+    except BaseException:
+        if 'resident' in res:
+            res['resident'].free()  # (the batch with it)
+        raise
 
 
 def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _resident=False, _paf=False, _bam=False, _collate=False,
@@ -589,33 +631,11 @@ def map_and_process_file(args, path, acc2info, taxid2info, _want_lists=True, _re
         finally:
             if d_text is not None:
                 d_text.free()
-        sides.open(hip, lengths, acc_index)  # (before stage C takes the batch over)
-        if sides.unique:
-            # --side_reads unique: the records are fed from inside stage C, where every read's verdict is known and the batch
-            # (the collated one, with its permuted side arrays, where it was collated) is still alive
-            feed = _unique_feed(sides, hip, batch.places_ptr if sides.placed and batch.count else None,
-                                batch.edits_ptr if sides.edited and batch.count else None, float(args.pct_id),
-                                (batch.bases_ptr, batch.pool_ptr) if sides.based and batch.count else None)
-            res = hip.profile_assign_dev_records(batch.ptr, batch.count, ref2tax, len(taxids), float(args.pct_id), [batch],
-                                                 resident=_resident, assign=_assignments, on_verdicts=feed)
-        else:
-            sides.add_batch(batch, float(args.pct_id))
-            res = hip.profile_assign_dev_records(batch.ptr, batch.count, ref2tax, len(taxids), float(args.pct_id), [batch],
-                                                 resident=_resident, assign=_assignments)
-        batch = None  # owned by the result now
-    except BaseException:
-        sides.free()
-        raise
     finally:
         index.free()
-        if batch is not None:
-            batch.free()
-    sides.close(acc2info, taxid2info)
-    if _assignments:
-        _append_assignments(args, assignment_rows(res, taxids))
-    if not _want_lists:
-        res = dict(res, taxids=taxids)
-    return assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=_want_lists)
+    # (under --side_reads unique the batch stage C feeds the accumulators from is the collated one, with its permuted side arrays,
+    # where it was collated)
+    return _stage_c(args, batch, sides, lengths, (acc_index, taxids, ref2tax), acc2info, taxid2info, _resident, _assignments, _want_lists)
 
 
 # ---- one process per GPU (python -m torch.distributed.run ... -m metalign_amd.map_and_profile ...) ---------------------
@@ -733,9 +753,11 @@ def gather_record_pieces(torch, dist, rank, world, mine, n, first_q, last_q, bad
     return buf, total
 
 
-class _TensorOwner:
-    def __init__(self, t):
-        self.t = t
+class _TensorBatch:
+    """n records in a device tensor, as the batch stage C takes over."""
+
+    def __init__(self, t, n):
+        self.t, self.ptr, self.count = t, t.data_ptr(), n
 
     def free(self):
         self.t = None
@@ -751,7 +773,7 @@ def map_and_process_file_dist(args, path, acc2info, taxid2info, ctx, _want_lists
     _ = taxid2info['Unmapped']
     index = _acc_index_of(hip, acc_index)
     start, end = sam_range_of_rank(path, rank, world)
-    d_text = batch = None
+    batch = None
     bad = 0
     try:
         try:
@@ -759,9 +781,6 @@ def map_and_process_file_dist(args, path, acc2info, taxid2info, ctx, _want_lists
                 batch = hip.sam_stream_file(path, index, offset=start, length=end - start)
         except (_hip.SamParseError, _hip.HipError):
             bad = 1
-        finally:
-            if d_text is not None:
-                d_text.free()
         n = batch.count if batch is not None else 0
         fq = (first_retained_qname(path, start, end) or '') if n else ''
         lq = batch.last_qname if n else ''
@@ -776,20 +795,16 @@ def map_and_process_file_dist(args, path, acc2info, taxid2info, ctx, _want_lists
             return got
         buf, total = got
         if dev == 'cpu':
-            d_all = hip.array(buf[: max(4 * total, 4)].numpy())
-            ptr, owner = d_all.ptr, d_all
+            gathered = _hip.UploadedBatch(hip, buf[: 4 * total].numpy().view(_hip.REC_DTYPE))
         else:
             torch.cuda.current_stream().synchronize()
-            ptr, owner = buf.data_ptr(), _TensorOwner(buf)
-        res = hip.profile_assign_dev_records(ptr, total, ref2tax, len(taxids), float(args.pct_id), [owner],
-                                             resident=_resident)
+            gathered = _TensorBatch(buf, total)
     finally:
         index.free()
         if batch is not None:
             batch.free()
-    if not _want_lists:
-        res = dict(res, taxids=taxids)
-    return assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=_want_lists)
+    return _stage_c(args, gathered, SideOutputs(args, (), path), None, (acc_index, taxids, ref2tax), acc2info, taxid2info, _resident,
+                    want_lists=_want_lists)
 
 
 class _CudaWords:
@@ -810,123 +825,26 @@ def map_and_process(args, instream, acc2info, taxid2info, _assign=None, _want_li
     if _sides is None:
         named = [(fam, src) for fam, src in ((COVERAGE, _coverage), (DEPTH, _depth), (IDENTITY, _identity)) if src is not None]
         _sides = SideOutputs(args, [fam for fam, _ in named], named[0][1] if named else None)
-    acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
-    if _sides:
-        if _assign is not None:
-            raise ValueError('--coverage, --depth and --identity need the device path')
-        return _map_and_process_sided(args, instream, acc2info, taxid2info, _want_lists, _resident, _assignments, _sides)
+    tables = acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
+    if _sides and _assign is not None:
+        raise ValueError('--coverage, --depth and --identity need the device path')
     _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
-    # test seam: an injected record-level backend is fed by the host tokeniser; product code never passes one
-    tokenise = _device_tokenise if _assign is None else tokenise_sam
-    if getattr(args, 'paf_input', False):
-        tokenise = _device_tokenise_paf if _assign is None else tokenise_paf
-    if _assignments:
+    paf, decode = getattr(args, 'paf_input', False), args.input_type != 'sam'
+    if _sides or _assignments:
         if _assign is not None:
             raise ValueError('--read_assignments needs the device path')
-        parts = []
-        recs = tokenise(instream, acc_index, decode=(args.input_type != 'sam'), read_names=parts)
-        hip = _hip.Hip.get()
-        d_recs = hip.array(recs if len(recs) else np.zeros(1, _hip.REC_DTYPE))
-        res = hip.profile_assign_dev_records(d_recs.ptr, len(recs), ref2tax, len(taxids), float(args.pct_id), [d_recs],
-                                             resident=_resident, assign=True)
-        res['names'] = _join_names(parts)
-        _append_assignments(args, assignment_rows(res, taxids))
-        if not _want_lists:
-            res = dict(res, taxids=taxids)
-        return assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=_want_lists)
-    recs = tokenise(instream, acc_index, decode=(args.input_type != 'sam'))
-    res = (_assign or (_device_assign_resident if _resident else _device_assign))(recs, ref2tax, len(taxids),
-                                                                                  float(args.pct_id))
-    if not _want_lists:
-        res = dict(res, taxids=taxids)
-    return assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=_want_lists)
-
-
-def _map_and_process_sided(args, instream, acc2info, taxid2info, _want_lists, _resident, _assignments, sides):
-    """map_and_process with side outputs, and --read_assignments where that is on."""
-    acc_index, taxids, ref2tax = dense_tables(acc2info, taxid2info)
-    _ = taxid2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
-    names, header = ([] if _assignments else None), []
-    places, edits, bases = ([] if sides.placed else None), ([] if sides.edited else None), ([] if sides.based else None)
-    recs = _device_tokenise(instream, acc_index, decode=(args.input_type != 'sam'), read_names=names, places=places, header=header,
-                            edits=edits, bases=bases)
-    place = np.concatenate(places) if places else np.zeros(0, dtype=_hip.PLACE_DTYPE)
-    edit = np.concatenate(edits) if edits else np.zeros(0, dtype=_hip.EDIT_DTYPE)
-    assert places is None or len(place) == len(recs)
-    assert edits is None or len(edit) == len(recs)
-    entry, pool = _join_bases(bases or [])
-    assert bases is None or len(entry) == len(recs)
-    hip = _hip.Hip.get()
-    d_recs = hip.array(recs if len(recs) else np.zeros(1, _hip.REC_DTYPE))
-    if sides.unique:  # (--side_reads unique: the uploaded places and edits live until stage C has fed the accumulators)
-        d_place = d_edit = d_entry = d_pool = None
-        try:
-            try:
-                sides.open(hip, coverage.lengths_of(header, acc2info), acc_index)
-                if len(recs):
-                    d_place = hip.array(place.view(np.uint8)) if sides.placed else None
-                    d_edit = hip.array(edit.view(np.uint8)) if sides.edited else None
-                    if sides.based:
-                        d_entry = hip.array(entry.view(np.uint8))
-                        d_pool = hip.array(np.frombuffer(pool, dtype=np.uint8) if pool else np.zeros(16, np.uint8))
-            except BaseException:
-                d_recs.free()  # (stage C has not taken the records over yet)
-                raise
-            feed = _unique_feed(sides, hip, d_place.ptr if d_place is not None else None, d_edit.ptr if d_edit is not None else None,
-                                float(args.pct_id), (d_entry.ptr, d_pool.ptr) if d_pool is not None else None)
-            res = hip.profile_assign_dev_records(d_recs.ptr, len(recs), ref2tax, len(taxids), float(args.pct_id), [d_recs],
-                                                 resident=_resident, assign=_assignments, on_verdicts=feed)
-        except BaseException:
-            sides.free()
-            raise
-        finally:
-            if d_place is not None:
-                d_place.free()
-            if d_edit is not None:
-                d_edit.free()
-            for d in (d_entry, d_pool):
-                if d is not None:
-                    d.free()
-        sides.close(acc2info, taxid2info)
-        return _sided_tail(args, res, names, taxids, taxid2info, _want_lists, _assignments)
-    try:
-        sides.open(hip, coverage.lengths_of(header, acc2info), acc_index)
-        if len(recs):
-            d_place = d_edit = d_entry = d_pool = None
-            try:
-                d_place = hip.array(place.view(np.uint8)) if sides.placed else None
-                d_edit = hip.array(edit.view(np.uint8)) if sides.edited else None
-                if sides.based:
-                    d_entry = hip.array(entry.view(np.uint8))
-                    d_pool = hip.array(np.frombuffer(pool, dtype=np.uint8) if pool else np.zeros(16, np.uint8))
-                sides.add_ptrs(d_recs.ptr, d_place.ptr if sides.placed else None, d_edit.ptr if sides.edited else None, len(recs),
-                               float(args.pct_id), (d_entry.ptr, d_pool.ptr) if sides.based else None)
-                hip.sync()
-            finally:
-                if d_place is not None:
-                    d_place.free()
-                if d_edit is not None:
-                    d_edit.free()
-                for d in (d_entry, d_pool):
-                    if d is not None:
-                        d.free()
-        sides.close(acc2info, taxid2info)
-    except BaseException:
-        sides.free()
-        d_recs.free()  # (stage C has not taken the records over yet)
-        raise
-    res = hip.profile_assign_dev_records(d_recs.ptr, len(recs), ref2tax, len(taxids), float(args.pct_id), [d_recs],
-                                         resident=_resident, assign=_assignments)
-    return _sided_tail(args, res, names, taxids, taxid2info, _want_lists, _assignments)
-
-
-def _sided_tail(args, res, names, taxids, taxid2info, _want_lists, _assignments):
-    """What _map_and_process_sided does with stage C's result."""
-    if _assignments:
-        res['names'] = _join_names(names)
-        _append_assignments(args, assignment_rows(res, taxids))
-    if not _want_lists:
-        res = dict(res, taxids=taxids)
+        chunks = TokenisedChunks(named=_assignments, placed=_sides.placed, edited=_sides.edited, based=_sides.based)
+        (_device_tokenise_paf if paf else _device_tokenise)(instream, acc_index, decode=decode, collect=chunks)
+        batch = _hip.UploadedBatch(_hip.Hip.get(), **chunks.joined())
+        return _stage_c(args, batch, _sides, coverage.lengths_of(chunks.header, acc2info), tables, acc2info, taxid2info, _resident,
+                        _assignments, _want_lists)
+    # test seam: an injected record-level backend is fed by the host tokeniser; product code never passes one
+    if _assign is None:
+        tokenise = _device_tokenise_paf if paf else _device_tokenise
+    else:
+        tokenise = tokenise_paf if paf else tokenise_sam
+    recs = tokenise(instream, acc_index, decode=decode)
+    res = (_assign or (_device_assign_resident if _resident else _device_assign))(recs, ref2tax, len(taxids), float(args.pct_id))
     return assemble_taxids2abs(args, res, taxids, taxid2info, want_lists=_want_lists)
 
 

@@ -102,7 +102,8 @@ class _Coverage(_Family):
             aln, bases, covered, unplaced = dev.result()
         finally:
             dev.free()
-        per = {a: [int(aln[i]), int(bases[i]), int(covered[i])] for a, i in acc_index.items() if aln[i]}
+        names = {i: a for a, i in acc_index.items()}
+        per = {names[r]: [int(aln[r]), int(bases[r]), int(covered[r])] for r in np.flatnonzero(aln).tolist()}  # (the rows that are hit)
         self.append(args, source, coverage.Coverage(lengths, per, unplaced), acc2info, taxid2info)
 
     def append(self, args, source, cov, acc2info, taxid2info):
@@ -341,8 +342,21 @@ class SideOutputs:
             self.free()
             raise
 
+    def on_verdicts(self, hip, batch, pct_id):
+        """The on_verdicts hook of Hip.profile_assign_dev_records over `batch` under --side_reads unique: the records, masked by their
+        reads' verdicts, go to the accumulators beside the batch's side arrays, from inside stage C.  None where the accumulators are
+        fed before stage C (add_batch)."""
+        if not self.unique:
+            return None
+
+        def feed(d_recs, n, d_words, nreads, d_ref2tax, nref):
+            if n:  # (as add_batch: an empty stream adds nothing)
+                self.add_unique_ptrs(hip, d_recs, batch.places_ptr if self.placed else None, batch.edits_ptr if self.edited else None, n,
+                                     pct_id, d_words, nreads, d_ref2tax, nref, (batch.bases_ptr, batch.pool_ptr) if self.based else None)
+        return feed
+
     def add_batch(self, batch, pct_id):
-        """A SamBatch that carries every side array the families read."""
+        """A batch (SamBatch, UploadedBatch) that carries every side array the families read."""
         try:
             for _, dev in self._open:
                 dev.add_batch(batch, pct_id)

@@ -301,6 +301,71 @@ def test_hand_table_through_the_tokenisers(hip, tmp_path):
         idx.free()
 
 
+def _same(a, b):
+    """Equality through tuples, lists, dicts and arrays."""
+    if isinstance(a, (tuple, list)):
+        return type(a) is type(b) and len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    if isinstance(a, dict):
+        return isinstance(b, dict) and sorted(a) == sorted(b) and all(_same(a[k], b[k]) for k in a)
+    if isinstance(a, np.ndarray):
+        return isinstance(b, np.ndarray) and a.dtype == b.dtype and np.array_equal(a, b)
+    return a == b and type(a) is type(b)
+
+
+def _through_add_batch_and_stage_c(hip, tmp_path, batch):
+    """Every family's result over `batch`, each fed through SideOutputs.add_batch, then stage C's verdict words and names (which frees
+    the batch)."""
+    t = lambda name: str(tmp_path / name)
+    args = sc.make_args(t("h.sam"), t("db_info.txt"), t("o.cami"), dict(coverage=t("c.tsv"), depth=t("d.tsv"), depth_windows=t("w.tsv"),
+                                                                        depth_window_size=4, identity=t("i.tsv"), variants=t("v.tsv")))
+    sides = so.SideOutputs.of(args, "h.sam")
+    assert sides.families == so.FAMILIES
+    try:
+        sides.open(hip, dict(zip(vc.ACC_INDEX, [0, 20, 1000, 8])), vc.ACC_INDEX)
+        sides.add_batch(batch, PCT)
+        out = [dev.result(*(P if fam is so.VARIANTS else ())) for fam, dev in sides._open]
+    except BaseException:
+        batch.free()
+        raise
+    finally:
+        sides.free()
+    res = hip.profile_assign_dev_records(batch.ptr, batch.count, np.arange(4, dtype=np.uint32), 4, PCT, [batch], assign=True)
+    return out, res["assign"], res["names"], {k: res[k] for k in ("count", "bases", "first_seen", "tot_rds", "n_ambig")}
+
+
+@pytest.mark.parametrize("empty", [False, True])
+def test_an_uploaded_batch_is_read_as_the_batch_it_was_downloaded_from(hip, tmp_path, empty):
+    """The hand table (and a header alone: zero records) tokenised with names, places, edits and bases; everything downloaded and
+    uploaded again as an UploadedBatch: the four accumulators and stage C read the two batches alike."""
+    text = b"@HD\tVN:1.6\n" if empty else b"".join(ln if isinstance(ln, bytes) else ln.encode() for ln in vc.HAND)
+    idx = _index(hip, vc.ACC_INDEX)
+    raw = np.frombuffer(text, dtype=np.uint8)
+    d_t = hip.array(raw)
+    up = None
+    try:
+        b = hip.sam_tokenize_dev_batch(d_t.ptr, raw.size, idx, named=True, placed=True, edited=True, based=True)
+        try:
+            recs, places, edits, bases, names = b.download(), b.places(), b.edits(), b.bases(), b.names()
+            assert b.count == (0 if empty else len(mp.tokenise_sam(vc.HAND, vc.ACC_INDEX)))
+            up = _hip.UploadedBatch(hip, recs, places=places, edits=edits, bases=bases, names=names)
+            assert up.count == b.count and (up.ptr and up.ptr != b.ptr)
+        except BaseException:
+            b.free()
+            raise
+        want = _through_add_batch_and_stage_c(hip, tmp_path, b)
+        got = _through_add_batch_and_stage_c(hip, tmp_path, up)
+        assert _same(got, want)
+        if not empty:  # (what the hand table's test holds the accumulator to)
+            assert list(want[0][3][0]) == [0, 9, 1, 1] and want[0][3][5] == vc.HAND_UNPILED and len(want[1]) == 2 * (len(names[1]) - 1) > 0
+        else:
+            assert len(want[1]) == 0 and names[1].tolist() == [0] and int(want[3]["tot_rds"]) == 0
+    finally:
+        if up is not None:
+            up.free()
+        d_t.free()
+        idx.free()
+
+
 def test_entries_and_pool_are_the_same_whole_host_streamed_compressed_and_bam(hip, tmp_path):
     _, _, _, _, acc_index, lines, (want_ent, want_pool) = _case()
     text = "".join(lines)

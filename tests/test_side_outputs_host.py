@@ -395,7 +395,11 @@ def test_dispatch_reaches_the_former_entry_point(monkeypatch, tmp_path, _bam, _c
 def test_the_keywords_of_map_and_process_become_the_object(monkeypatch, tmp_path):
     """_coverage=, _depth=, _identity= (the name the block is written under) reach the streaming path as one SideOutputs."""
     seen = []
-    monkeypatch.setattr(mp, "_map_and_process_sided", lambda *a: seen.append(a[-1]) or "done")
+    hip = DispatchHip()
+    hip.array = lambda host: _Freeable()
+    monkeypatch.setattr(_hip.Hip, "get", classmethod(lambda cls, *a, **k: hip))
+    monkeypatch.setattr(mp, "_device_tokenise", lambda instream, acc_index, decode=False, collect=None: None)
+    monkeypatch.setattr(mp, "_stage_c", lambda args, batch, sides, *a: seen.append(sides) or "done")
     args = _all_on(tmp_path)
     assert mp.map_and_process(args, [], ACC2INFO, TAXID2INFO, _depth="f.sam", _identity="f.sam") == "done"
     assert seen[0].families == (so.DEPTH, so.IDENTITY) and seen[0].source == "f.sam" and seen[0].placed and seen[0].edited
