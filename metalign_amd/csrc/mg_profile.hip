@@ -1248,7 +1248,8 @@ int launch_pass(mg_profile* p, bool commit, uint32_t incoming, uint32_t first_sh
   a.out_tot = p->tot.as<uint64_t>();
   if (!commit) {
     ProfScope ps("profile_map", st);
-    const unsigned grid = grid_for(p->ntiles, 1, (unsigned)c.num_cus * 4);
+    unsigned grid = grid_for(p->ntiles, 1, (unsigned)c.num_cus * 4);
+    { const int64_t v = dbg("k3_grid"); if (v > 0 && (uint64_t)v < grid) grid = (unsigned)v; }  // test hook, as for the commit pass below
     if (grid < a.ticket_lanes) a.ticket_lanes = grid;
     hipLaunchKernelGGL(k_profile_pass<false>, dim3(grid), dim3(kPB), 0, st, a);
     MG_HIP(hipGetLastError());

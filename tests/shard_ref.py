@@ -53,6 +53,13 @@ def _process(hits, recs, ref2tax, pct_id, npair):
 
 
 def run_shard(recs, nrecs, has_look, ref2tax, ntax, pct_id, incoming, first_shard, group_base):
+    """Also: verdicts = one (kind, taxon, hitlen or row in the shard's multimapped CSR) per read of the shard, in the terms of
+    mg_profile_commit_assign_dev's two words (kind 3: the shard's last read when no line closes it), and state_end = the state
+    after the last read that was closed (`incoming` when none was) — the value of the shard's state map at `incoming`."""
+    if isinstance(recs, np.ndarray):  # plain lists: the loop below reads every field of every record one by one
+        recs = {k: recs[k].tolist() for k in recs.dtype.names}
+    ref2tax = np.asarray(ref2tax).tolist()
+    verdicts, state_end = [], incoming
     count = np.zeros(ntax, dtype=np.uint64)
     bases = np.zeros(ntax, dtype=np.uint64)
     first = np.full(ntax, 2**64 - 1, dtype=np.uint64)
@@ -83,6 +90,8 @@ def run_shard(recs, nrecs, has_look, ref2tax, ntax, pct_id, incoming, first_shar
                     mm.append((ridx, taxa, hitlen))
                 else:
                     ambig += 1
+                verdicts.append((kind, tax if kind == 1 else 0, hitlen if kind == 1 else len(mm) - 1 if kind == 2 else 0))
+                state_end = 1 if kind == 0 else 0
                 if i == nrecs:  # the lookahead only closes the last read
                     outgoing = 1 if kind == 0 else 0
                     break
@@ -91,4 +100,6 @@ def run_shard(recs, nrecs, has_look, ref2tax, ntax, pct_id, incoming, first_shar
                     continue
         if i < nrecs:
             hits.append(i)
-    return dict(count=count, bases=bases, first_seen=first, groups=groups, ambig=ambig, outgoing=outgoing, mm=mm)
+    verdicts += [(3, 0, 0)] * (groups - len(verdicts))
+    return dict(count=count, bases=bases, first_seen=first, groups=groups, ambig=ambig, outgoing=outgoing, mm=mm,
+                verdicts=verdicts, state_end=state_end)

@@ -3,55 +3,13 @@ sharded C-ABI of stage C (begin / state_map / commit with lookahead) on the real
 import numpy as np
 import pytest
 
-from metalign_amd import _hip, synth
-from metalign_amd.distributed import compose_incoming
+from metalign_amd import synth
+from util import stage_c_sharded
 
 pytestmark = pytest.mark.gpu
-U64_MAX = 0xFFFFFFFFFFFFFFFF
 _COMP = np.zeros(256, dtype=np.uint8)
 for a, b in zip(b"ACGT", b"TGCA"):
     _COMP[a] = b
-
-
-def _stage_c_sharded(hip, recs, ref2tax, ntax, cuts, pct_id=0.5):
-    """Run stage C as len(cuts)+1 shards through mg_profile_begin_dev / _commit_dev; -> same dict as profile_assign."""
-    bounds = [0] + list(cuts) + [len(recs)]
-    d_r2t = hip.array(ref2tax)
-    acc = hip.empty(3 * ntax + 2, np.uint64)
-    host = np.zeros(3 * ntax + 2, dtype=np.uint64)
-    host[2 * ntax:3 * ntax] = U64_MAX
-    acc.upload(host)
-    shards, arrays = [], []
-    for i in range(len(bounds) - 1):
-        a, b = bounds[i], bounds[i + 1]
-        look = i + 1 < len(bounds) - 1 or False
-        has_look = b < len(recs)
-        part = recs[a:b + (1 if has_look else 0)]
-        d = hip.array(part if len(part) else np.zeros(1, _hip.REC_DTYPE))
-        arrays.append(d)
-        shards.append(hip.profile_begin_dev(d.ptr, b - a, has_look, d_r2t.ptr, len(ref2tax), ntax, pct_id))
-    maps = [s.state_map() for s in shards]
-    groups = [s.ngroups for s in shards]
-    mm_all = []
-    base = acc.ptr
-    first_nonempty = next(i for i in range(len(shards)) if bounds[i + 1] > bounds[i])
-    for i, s in enumerate(shards):
-        s.commit(compose_incoming(maps, i), i == first_nonempty, sum(groups[:i]), base, base + 8 * ntax,
-                 base + 16 * ntax, base + 24 * ntax)
-        mm_all.append(s.multimapped())
-    out = acc.download()
-    off = [np.zeros(1, np.uint64)]
-    tot_e = 0
-    for o, t, h, r in mm_all:
-        off.append(o[1:] + np.uint64(tot_e))
-        tot_e += len(t)
-    res = dict(count=out[:ntax], bases=out[ntax:2 * ntax], first_seen=out[2 * ntax:3 * ntax], tot_rds=int(out[3 * ntax]),
-               n_ambig=int(out[3 * ntax + 1]), mm_offsets=np.concatenate(off),
-               mm_tax=np.concatenate([m[1] for m in mm_all]), mm_hitlen=np.concatenate([m[2] for m in mm_all]),
-               mm_read=np.concatenate([m[3] for m in mm_all]))
-    for s in shards:
-        s.free()
-    return res
 
 
 def _random_records(rng, n, nref, p_new, flags, oracle_dtype):
@@ -77,7 +35,7 @@ def test_stage_c_shards_on_gpu_equal_whole_stream(hip, oracle_lib, p_new, flags)
     want = oracle_lib.profile_assign(recs, ref2tax, ntax, 0.5)
     for cuts in ([int(starts[len(starts) // 2])], [int(starts[3]), int(starts[len(starts) // 3]), int(starts[-2])],
                  [int(starts[1]), int(starts[1]), int(starts[2])]):  # an empty middle shard too
-        got = _stage_c_sharded(hip, recs, ref2tax, ntax, sorted(cuts))
+        got = stage_c_sharded(hip, recs, ref2tax, ntax, sorted(cuts))
         for key in want:
             assert np.array_equal(np.asarray(got[key]), np.asarray(want[key])), (key, cuts)
 
@@ -163,7 +121,7 @@ def test_config2_full_size_properties(hip):
     assert int(res["count"].sum()) + len(res["mm_hitlen"]) + (res["n_ambig"] - 1) == res["tot_rds"] - 1
     starts = np.nonzero(recs["ref_new"] >> 31)[0]
     cuts = [int(starts[len(starts) // 4]), int(starts[len(starts) // 2]), int(starts[3 * len(starts) // 4])]
-    sharded = _stage_c_sharded(hip, recs, ref2tax, 10_001, cuts)
+    sharded = stage_c_sharded(hip, recs, ref2tax, 10_001, cuts)
     for key in ("count", "bases", "first_seen", "tot_rds", "n_ambig", "mm_read", "mm_tax", "mm_hitlen", "mm_offsets"):
         assert np.array_equal(np.asarray(sharded[key]), np.asarray(res[key])), key
 

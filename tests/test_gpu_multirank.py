@@ -22,7 +22,7 @@ import pytest
 import util
 from metalign_amd import formats, synth
 from metalign_amd.distributed import table_bounds, table_max_hash, table_slice
-from test_gpu_fullsize import _stage_c_sharded
+from util import stage_c_sharded
 
 pytestmark = pytest.mark.gpu
 
@@ -92,7 +92,7 @@ def test_hash_range_sharding_emulated(hip, oracle_lib, world, ks):
     want = oracle_lib.profile_assign(recs, ref2tax, 37, 0.5)
     starts = np.nonzero(recs["ref_new"] >> 31)[0]
     cuts = [int(starts[len(starts) * r // world]) for r in range(1, world)]
-    got = _stage_c_sharded(hip, recs, ref2tax, 37, cuts)
+    got = stage_c_sharded(hip, recs, ref2tax, 37, cuts)
     for key in want:
         assert np.array_equal(np.asarray(got[key]), np.asarray(want[key])), (key, world)
 
@@ -198,7 +198,7 @@ def test_config4_one_rank_stage_c_full_size(hip, oracle_lib):
         assert np.array_equal(np.asarray(got[key]), np.asarray(want[key])), key
     starts = np.nonzero(recs["ref_new"] >> 31)[0]
     cuts = [int(starts[len(starts) * r // 8]) for r in range(1, 8)]
-    sharded = _stage_c_sharded(hip, recs, ref2tax, T, cuts)
+    sharded = stage_c_sharded(hip, recs, ref2tax, T, cuts)
     for key in want:
         assert np.array_equal(np.asarray(sharded[key]), np.asarray(want[key])), key
 

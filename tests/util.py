@@ -323,3 +323,59 @@ def edge_sample(rng, gbases, goffsets, kinds, k, edges, last=TILE, main=0, prese
             reads += [bytes(b[int(o[i]):int(o[i + 1])]) for i in range(len(o) - 1)]
     assert not e, "more edge reads than edge tiles"
     return flat(reads)
+
+
+# ---- stage C through the sharded C ABI (test_gpu_fullsize.py, test_gpu_profile_geometry.py)
+def stage_c_sharded(hip, recs, ref2tax, ntax, cuts, pct_id=0.5, info=None, assign=False):
+    """Run stage C as len(cuts)+1 shards through mg_profile_begin_dev / _commit_dev; -> same dict as profile_assign.
+    info (a dict): gets 'maps' and 'groups', every shard's state_map() and ngroups as the map-only passes gave them BEFORE any
+    commit.  assign: commit through mg_profile_commit_assign_dev; info['words'] = every shard's verdict words."""
+    from metalign_amd import _hip
+    from metalign_amd.distributed import compose_incoming
+    bounds = [0] + list(cuts) + [len(recs)]
+    d_r2t = hip.array(ref2tax)
+    acc = hip.empty(3 * ntax + 2, np.uint64)
+    host = np.zeros(3 * ntax + 2, dtype=np.uint64)
+    host[2 * ntax:3 * ntax] = 0xFFFFFFFFFFFFFFFF
+    acc.upload(host)
+    shards, arrays = [], []
+    for i in range(len(bounds) - 1):
+        a, b = bounds[i], bounds[i + 1]
+        has_look = b < len(recs)
+        part = recs[a:b + (1 if has_look else 0)]
+        d = hip.array(part if len(part) else np.zeros(1, _hip.REC_DTYPE))
+        arrays.append(d)
+        shards.append(hip.profile_begin_dev(d.ptr, b - a, has_look, d_r2t.ptr, len(ref2tax), ntax, pct_id))
+    maps = [s.state_map() for s in shards]
+    groups = [s.ngroups for s in shards]
+    if info is not None:
+        info.update(maps=maps, groups=groups, words=[])
+    mm_all = []
+    base = acc.ptr
+    first_nonempty = next(i for i in range(len(shards)) if bounds[i + 1] > bounds[i])
+    for i, s in enumerate(shards):
+        args = (compose_incoming(maps, i), i == first_nonempty, sum(groups[:i]), base, base + 8 * ntax, base + 16 * ntax, base + 24 * ntax)
+        if assign:
+            d_words = hip.empty(max(2 * groups[i], 2), np.uint64)
+            s.commit_assign(*args, d_words.ptr)
+            if info is not None:
+                info["words"].append(d_words.download()[:2 * groups[i]])
+            d_words.free()
+        else:
+            s.commit(*args)
+        mm_all.append(s.multimapped())
+    out = acc.download()
+    off = [np.zeros(1, np.uint64)]
+    tot_e = 0
+    for o, t, h, r in mm_all:
+        off.append(o[1:] + np.uint64(tot_e))
+        tot_e += len(t)
+    res = dict(count=out[:ntax], bases=out[ntax:2 * ntax], first_seen=out[2 * ntax:3 * ntax], tot_rds=int(out[3 * ntax]),
+               n_ambig=int(out[3 * ntax + 1]), mm_offsets=np.concatenate(off),
+               mm_tax=np.concatenate([m[1] for m in mm_all]), mm_hitlen=np.concatenate([m[2] for m in mm_all]),
+               mm_read=np.concatenate([m[3] for m in mm_all]))
+    for s in shards:
+        s.free()
+    for d in arrays + [d_r2t, acc]:
+        d.free()
+    return res

@@ -28,9 +28,9 @@ if which in ("all", "commit"):
     sh.free()
 if which in ("all", "shard"):
     import oracle
-    from test_gpu_fullsize import _stage_c_sharded
+    from util import stage_c_sharded
     oracle.build()
     starts = np.nonzero(recs["ref_new"] >> 31)[0]
     want = oracle.profile_assign(recs, np.arange(T, dtype=np.uint32), T, 0.5)
-    got = _stage_c_sharded(hip, recs, np.arange(T, dtype=np.uint32), T, [int(starts[len(starts) // 2])])
+    got = stage_c_sharded(hip, recs, np.arange(T, dtype=np.uint32), T, [int(starts[len(starts) // 2])])
     print("sharded:", all(np.array_equal(np.asarray(got[k]), np.asarray(want[k])) for k in want), flush=True)
