@@ -1063,7 +1063,18 @@ void mg_identity_free(mg_identity* h);
  *   MG_ERR_ARG): alignments, callable, polymorphic, pairs, discordant (u64[nacc] each), *unpiled, and *nsites = the polymorphic
  *   sites, which it keeps for fetch_sites.  Synchronises.  May be called again, with other thresholds or after further add_dev
  *   calls; the sites kept are those of the last call.
- * fetch_sites: out[nsites], ordered by (accession row, pos0).  MG_ERR_STATE before a finish. */
+ * fetch_sites: out[nsites], ordered by (accession row, pos0).  MG_ERR_STATE before a finish.
+ * consensus (--consensus; the definition is metalign_amd/consensus.py): the consensus sequences of accession rows
+ *   rows[0 .. nrows) as text, back to back in that order, into out (HOST memory).  A row's text is its length's characters with a
+ *   newline behind every `width` of them and behind the last one: length + ceil(length / width) bytes, none for a length of 0.  A
+ *   site's character is N where its A + C + G + T lie below min_depth; else the major allele's letter (ties to the lowest code),
+ *   or, with iupac = 1, the IUPAC code of the major allele and the variant alleles finish() would name.  Rows may come in any
+ *   order and may repeat; a row without an alignment gives N throughout.  Reads the counts only: needs no finish before it and
+ *   leaves what a finish kept (fetch_sites still works); may be called again after further add_dev calls.  Synchronises.
+ *   MG_ERR_ARG (the wanted figure in the message) for a row >= nacc, width outside 1 .. 65535, iupac above 1, thresholds outside
+ *   finish's ranges, or out_bytes other than the sum of the rows' text bytes: exactly out_bytes bytes of out are written.
+ *   nrows = 0 with out_bytes = 0 is legal and does nothing.  MG_ERR_NOMEM when the device buffer for the text does not fit: the
+ *   caller then asks for fewer rows.  Only the text crosses to the host, one byte per base, never the sixteen of the counts. */
 typedef struct mg_variants mg_variants;
 typedef struct mg_variant_site {
   uint32_t acc;  /* accession row */
@@ -1077,6 +1088,8 @@ int mg_variants_finish(mg_variants* h, uint32_t min_depth, uint32_t min_count, u
                        uint64_t* callable_sites, uint64_t* polymorphic_sites, uint64_t* pairs, uint64_t* discordant, uint64_t* unpiled,
                        uint64_t* nsites);
 int mg_variants_fetch_sites(mg_variants* h, mg_variant_site* out);
+int mg_variants_consensus(mg_variants* h, const uint32_t* rows, uint32_t nrows, uint32_t min_depth, uint32_t min_count,
+                          uint32_t freq_permille, uint32_t iupac, uint32_t width, uint8_t* out, uint64_t out_bytes);
 void mg_variants_free(mg_variants* h);
 
 /* SIDE OUTPUTS FROM UNIQUELY ASSIGNED READS (--side_reads unique; metalign_amd/csrc/mg_sidemask.hip; the definition is

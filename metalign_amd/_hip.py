@@ -53,7 +53,8 @@ EXPORTS = [
     "mg_sam_batch_edits_download", "mg_sam_batch_edits_device_ptr",
     "mg_identity_create", "mg_identity_add_dev", "mg_identity_result", "mg_identity_fetch_hist", "mg_identity_free",
     "mg_sam_batch_bases_download", "mg_sam_batch_bases_device_ptr",
-    "mg_variants_create", "mg_variants_add_dev", "mg_variants_finish", "mg_variants_fetch_sites", "mg_variants_free",
+    "mg_variants_create", "mg_variants_add_dev", "mg_variants_finish", "mg_variants_fetch_sites", "mg_variants_consensus",
+    "mg_variants_free",
     "mg_records_mask_unique_dev",
     "mg_gunzip_open", "mg_gunzip_read", "mg_gunzip_close", "mg_zcat_files", "mg_stream_thin_file",
     "mg_inflate_dev", "mg_inflated_bytes", "mg_inflated_download", "mg_inflated_free", "mg_inflate_config", "mg_inflate_stats",
@@ -152,6 +153,8 @@ def load_library(path=LIB_PATH):
     lib.mg_depth_free.restype = None
     lib.mg_identity_free.restype = None
     lib.mg_variants_free.restype = None
+    lib.mg_variants_consensus.argtypes = [_vp, _u32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                          ctypes.c_uint32, _u8p, ctypes.c_uint64]
     lib.mg_shutdown.restype = None
     return lib
 
@@ -1278,6 +1281,7 @@ class VariantsAcc(_SideAccumulator):
         self.hip = hip
         ln = np.ascontiguousarray(lengths, dtype=np.uint64)
         self.nacc = int(ln.size)
+        self.lengths = ln.copy()  # (what consensus() sizes its text by)
         h = _vp()
         hip._chk(hip.lib.mg_variants_create(_np(ln if ln.size else np.zeros(1, np.uint64), ctypes.c_uint64), ctypes.c_uint32(self.nacc),
                                             ctypes.byref(h)))
@@ -1336,6 +1340,30 @@ class VariantsAcc(_SideAccumulator):
         """finish() and the fetch -> (alignments, callable, polymorphic, pairs, discordant, unpiled, sites)."""
         r = self.finish(min_depth, min_count, permille)
         return r[:6] + (self.fetch_sites(),)
+
+    def text_bytes(self, rows, width=60):
+        """The bytes of these accession rows' consensus texts, back to back: per row L + ceil(L / width)."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        ln = self.lengths[rows[rows < self.nacc]]  # (a row at or above nacc: the library refuses it)
+        return sum(int(L) + (int(L) + width - 1) // width for L in ln.tolist())
+
+    def consensus_into(self, rows, min_depth, min_count, permille, iupac, width, out, out_bytes):
+        """mg_variants_consensus as it stands: the texts of `rows` into the first out_bytes bytes of the uint8 array `out`."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        assert out.dtype == np.uint8 and out.flags.c_contiguous and out.size >= out_bytes
+        self.hip._chk(self.hip.lib.mg_variants_consensus(self.handle, _np(rows if rows.size else np.zeros(1, np.uint32), ctypes.c_uint32),
+                                                         rows.size, int(min_depth), int(min_count), int(permille), int(iupac), int(width),
+                                                         _np(out, ctypes.c_uint8), int(out_bytes)))
+
+    def consensus(self, rows, min_depth, min_count, permille, iupac, width=60):
+        """-> bytes: the consensus sequences of these accession rows as text of lines of `width` characters, back to back in the
+        order of `rows` (metalign_amd/consensus.py is the definition: char_of, text_of).  Reads the counts only: before or after a
+        finish(), and again after further adds.  HipError with code ERR_NOMEM when the text does not fit on the device: ask for fewer
+        rows."""
+        nbytes = self.text_bytes(rows, width) if 1 <= int(width) <= 65535 else 0  # (the library refuses the width)
+        out = np.empty(max(nbytes, 1), dtype=np.uint8)
+        self.consensus_into(rows, min_depth, min_count, permille, iupac, width, out, nbytes)
+        return out[:nbytes].tobytes()
 
 
 class Depth(_SideAccumulator):

@@ -76,6 +76,15 @@ _OPTIONS = {
     'variant_min_count': dict(type=int, default=2, help='A variant allele has at least this many reads (default 2, at least 1).'),
     'variant_min_freq': dict(type=float, default=0.05, help='... and at least this share of the site\'s depth (default 0.05, within '
                              '0 to 0.5; compared in parts per thousand).'),
+    'consensus': dict(default='NONE', help='Also write the consensus sequence of every accession with a piled alignment here '
+                      '(FASTA, lines of 60): per reference base the major allele of the reads, N below --variant_min_depth, from the '
+                      'allele counts --variants keeps (metalign_amd/consensus.py is the definition). SAM / BAM input, one process '
+                      'only.'),
+    'consensus_ambiguity': dict(default='major', choices=['major', 'iupac'],
+                                help='A polymorphic site of --consensus: "major" writes its major allele (default), "iupac" the IUPAC '
+                                     'code of the major and the variant alleles (--variant_min_count, --variant_min_freq).'),
+    'consensus_min_called': dict(type=float, default=0.0, help='Write an accession to --consensus only when at least this share of '
+                                 'its bases is callable (default 0.0, within 0 to 1; compared in parts per thousand).'),
     'side_reads': dict(default='all', choices=['all', 'unique'],
                        help='Which alignments --coverage, --depth, --depth_windows and --identity count: "all" that pass --pct_id (the '
                             'default), or "unique": only those of reads the profile assigned uniquely, on an accession of the taxon '
@@ -102,7 +111,8 @@ _TOOLS = {
                  'read_cutoff', 'sampleID', 'sensitive', 'strain_level', 'temp_dir', 'threads', 'verbose',
                  'sketch_table', 'min_count', 'sketch_size', 'kmer_match', 'device_multimap', 'collate', 'read_assignments', 'coverage',
                  'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size', 'identity', 'side_reads',
-                 'variants', 'variant_sites', 'variant_min_depth', 'variant_min_count', 'variant_min_freq']),
+                 'variants', 'variant_sites', 'variant_min_depth', 'variant_min_count', 'variant_min_freq',
+                 'consensus', 'consensus_ambiguity', 'consensus_min_called']),
     'select_db': dict(
         description='Run CMash and select a subset of the whole database to align to.',
         positionals=[('reads', dict(help='Reads file (FASTA / FASTQ, optionally .gz, or a BAM of reads).')),
@@ -119,7 +129,8 @@ _TOOLS = {
                  'rank_renormalize', 'output', 'pct_id', 'no_quantify_unmapped', 'read_cutoff', 'sampleID', 'threads',
                  'verbose', 'device_multimap', 'collate', 'read_assignments', 'coverage',
                  'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size', 'identity', 'side_reads',
-                 'variants', 'variant_sites', 'variant_min_depth', 'variant_min_count', 'variant_min_freq']),
+                 'variants', 'variant_sites', 'variant_min_depth', 'variant_min_count', 'variant_min_freq',
+                 'consensus', 'consensus_ambiguity', 'consensus_min_called']),
 }
 
 

@@ -20,6 +20,12 @@
 //   k_var_sites<true>   the sites: the same walk a second time; a polymorphic site goes to the block's base + the polymorphic sites
 //                       before it in the block (a ballot and mbcnt per 64 sites), so the sites come out ordered by (accession row,
 //                       pos0) whatever the grid.
+//   k_var_consensus     the counts of a list of accession rows -> their consensus sequences as text (--consensus;
+//                       metalign_amd/consensus.py is the definition), laid out over OUTPUT bytes: every wavefront takes kTextStep
+//                       bytes of the texts, which lie back to back, finds the row of its first byte in the text offsets
+//                       (mgv::owner_of, every lane then mgv::owner_from for its own byte) and each lane judges the site its byte
+//                       shows (mgvar::text_at, mgvar::consensus_char): neighbouring lanes load neighbouring 16-byte cells, four
+//                       lanes' characters are packed into one dword store.  Reads the counts only.
 #include "mg_internal.h"
 #include "mg_variants_core.h"
 #include "mg_side_dev.h"
@@ -36,6 +42,7 @@ struct mg_variants {
   DevBuf sums;   // u64[5 nacc + 1]: alignments, callable, polymorphic, pairs, discordant, unpiled
   DevBuf blk;    // u64[1 + nblocks]: the scan's carry, then the blocks' polymorphic sites / bases
   DevBuf sites;  // mg_variant_site[npoly]
+  std::vector<uint64_t> h_len;  // the lengths again, on the host: what mg_variants_consensus sizes the texts by
   ~mg_variants() { if (cnt) (void)hipFree(cnt); }
 };
 
@@ -43,6 +50,7 @@ namespace {
 
 constexpr unsigned kBlock = 256, kBins = 1024, kScanBlock = 256;
 constexpr uint64_t kStep = 1024;  // sites per wavefront and step of k_var_sites
+constexpr uint64_t kTextStep = 1024;  // output bytes per wavefront and step of k_var_consensus (a multiple of 64)
 
 struct PoolView {
   const uint8_t* p;
@@ -181,6 +189,44 @@ __global__ __launch_bounds__(kScanBlock) void k_var_scan(unsigned long long* __r
   if (threadIdx.x == 0) *total = all;
 }
 
+// The texts of rows[0 .. nrows) back to back: toff[r] is the first byte of row r's text, toff[nrows] = total their sum.  Byte i of
+// the buffer belongs to the row that owns offset i; a row of length 0 has no byte and owns nothing.  out32 has (total + 3) / 4 words;
+// the bytes of the last word behind `total` are written as 0.
+__global__ __launch_bounds__(kBlock) void k_var_consensus(const uint32_t* __restrict__ cnt, const uint64_t* __restrict__ off,
+                                                          const uint64_t* __restrict__ len, const uint64_t* __restrict__ toff,
+                                                          const uint32_t* __restrict__ rows, uint32_t nrows, uint64_t total,
+                                                          uint64_t nsteps, uint32_t min_depth, uint32_t min_count, uint32_t permille,
+                                                          uint32_t iupac, uint32_t width, uint32_t* __restrict__ out32) {
+  const unsigned lane = threadIdx.x & 63u;
+  const uint64_t wave = (uint64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  const uint64_t nwaves = (uint64_t)gridDim.x * (kBlock / 64);
+  const uint4* cnt4 = reinterpret_cast<const uint4*>(cnt);
+  for (uint64_t b = wave; b < nsteps; b += nwaves) {
+    const uint64_t t0 = b * kTextStep, t1 = t0 + kTextStep < total ? t0 + kTextStep : total;
+    uint32_t r = mgv::owner_of(toff, nrows, t0);  // (toff[nrows] = total > t0)
+    for (uint64_t i0 = t0; i0 < t1; i0 += 64) {    // (uniform: every lane takes part in the shuffles; i0 is a multiple of 64)
+      const uint64_t i = i0 + lane;
+      uint32_t ch = 0;
+      if (i < total) {
+        r = mgv::owner_from(toff, nrows, r, i);  // (the lane's own row: r < nrows, as i < toff[nrows])
+        const uint32_t a = rows[r];
+        // (i - toff[r] < text_bytes(len[a]): a byte that is no newline shows a site below len[a], a cell of accession a)
+        const mgvar::TextAt t = mgvar::text_at(i - toff[r], width, len[a]);
+        ch = '\n';
+        if (!t.newline) {
+          const uint4 v = cnt4[off[a] + t.site];
+          const uint32_t n4[4] = {v.x, v.y, v.z, v.w};
+          ch = mgvar::consensus_char(n4, min_depth, min_count, permille, iupac != 0);
+        }
+      }
+      // lanes 4q .. 4q + 3 hold bytes 4q .. 4q + 3 of a word: lane 4q stores it
+      uint32_t w = ch | ((uint32_t)__shfl_down(ch, 1, 64) << 8);
+      w |= (uint32_t)__shfl_down(w, 2, 64) << 16;
+      if ((lane & 3u) == 0 && i < total) out32[i >> 2] = w;
+    }
+  }
+}
+
 unsigned var_grid(uint64_t items, unsigned per_block) { return side_grid(items, per_block, "var_grid"); }
 
 }  // namespace
@@ -211,6 +257,7 @@ int mg_variants_create(const uint64_t* lengths, uint32_t nacc, mg_variants** out
   MG_HIP(hipMemsetAsync(h->sums.p, 0, (5ull * nacc + 1) * sizeof(uint64_t), st));
   MG_HIP(hipMemcpyAsync(h->off.p, h_off.data(), (nacc + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
   if (nacc) MG_HIP(hipMemcpyAsync(h->len.p, lengths, (uint64_t)nacc * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  h->h_len.assign(lengths, lengths + nacc);
   MG_HIP(hipStreamSynchronize(st));  // (h_off and the caller's lengths are free from here)
   *out = h.release();
   return MG_OK;
@@ -291,6 +338,47 @@ int mg_variants_fetch_sites(mg_variants* h, mg_variant_site* out) {
     MG_HIP(hipMemcpyAsync(out, h->sites.p, h->npoly * sizeof(mg_variant_site), hipMemcpyDeviceToHost, st));
     MG_HIP(hipStreamSynchronize(st));
   }
+  return MG_OK;
+}
+
+int mg_variants_consensus(mg_variants* h, const uint32_t* rows, uint32_t nrows, uint32_t min_depth, uint32_t min_count,
+                          uint32_t freq_permille, uint32_t iupac, uint32_t width, uint8_t* out, uint64_t out_bytes) {
+  MG_REQUIRE_READY();
+  if (!h || (nrows && !rows) || (out_bytes && !out)) return fail(MG_ERR_ARG, "null argument");
+  if (min_depth < 2 || min_count < 1 || freq_permille > 500)
+    return fail(MG_ERR_ARG, "min_depth %u (at least 2), min_count %u (at least 1), freq_permille %u (at most 500)", min_depth, min_count,
+                freq_permille);
+  if (width < 1 || width > 65535) return fail(MG_ERR_ARG, "width %u (1 to 65535)", width);
+  if (iupac > 1) return fail(MG_ERR_ARG, "iupac %u (0 or 1)", iupac);
+  std::vector<uint64_t> toff(nrows + 1ull, 0);
+  for (uint32_t r = 0; r < nrows; ++r) {
+    if (rows[r] >= h->nacc) return fail(MG_ERR_ARG, "row %u: accession row %u (below %u)", r, rows[r], h->nacc);
+    toff[r + 1] = toff[r] + mgvar::text_bytes(h->h_len[rows[r]], width);  // (a length is below 2^48: the check below keeps the sum in 64 bits)
+    if (toff[r + 1] >> 62) return fail(MG_ERR_ARG, "rows 0 to %u: %llu bytes of text, too many for one call", r, (unsigned long long)toff[r + 1]);
+  }
+  const uint64_t total = toff[nrows];
+  if (out_bytes != total)
+    return fail(MG_ERR_ARG, "out_bytes %llu: the texts of these rows are %llu bytes", (unsigned long long)out_bytes, (unsigned long long)total);
+  if (total == 0) return MG_OK;
+  hipStream_t st = ctx().stream;
+  DevBuf text, meta;  // u8[total rounded up to a word]; the offsets u64[nrows + 1], then the rows u32[nrows]
+  const uint64_t off_bytes = (nrows + 1ull) * sizeof(uint64_t);
+  if (text.alloc((total + 3) / 4 * 4) != MG_OK)
+    return fail(MG_ERR_NOMEM, "the consensus text (%llu bytes) does not fit on the device: ask for fewer rows", (unsigned long long)total);
+  MG_TRY(meta.alloc(off_bytes + (uint64_t)nrows * sizeof(uint32_t)));
+  uint32_t* d_rows = reinterpret_cast<uint32_t*>(meta.as<uint8_t>() + off_bytes);
+  MG_HIP(hipMemcpyAsync(meta.p, toff.data(), off_bytes, hipMemcpyHostToDevice, st));
+  MG_HIP(hipMemcpyAsync(d_rows, rows, (uint64_t)nrows * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  const uint64_t nsteps = (total + kTextStep - 1) / kTextStep;
+  {
+    ProfScope ps("var_consensus");
+    hipLaunchKernelGGL(k_var_consensus, dim3(var_grid(nsteps, kBlock / 64)), dim3(kBlock), 0, st, h->cnt, h->off.as<uint64_t>(),
+                       h->len.as<uint64_t>(), meta.as<uint64_t>(), d_rows, nrows, total, nsteps, min_depth, min_count, freq_permille, iupac,
+                       width, text.as<uint32_t>());
+    MG_HIP(hipGetLastError());
+  }
+  MG_HIP(hipMemcpyAsync(out, text.p, total, hipMemcpyDeviceToHost, st));
+  MG_HIP(hipStreamSynchronize(st));  // (toff and the caller's rows are free from here)
   return MG_OK;
 }
 

@@ -16,6 +16,9 @@
 //   NibblePacker     a sink that packs codes two per byte, the low nibble first; flush() writes a last odd code with a 0 above it
 //   site_of()        one site's four counts against (D, C, F): its depth, whether it is callable, its major allele (ties to the
 //                    lowest code), the mask of its variant alleles, d (d - 1) and d (d - 1) - sum n_i (n_i - 1)
+//   consensus_char() one site's character in the consensus sequence (--consensus; metalign_amd/consensus.py), over site_of()
+//   text_bytes()     the bytes of a sequence as text of lines of `width` bases; text_at(): the inverse layout map, which byte of the
+//                    text is a newline and which site every other byte shows; 64-bit throughout
 //
 // Written so that the SAME code compiles for the host (tests/host_variants_check.cpp) and for gfx950.  Memory is reached through an
 // accessor (`m[i]` = byte i).  No byte at or behind the end of a line or record is read.
@@ -178,6 +181,56 @@ MGV_HD Site site_of(const uint32_t n[4], uint32_t min_depth, uint32_t min_count,
   s.discordant = s.pairs - same;
   s.polymorphic = s.variants != 0;
   return s;
+}
+
+// ---- the consensus text (--consensus; metalign_amd/consensus.py is the definition) --------------------------------------------
+
+constexpr uint64_t pack8(const char* s) {
+  uint64_t v = 0;
+  for (int i = 0; i < 8; ++i) v |= (uint64_t)(uint8_t)s[i] << (8 * i);
+  return v;
+}
+
+// "-ACMGRSVTWYHKDBN"[mask], bits A = 1, C = 2, G = 4, T = 8 (two 64-bit constants: no table in memory)
+MGV_HD uint8_t iupac_of(uint32_t mask) {
+  constexpr uint64_t lo = pack8("-ACMGRSV"), hi = pack8("TWYHKDBN");
+  return (uint8_t)(((mask & 8u) ? hi : lo) >> (8u * (mask & 7u)));
+}
+
+// One site's character: N below min_depth; else the major allele's letter, or (iupac) the code of the major and the variant alleles.
+MGV_HD uint8_t consensus_char(const uint32_t n[4], uint32_t min_depth, uint32_t min_count, uint32_t permille, bool iupac) {
+  const Site s = site_of(n, min_depth, min_count, permille);
+  if (!s.callable_) return 'N';
+  return iupac_of((1u << s.major) | (iupac ? s.variants : 0u));
+}
+
+// The bytes of a sequence of L bases as text: a newline behind every `width` bases and behind the last one (width >= 1).
+MGV_HD uint64_t text_bytes(uint64_t L, uint32_t width) { return L + (L + width - 1) / width; }
+
+struct TextAt {
+  bool newline;
+  uint64_t site;  // (of a byte that is no newline)
+};
+// Byte i of a text of lines of `width` bases: the newline that closes a full line, or the site it shows.  (A 32-bit division
+// where i allows it: the 64-bit one is a long loop on the device.)
+MGV_HD TextAt text_at(uint64_t i, uint32_t width) {
+  const uint64_t w1 = (uint64_t)width + 1;
+  uint64_t line, col;
+  if ((i >> 32) == 0) {
+    line = (uint32_t)i / (uint32_t)w1;
+    col = (uint32_t)i % (uint32_t)w1;
+  } else {
+    line = i / w1;
+    col = i % w1;
+  }
+  return TextAt{col == width, line * width + col};
+}
+// ... of the text of a sequence of L bases, i < text_bytes(L, width): the newline behind a short last line stands where site L
+// would.  The inverse of the layout: site s is byte s + s / width.
+MGV_HD TextAt text_at(uint64_t i, uint32_t width, uint64_t L) {
+  TextAt t = text_at(i, width);
+  t.newline = t.newline || t.site >= L;
+  return t;
 }
 
 }  // namespace mgvar

@@ -2,7 +2,8 @@
 
 A family (COVERAGE, DEPTH, IDENTITY, VARIANTS) is a descriptor: its flags, the side array of a batch it reads, its refusals, its header,
 what it holds on the device, and how its device accumulator is opened and turned into the file's block.  ASSIGNMENTS
-(--read_assignments) shares only the flag test, the refusal and the header: its rows come from stage C itself.
+(--read_assignments) shares only the flag test, the refusal and the header: its rows come from stage C itself.  --consensus
+(metalign_amd/consensus.py) is no family of its own: it reads VARIANTS' accumulator and opens it by itself too.
 
 SideOutputs is the families wanted for ONE input file.  map_and_profile opens it, feeds it the records and closes it; the
 order is always coverage, depth, identity, variants, and whatever was opened is freed on every way out.
@@ -16,7 +17,7 @@ import sys
 
 import numpy as np
 
-from . import _hip, assignments, coverage, depth, identity, side_reads, variants
+from . import _hip, assignments, consensus, coverage, depth, identity, side_reads, variants
 
 
 def _flag(args, name):
@@ -48,6 +49,10 @@ class _Flags:
 
     def wanted(self, args):
         return any(_flag(args, f) for f in self.flags)
+
+    def refusal(self, args, what):
+        """The exit text for more than one process (what = 'world') or a PAF input ('paf'); None: not refused."""
+        return getattr(self, 'refuse_' + what)
 
 
 class _Assignments(_Flags):
@@ -206,16 +211,36 @@ class _Identity(_Family):
 
 
 class _Variants(_Family):
-    """--variants or --variant_sites: either one asks for the per-site allele counts."""
+    """--variants or --variant_sites: either one asks for the per-site allele counts.  --consensus (metalign_amd/consensus.py) reads
+    the same accumulator and opens it by itself too: it is no member of `flags` — the files with a `#reads` line, the refusal texts —
+    but of wanted()."""
     flags, side = ('variants', 'variant_sites'), 'bases'
     refuse_world = 'Error: --variants and --variant_sites run in one process on one GPU; start it without torch.distributed.run.'
     refuse_paf = 'Error: --variants and --variant_sites need SAM or BAM alignments: a PAF line has no CIGAR and SEQ columns.'
+    refuse_world_consensus = 'Error: --consensus runs in one process on one GPU; start it without torch.distributed.run.'
+    refuse_paf_consensus = 'Error: --consensus needs SAM or BAM alignments: a PAF line has no CIGAR and SEQ columns.'
     nomem = 'Error: --variants keeps sixteen bytes per reference base on the GPU; %d MB for this database do not fit.'
+
+    def wanted(self, args):
+        return _Family.wanted(self, args) or _flag(args, 'consensus')
+
+    def refusal(self, args, what):
+        """--consensus as the family's only flag is refused under its own name."""
+        return getattr(self, 'refuse_' + what + ('' if _Family.wanted(self, args) else '_consensus'))
 
     @staticmethod
     def params(args):
         return variants.params(getattr(args, 'variant_min_depth', 5), getattr(args, 'variant_min_count', 2),
                                getattr(args, 'variant_min_freq', 0.05))
+
+    @staticmethod
+    def min_called(args):
+        """--consensus_min_called in parts per thousand; ValueError out of range."""
+        return consensus.min_called_permille(getattr(args, 'consensus_min_called', 0.0))
+
+    @staticmethod
+    def iupac(args):
+        return getattr(args, 'consensus_ambiguity', 'major') == 'iupac'
 
     def write_header(self, args):
         p = self.params(args)
@@ -223,11 +248,17 @@ class _Variants(_Family):
             variants.write_variants(args.variants, p)
         if _flag(args, 'variant_sites'):
             variants.write_sites(args.variant_sites, p)
+        if _flag(args, 'consensus'):
+            consensus.write_consensus(args.consensus)  # (an empty file: FASTA has no comment lines)
 
     def device_bytes(self, args, lengths, nacc, nrec):
         """16 B per reference base and five sums per accession; per record a 16 B entry (and as much again where a collation
-        permutes them) and the pool's 4-bit codes — 75 B for a 150-base read, reckoned as 80 B with the entry."""
-        return 16 * sum(lengths.values()) + 40 * nacc + 16 * nrec + 80 * nrec
+        permutes them) and the pool's 4-bit codes — 75 B for a 150-base read, reckoned as 80 B with the entry.  --consensus: a slab
+        of text."""
+        need = 16 * sum(lengths.values()) + 40 * nacc + 16 * nrec + 80 * nrec
+        if _flag(args, 'consensus'):
+            need += min(consensus.SLAB_BYTES, sum(consensus.text_bytes(n) for n in lengths.values()))
+        return need
 
     def nomem_mb(self, args, lengths, acc_index):
         return self.device_bytes(args, lengths, len(acc_index), 0) >> 20
@@ -240,8 +271,12 @@ class _Variants(_Family):
         p = self.params(args)
         try:
             aln, call, poly, pairs, disc, unpiled, sites = dev.result(*p)
+            if _flag(args, 'consensus'):
+                self.write_consensus_from(args, source, lengths, dev, acc_index, acc2info, aln, call, poly)
         finally:
             dev.free()
+        if not _Family.wanted(self, args):
+            return
         names = {i: a for a, i in acc_index.items()}
         per = {a: [int(aln[i]), int(call[i]), int(poly[i]), int(pairs[i]), int(disc[i])] for a, i in acc_index.items() if aln[i]}
         # (the device orders the sites by accession row; the file by db_info's order, which is the rows' where db_info has no
@@ -251,6 +286,35 @@ class _Variants(_Family):
                       key=lambda s: (order[s[0]], s[1]))
         self.append(args, source, variants.Variants(lengths, per, rows, unpiled), acc2info, taxid2info)
 
+    def write_consensus_from(self, args, source, lengths, dev, acc_index, acc2info, aln, call, poly):
+        """--consensus from the open accumulator: the accessions that are written, in db_info order; their text fetched in slabs of
+        consecutive rows of up to consensus.SLAB_BYTES (half the rows again, down to one, where the device has no room for a slab),
+        every record's header and its slice of the slab straight to the file."""
+        p, M, iupac = self.params(args), self.min_called(args), self.iupac(args)
+        unique, label = reads_mode(args) == 'unique', source_label(args, source)
+        accs = [a for a in acc2info if aln[acc_index[a]] and consensus.written(lengths[a], int(call[acc_index[a]]), M)]
+        sizes = [consensus.text_bytes(lengths[a]) for a in accs]
+        todo = consensus.slabs(sizes)
+        with open(args.consensus, 'ab') as out:
+            while todo:
+                first, end = todo.pop(0)
+                try:
+                    text = dev.consensus([acc_index[a] for a in accs[first:end]], p.min_depth, p.min_count, p.permille, iupac,
+                                         consensus.LINE_WIDTH)
+                except _hip.HipError as e:
+                    if e.code != _hip.ERR_NOMEM or end - first < 2:
+                        raise
+                    mid = (first + end) // 2
+                    todo[:0] = [(first, mid), (mid, end)]
+                    continue
+                at = 0
+                for a, size in zip(accs[first:end], sizes[first:end]):
+                    i = acc_index[a]
+                    out.write(consensus.header_line(a, acc2info[a][1], lengths[a], int(aln[i]), int(call[i]), int(poly[i]), p, iupac,
+                                                    unique, label).encode('utf-8'))
+                    out.write(text[at:at + size])
+                    at += size
+
     def append(self, args, source, var, acc2info, taxid2info):
         p, source = self.params(args), source_label(args, source)
         if _flag(args, 'variants'):
@@ -259,7 +323,16 @@ class _Variants(_Family):
             variants.write_sites(args.variant_sites, p, var.sites, source=source, append=True)
 
     def append_from_definition(self, args, path, lines, acc2info, taxid2info):
-        self.append(args, path, variants.variants(lines, acc2info, args.pct_id, self.params(args)), acc2info, taxid2info)
+        if not _flag(args, 'consensus'):
+            self.append(args, path, variants.variants(lines, acc2info, args.pct_id, self.params(args)), acc2info, taxid2info)
+            return
+        # (one pass over the lines, which come as an iterator: variants.variants and consensus.consensus are these two over them)
+        p, iupac, order = self.params(args), self.iupac(args), list(acc2info)
+        n, aln, unpiled, lengths = variants.counts_of_lines(lines, acc2info, args.pct_id)
+        if _Family.wanted(self, args):
+            self.append(args, path, variants.summarise(n, aln, unpiled, lengths, order, p), acc2info, taxid2info)
+        recs = consensus.records_of(n, aln, unpiled, lengths, order, acc2info, p, iupac, getattr(args, 'consensus_min_called', 0.0))
+        consensus.write_consensus(args.consensus, recs, True, p, iupac, reads_mode(args) == 'unique', source_label(args, path))
 
 
 ASSIGNMENTS, COVERAGE, DEPTH, IDENTITY, VARIANTS = _Assignments(), _Coverage(), _Depth(), _Identity(), _Variants()
@@ -274,13 +347,14 @@ def check_flags(args):
         if not fam.wanted(args):
             continue
         if world > 1:
-            sys.exit(fam.refuse_world)
-        if paf and fam.refuse_paf:
-            sys.exit(fam.refuse_paf)
+            sys.exit(fam.refusal(args, 'world'))
+        if paf and fam.refusal(args, 'paf'):
+            sys.exit(fam.refusal(args, 'paf'))
     if int(getattr(args, 'depth_window_size', 1000)) < 1:
         sys.exit('Error: --depth_window_size must be at least 1.')
     try:
         VARIANTS.params(args)
+        VARIANTS.min_called(args)
     except ValueError as e:
         sys.exit('Error: %s' % e)
     if reads_mode(args) == 'unique' and not any(fam.wanted(args) for fam in FAMILIES):

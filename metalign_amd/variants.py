@@ -169,9 +169,8 @@ def summarise(n, aln, unpiled, lengths, order, p):
     return Variants(lengths, per, sites, unpiled)
 
 
-def variants(lines, acc2info, pct_id, p=None):
-    """SAM lines (str or bytes; the header among them) -> Variants."""
-    p = p or params()
+def counts_of_lines(lines, acc2info, pct_id):
+    """SAM lines (str or bytes; the header among them) -> accumulate()'s three and the lengths."""
     header, piles, leading = [], [], True
     for line in lines:
         if leading:
@@ -188,8 +187,13 @@ def variants(lines, acc2info, pct_id, p=None):
             continue
         piles.append((f[2],) + bases_of(f))
     lengths = lengths_of(header, acc2info)
-    n, aln, unpiled = accumulate(piles, lengths)
-    return summarise(n, aln, unpiled, lengths, list(acc2info), p)
+    return accumulate(piles, lengths) + (lengths,)
+
+
+def variants(lines, acc2info, pct_id, p=None):
+    """SAM lines (str or bytes; the header among them) -> Variants."""
+    n, aln, unpiled, lengths = counts_of_lines(lines, acc2info, pct_id)
+    return summarise(n, aln, unpiled, lengths, list(acc2info), p or params())
 
 
 def counts_of_records(recs, entries, pool, accessions, lengths, pct_id):
