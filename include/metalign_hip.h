@@ -1092,6 +1092,48 @@ int mg_variants_consensus(mg_variants* h, const uint32_t* rows, uint32_t nrows, 
                           uint32_t freq_permille, uint32_t iupac, uint32_t width, uint8_t* out, uint64_t out_bytes);
 void mg_variants_free(mg_variants* h);
 
+/* THE REFERENCE BASES PER ACCESSION ROW (--ani, --vcf; metalign_amd/csrc/mg_refseq.hip; the definition is metalign_amd/refseq.py).
+ * parse_dev: d_text[nbytes] = a FASTA file's text in HBM (device pointer; it need only be readable up to the next 16-byte boundary
+ *   on both sides, the contract of mg_genomes_parse_dev) -> one code byte per site (A a 0, C c 1, G g 2, T t 3, every other byte
+ *   4) of the accession rows of ix, row a at the site offset mg_variants_create derives from the same lengths.  The text is split
+ *   at '\n' (a last line needs none); a line whose first byte is '>' opens a record, named by the bytes behind the '>' up to the
+ *   first space, tab, \r, \v or \f; lines in front of the first header are dropped; every other line is stripped of those five
+ *   bytes at both ends and appended to the open record.  A record is LOADED when its name is a row of ix and it has exactly
+ *   lengths[row] bases; foreign when its name is no row (an empty name is none); mismatched when the row has another length (the
+ *   row stays without a reference); duplicate when an earlier record of the text loaded or mismatched its row — the first record
+ *   wins, whatever the grid.  nacc must be ix's number of rows (else MG_ERR_ARG); nbytes = 0, nacc = 0 and lengths of 0 are legal
+ *   (a row of length 0 is loaded by a record without bases).  MG_ERR_NOMEM (the byte count in the message) when the codes or the
+ *   line index do not fit; MG_ERR_ARG for a line of 2^32 bases or more.  Synchronises; d_text is the caller's and free on return.
+ * stats: out5 = records, loaded, foreign, mismatched, duplicate (records is the sum of the other four).
+ * loaded: u8[nacc], 1 for a row with a reference.
+ * download: u8[sum of the lengths], the rows' codes back to back; 0xff throughout a row that is not loaded, which the parse never
+ *   writes and mg_variants_diff never reads. */
+typedef struct mg_refseq mg_refseq;
+int mg_refseq_parse_dev(const uint8_t* d_text, uint64_t nbytes, const mg_acc_index* ix, const uint64_t* lengths, uint32_t nacc,
+                        mg_refseq** out);
+int mg_refseq_stats(const mg_refseq* h, uint64_t out5[5]);
+int mg_refseq_loaded(const mg_refseq* h, uint8_t* loaded);
+int mg_refseq_download(const mg_refseq* h, uint8_t* codes);
+void mg_refseq_free(mg_refseq* h);
+
+/* THE PILEUP AGAINST THE REFERENCE (--ani, --vcf; mg_variants.hip; the definition is metalign_amd/refdiff.py), over an open
+ * mg_variants and the reference parsed for the same nacc and lengths (else MG_ERR_ARG).
+ * diff: every site of an accession with an alignment and a loaded reference, judged as finish judges it and against its reference
+ *   code r: compared (callable and r < 4), con_subs (compared and the major allele is not r), pop_subs (compared and r is neither
+ *   the major nor a variant allele), ref_other (callable and r = 4): u64[nacc] each; *nsites = the sites with a present allele
+ *   other than r, which it keeps for fetch_diffs.  Thresholds as finish (else MG_ERR_ARG).  Reads the counts only: it needs no
+ *   finish and leaves what a finish kept; may be called again.  Synchronises.
+ * fetch_diffs: out[nsites] of the last diff, ordered by (accession row, pos0); ref = the reference code.  MG_ERR_STATE before a diff. */
+typedef struct mg_variant_diff {
+  uint32_t acc;  /* accession row */
+  uint32_t pos0; /* 0-based position */
+  uint32_t n[4]; /* the reads' A, C, G, T */
+  uint32_t ref;  /* the reference code, 0 .. 3 */
+} mg_variant_diff;
+int mg_variants_diff(mg_variants* h, const mg_refseq* ref, uint32_t min_depth, uint32_t min_count, uint32_t freq_permille,
+                     uint64_t* compared, uint64_t* con_subs, uint64_t* pop_subs, uint64_t* ref_other, uint64_t* nsites);
+int mg_variants_fetch_diffs(mg_variants* h, mg_variant_diff* out);
+
 /* SIDE OUTPUTS FROM UNIQUELY ASSIGNED READS (--side_reads unique; metalign_amd/csrc/mg_sidemask.hip; the definition is
  * metalign_amd/side_reads.py: unique_mask_of_records).
  * d_out[i] = d_recs[i] for i < n, with FLAG bit 2048 set in flag_len where the record is masked: the bit by which the three

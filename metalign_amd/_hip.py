@@ -54,7 +54,8 @@ EXPORTS = [
     "mg_identity_create", "mg_identity_add_dev", "mg_identity_result", "mg_identity_fetch_hist", "mg_identity_free",
     "mg_sam_batch_bases_download", "mg_sam_batch_bases_device_ptr",
     "mg_variants_create", "mg_variants_add_dev", "mg_variants_finish", "mg_variants_fetch_sites", "mg_variants_consensus",
-    "mg_variants_free",
+    "mg_variants_free", "mg_variants_diff", "mg_variants_fetch_diffs",
+    "mg_refseq_parse_dev", "mg_refseq_stats", "mg_refseq_loaded", "mg_refseq_download", "mg_refseq_free",
     "mg_records_mask_unique_dev",
     "mg_gunzip_open", "mg_gunzip_read", "mg_gunzip_close", "mg_zcat_files", "mg_stream_thin_file",
     "mg_inflate_dev", "mg_inflated_bytes", "mg_inflated_download", "mg_inflated_free", "mg_inflate_config", "mg_inflate_stats",
@@ -96,6 +97,8 @@ BASES_DTYPE = np.dtype([("off", np.uint64), ("pos0", np.uint32), ("span", np.uin
 MAX_PILE_SPAN = (1 << 21) - 1
 # a polymorphic site of a VariantsAcc (mg_variant_site)
 VARIANT_SITE_DTYPE = np.dtype([("acc", np.uint32), ("pos0", np.uint32), ("n", np.uint32, (4,))])
+# a site where the sample differs from the reference (mg_variant_diff); ref: the reference code
+VARIANT_DIFF_DTYPE = np.dtype([("acc", np.uint32), ("pos0", np.uint32), ("n", np.uint32, (4,)), ("ref", np.uint32)])
 # a kept window of a Depth (mg_depth_window) and the histogram's bins (depth clamped to DEPTH_BINS - 1)
 DEPTH_WINDOW_DTYPE = np.dtype([("index", np.uint64), ("depth_sum", np.uint64), ("acc", np.uint32), ("covered", np.uint32)])
 DEPTH_BINS = 4096
@@ -153,6 +156,7 @@ def load_library(path=LIB_PATH):
     lib.mg_depth_free.restype = None
     lib.mg_identity_free.restype = None
     lib.mg_variants_free.restype = None
+    lib.mg_refseq_free.restype = None
     lib.mg_variants_consensus.argtypes = [_vp, _u32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                           ctypes.c_uint32, _u8p, ctypes.c_uint64]
     lib.mg_shutdown.restype = None
@@ -1341,6 +1345,19 @@ class VariantsAcc(_SideAccumulator):
         r = self.finish(min_depth, min_count, permille)
         return r[:6] + (self.fetch_sites(),)
 
+    def diff(self, ref, min_depth, min_count, permille):
+        """The pileup against a RefSeq (mg_variants_diff, mg_variants_fetch_diffs; metalign_amd/refdiff.py is the definition) ->
+        (compared, con_subs, pop_subs, ref_other) uint64[nacc] each and VARIANT_DIFF_DTYPE[]: the sites with a present allele other
+        than the reference's, ordered by (accession row, pos0).  Reads the counts only: before or after a finish()."""
+        out = [np.zeros(max(self.nacc, 1), dtype=np.uint64) for _ in range(4)]
+        nsites = ctypes.c_uint64(0)
+        self.hip._chk(self.hip.lib.mg_variants_diff(self.handle, ref.handle, ctypes.c_uint32(int(min_depth)), ctypes.c_uint32(int(min_count)),
+                                                    ctypes.c_uint32(int(permille)), *[_np(a, ctypes.c_uint64) for a in out],
+                                                    ctypes.byref(nsites)))
+        sites = np.zeros(int(nsites.value) + 1, dtype=VARIANT_DIFF_DTYPE)
+        self.hip._chk(self.hip.lib.mg_variants_fetch_diffs(self.handle, _vp(sites.ctypes.data)))
+        return tuple(a[:self.nacc] for a in out) + (sites[:int(nsites.value)],)
+
     def text_bytes(self, rows, width=60):
         """The bytes of these accession rows' consensus texts, back to back: per row L + ceil(L / width)."""
         rows = np.ascontiguousarray(rows, dtype=np.int64)
@@ -1364,6 +1381,47 @@ class VariantsAcc(_SideAccumulator):
         out = np.empty(max(nbytes, 1), dtype=np.uint8)
         self.consensus_into(rows, min_depth, min_count, permille, iupac, width, out, nbytes)
         return out[:nbytes].tobytes()
+
+
+class RefSeq:
+    """The reference bases of the accession rows on the device, one code byte per site (mg_refseq_*; metalign_amd/refseq.py is the
+    definition): what VariantsAcc.diff compares the pileup with.  Made by Hip.refseq_from_file or Hip.refseq_parse."""
+
+    def __init__(self, hip, handle, lengths):
+        self.hip, self.handle = hip, handle
+        self.lengths = np.ascontiguousarray(lengths, dtype=np.uint64).copy()
+        self.nacc = int(self.lengths.size)
+
+    def stats(self):
+        """-> refseq.Counters: records, loaded, foreign, mismatched, duplicate."""
+        from .refseq import Counters
+        out = np.zeros(5, dtype=np.uint64)
+        self.hip._chk(self.hip.lib.mg_refseq_stats(self.handle, _np(out, ctypes.c_uint64)))
+        return Counters(*(int(x) for x in out))
+
+    def loaded(self):
+        """-> uint8[nacc]: 1 for a row with a reference."""
+        out = np.zeros(max(self.nacc, 1), dtype=np.uint8)
+        self.hip._chk(self.hip.lib.mg_refseq_loaded(self.handle, _np(out, ctypes.c_uint8)))
+        return out[:self.nacc]
+
+    def download(self):
+        """-> bytes: the rows' codes back to back, 0xff throughout a row that is not loaded."""
+        n = int(self.lengths.sum())
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        self.hip._chk(self.hip.lib.mg_refseq_download(self.handle, _np(out, ctypes.c_uint8)))
+        return out[:n].tobytes()
+
+    def free(self):
+        if self.handle:
+            self.hip.lib.mg_refseq_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:  # noqa: BLE001
+            pass
 
 
 class Depth(_SideAccumulator):
@@ -1522,6 +1580,33 @@ class Hip:
     def variants(self, lengths):
         """A VariantsAcc over accessions of these lengths (mg_variants_create)."""
         return VariantsAcc(self, lengths)
+
+    def refseq_parse(self, d_text, nbytes, acc_index, lengths):
+        """FASTA text at a device pointer -> a RefSeq over the rows of acc_index (an AccIndex) and these lengths
+        (mg_refseq_parse_dev).  The text is the caller's and free on return."""
+        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
+        h = _vp()
+        self._chk(self.lib.mg_refseq_parse_dev(_vp(d_text), ctypes.c_uint64(int(nbytes)), acc_index.handle,
+                                               _np(ln if ln.size else np.zeros(1, np.uint64), ctypes.c_uint64), ctypes.c_uint32(ln.size),
+                                               ctypes.byref(h)))
+        return RefSeq(self, h, ln)
+
+    def refseq_from_file(self, path, acc_index, lengths):
+        """A reference FASTA file -> a RefSeq.  A plain file goes up as it is (upload_file); a gzip / BGZF file (by its magic) goes
+        through inflate(), so its compressed bytes cross the link and the device decodes them.  The text is never split into lines
+        or records on the host."""
+        with open(path, "rb") as f:
+            gz = f.read(2) == b"\x1f\x8b"
+        if gz:
+            with open(path, "rb") as f:
+                text = np.frombuffer(self.inflate(f.read()), dtype=np.uint8)
+            dev, size = self.array(text if text.size else np.zeros(1, np.uint8)), int(text.size)
+        else:
+            dev, size = self.upload_file(path)
+        try:
+            return self.refseq_parse(dev.ptr, size, acc_index, lengths)
+        finally:
+            dev.free()
 
     def depth(self, lengths, window=0):
         """A Depth over accessions of these lengths, with windows of `window` bases (mg_depth_create)."""

@@ -85,6 +85,16 @@ _OPTIONS = {
                                      'code of the major and the variant alleles (--variant_min_count, --variant_min_freq).'),
     'consensus_min_called': dict(type=float, default=0.0, help='Write an accession to --consensus only when at least this share of '
                                  'its bases is callable (default 0.0, within 0 to 1; compared in parts per thousand).'),
+    'ani': dict(default='NONE', help='Also write the consensus and population ANI of every detected accession to its reference '
+                'sequence here (TSV): per accession (S rows) and per genome (G rows) the callable sites compared with a reference '
+                'A / C / G / T, the substitutions of the consensus (the major allele differs) and of the population (the reference '
+                'base is no allele of the sample), conANI and popANI (metalign_amd/refdiff.py is the definition). Needs the '
+                'reference FASTA (--reference). SAM / BAM input, one process only.'),
+    'vcf': dict(default='NONE', help='Also write every site where the sample differs from the reference here (VCFv4.2): REF, the '
+                'alleles of the sample that are not REF as ALT, DP, AD and AF. One input file only. Needs the reference FASTA '
+                '(--reference).'),
+    'reference': dict(default='AUTO', help='The FASTA (optionally .gz) the reads were aligned to, for --ani and --vcf (default: '
+                      'the database FASTA the aligner gets, --db).'),
     'side_reads': dict(default='all', choices=['all', 'unique'],
                        help='Which alignments --coverage, --depth, --depth_windows and --identity count: "all" that pass --pct_id (the '
                             'default), or "unique": only those of reads the profile assigned uniquely, on an accession of the taxon '
@@ -112,7 +122,7 @@ _TOOLS = {
                  'sketch_table', 'min_count', 'sketch_size', 'kmer_match', 'device_multimap', 'collate', 'read_assignments', 'coverage',
                  'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size', 'identity', 'side_reads',
                  'variants', 'variant_sites', 'variant_min_depth', 'variant_min_count', 'variant_min_freq',
-                 'consensus', 'consensus_ambiguity', 'consensus_min_called']),
+                 'consensus', 'consensus_ambiguity', 'consensus_min_called', 'ani', 'vcf', 'reference']),
     'select_db': dict(
         description='Run CMash and select a subset of the whole database to align to.',
         positionals=[('reads', dict(help='Reads file (FASTA / FASTQ, optionally .gz, or a BAM of reads).')),
@@ -130,7 +140,7 @@ _TOOLS = {
                  'verbose', 'device_multimap', 'collate', 'read_assignments', 'coverage',
                  'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size', 'identity', 'side_reads',
                  'variants', 'variant_sites', 'variant_min_depth', 'variant_min_count', 'variant_min_freq',
-                 'consensus', 'consensus_ambiguity', 'consensus_min_called']),
+                 'consensus', 'consensus_ambiguity', 'consensus_min_called', 'ani', 'vcf', 'reference']),
 }
 
 

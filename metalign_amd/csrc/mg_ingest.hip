@@ -21,6 +21,7 @@
 #include "mg_identity_core.h"
 #include "mg_variants_core.h"
 #include "mg_internal.h"
+#include "mg_acc_dev.h"
 
 namespace mg {
 
@@ -250,37 +251,7 @@ __device__ __forceinline__ uint64_t scan_to_ws(const uint8_t* __restrict__ text,
   return p;
 }
 
-__device__ __forceinline__ uint64_t fnv1a(const uint8_t* p, uint32_t n) {
-  uint64_t h = 0xcbf29ce484222325ull;
-  for (uint32_t i = 0; i < n; ++i) { h ^= p[i]; h *= 0x100000001b3ull; }
-  return h;
-}
-
-struct AccTable {
-  const uint64_t* slot_hash;   // 0 = empty
-  const uint32_t* slot_row;
-  uint64_t mask;               // slots - 1
-  const uint8_t* names;        // concatenated accession strings
-  const uint64_t* name_off;    // [nacc + 1]
-};
-
-__device__ __forceinline__ int64_t acc_lookup(const AccTable& t, const uint8_t* s, uint32_t n) {
-  uint64_t h = fnv1a(s, n);
-  if (h == 0) h = 1;
-  for (uint64_t p = h & t.mask;; p = (p + 1) & t.mask) {
-    const uint64_t sh = t.slot_hash[p];
-    if (sh == 0) return -1;
-    if (sh == h) {
-      const uint32_t row = t.slot_row[p];
-      const uint64_t b = t.name_off[row], e = t.name_off[row + 1];
-      if (e - b == n) {
-        bool same = true;
-        for (uint32_t i = 0; i < n && same; ++i) same = t.names[b + i] == s[i];
-        if (same) return row;
-      }
-    }
-  }
-}
+// (fnv1a, AccTable, acc_lookup: mg_acc_dev.h, shared with mg_refseq.hip)
 
 // One thread per line: everything except the new-read bit.  err: [0] = first failing line (atomicMin),
 // kinds[line] holds the failure kind for the host to look up.
@@ -718,8 +689,8 @@ __global__ __launch_bounds__(256) void k_bam_bases_pack(const uint8_t* __restric
 // line is terminated virtually.  -> d_line_end (scratch "ing_lines"), *nlines.
 // last_end (optional): the end of the last line, brought back in the same round trip as the marks' completion (a piece of a
 // stream is consumed up to there).  Two host synchronisations per call: the count, then the marks.
-static int build_line_index(const uint8_t* d_text, uint64_t nbytes, uint64_t** d_line_end, uint64_t* nlines,
-                            bool* virtual_last, bool allow_virtual = true, uint64_t* last_end = nullptr) {
+int build_line_index(const uint8_t* d_text, uint64_t nbytes, uint64_t** d_line_end, uint64_t* nlines, bool* virtual_last,
+                     bool allow_virtual, uint64_t* last_end) {
   Context& c = ctx();
   hipStream_t st = c.stream;
   *nlines = 0;
@@ -1061,8 +1032,7 @@ int mg::aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg
   }
   MG_HIP(hipMemsetAsync(d_err, 0xff, sizeof(unsigned long long), st));
   if (plen) MG_HIP(hipMemcpyAsync(d_prev, prev_qname, plen, hipMemcpyHostToDevice, st));
-  AccTable at{ix->slot_hash.as<uint64_t>(), ix->slot_row.as<uint32_t>(), ix->slots - 1, ix->names.as<uint8_t>(),
-              ix->name_off.as<uint64_t>()};
+  const AccTable at = acc_table_of(ix);
   uint64_t nret = 0;
   {
     ProfScope ps("ingest_sam");

@@ -343,7 +343,19 @@ struct mg_acc_index {
   uint32_t nacc = 0;
 };
 
-#define MG_THIN_MARK 0x01  // first byte of a SEQ field the file reader replaced by its length (never whitespace, never a base)
+// The reference bases of the accession rows (mg_refseq.hip): one code per site at the site offsets mg_variants_create derives from
+// the same lengths.  The codes of a row that is not loaded are never written and never read.
+struct mg_refseq {
+  uint8_t* codes = nullptr;  // u8[nsites + 16] (its own allocation, as the allele counts)
+  mg::DevBuf loaded;         // u8[nacc]
+  uint64_t nsites = 0;
+  uint32_t nacc = 0;
+  uint64_t stats[5] = {0, 0, 0, 0, 0};  // records, loaded, foreign, mismatched, duplicate
+  std::vector<uint64_t> h_len;          // the lengths it was parsed for
+  ~mg_refseq() { if (codes) (void)hipFree(codes); }
+};
+
+#define MG_THIN_MARK 0x01 // first byte of a SEQ field the file reader replaced by its length (never whitespace, never a base)
 
 struct mg_sam_batch {
   mg::DevBuf recs;
@@ -418,6 +430,12 @@ int bam_reads_prefix_dev(const uint8_t* d_bytes, uint64_t nbytes, int32_t n_ref,
 int aln_tokenize_prefix_dev(const uint8_t* d_text, uint64_t nbytes, const mg_acc_index* ix, const char* prev_qname, bool paf,
                             bool final, uint64_t* consumed, mg_sam_batch** out, int* err_kind, uint64_t* err_line, bool thin = false,
                             bool keyed = false, bool named = false, bool placed = false, bool edited = false, bool based = false);
+// mg_ingest.hip: the line index of a text in HBM, which the parsers of reads, alignments and the reference FASTA (mg_refseq.hip)
+// share: *d_line_end (scratch "ing_lines") = the offsets of the '\n', then nbytes where the text's last line lacks one and
+// allow_virtual is set (*virtual_last); *nlines = their number.  d_text need only be readable up to the next 16-byte boundary on
+// both sides.  last_end (optional): the end of the last line.
+int build_line_index(const uint8_t* d_text, uint64_t nbytes, uint64_t** d_line_end, uint64_t* nlines, bool* virtual_last,
+                     bool allow_virtual = true, uint64_t* last_end = nullptr);
 // mg_collate.hip: a keyed batch -> its records regrouped by read (metalign_amd/collate.py is the definition), the keys freed.
 int collate_batch(mg_sam_batch* b, uint64_t* d_perm_or_null);
 }

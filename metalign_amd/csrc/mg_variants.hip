@@ -20,6 +20,9 @@
 //   k_var_sites<true>   the sites: the same walk a second time; a polymorphic site goes to the block's base + the polymorphic sites
 //                       before it in the block (a ballot and mbcnt per 64 sites), so the sites come out ordered by (accession row,
 //                       pos0) whatever the grid.
+//   k_var_diff<...>     the same two passes against the reference code of every site (mg_variants_diff; --ani, --vcf): compared,
+//                       con_subs, pop_subs and ref_other per accession, and the sites where the sample differs from the reference.
+//                       The walk exists once (var_walk): k_var_sites and k_var_diff instantiate it with their pass.
 //   k_var_consensus     the counts of a list of accession rows -> their consensus sequences as text (--consensus;
 //                       metalign_amd/consensus.py is the definition), laid out over OUTPUT bytes: every wavefront takes kTextStep
 //                       bytes of the texts, which lie back to back, finds the row of its first byte in the text offsets
@@ -43,6 +46,12 @@ struct mg_variants {
   DevBuf blk;    // u64[1 + nblocks]: the scan's carry, then the blocks' polymorphic sites / bases
   DevBuf sites;  // mg_variant_site[npoly]
   std::vector<uint64_t> h_len;  // the lengths again, on the host: what mg_variants_consensus sizes the texts by
+  // mg_variants_diff keeps its own: finish's blocks and sites stay as they are
+  DevBuf dsums;   // u64[4 nacc]: compared, con_subs, pop_subs, ref_other
+  DevBuf dblk;    // u64[1 + nblocks]
+  DevBuf dsites;  // mg_variant_diff[ndiff]
+  uint64_t ndiff = 0;
+  bool diffed = false;
   ~mg_variants() { if (cnt) (void)hipFree(cnt); }
 };
 
@@ -109,15 +118,28 @@ __global__ __launch_bounds__(kBlock) void k_var_add(const mg_aln_rec* __restrict
   bins.flush(sums, unpiled);
 }
 
-// Both passes over the sites: kEmit = false sums and counts, kEmit = true writes the polymorphic sites.
-template <bool kEmit>
-__global__ __launch_bounds__(kBlock) void k_var_sites(const uint32_t* __restrict__ cnt, uint64_t nsites, uint64_t nblocks,
-                                                      const uint64_t* __restrict__ off, uint32_t nacc,
-                                                      const unsigned long long* __restrict__ aln, uint32_t min_depth, uint32_t min_count,
-                                                      uint32_t permille, unsigned long long* __restrict__ callable_,
-                                                      unsigned long long* __restrict__ poly, unsigned long long* __restrict__ pairs,
-                                                      unsigned long long* __restrict__ disc, unsigned long long* __restrict__ blk,
-                                                      mg_variant_site* __restrict__ out, uint64_t nout) {
+// Where a flagged site goes among the flagged sites of a walk: `at` + the flagged lanes below this one; `at` moves on by all of
+// them.  (The whole wavefront calls it.)
+__device__ __forceinline__ unsigned long long ballot_slot(bool flag, unsigned long long& at) {
+  const unsigned long long pm = __ballot(flag);
+  const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0u));
+  const unsigned long long o = at + below;
+  at += (unsigned long long)__builtin_popcountll(pm);
+  return o;
+}
+
+// THE walk over the sites, which the passes of finish (SitesPass) and of the comparison with the reference (DiffPass) share: every
+// wavefront takes blocks of kStep sites, finds the accession of its first site in the offsets (mgv::owner_of) and moves on from
+// there (mgv::owner_from); the sites of an accession without an alignment, or which the pass does not take, are stepped over;
+// the others go to the pass 64 at a time, every lane of the wavefront calling site() so that it may ballot.  A pass is
+//   takes(a)                    whether accession a's sites are looked at (beside aln[a] != 0)
+//   open_block(b) / close_block(b)   around a block's sites
+//   open_acc() / close_acc(a)        around the sites of one accession inside a block
+//   site(a, w, in, n4)          site w of accession a (in: w is a site of the run; else n4 is 0 and the lane only takes part)
+template <class Pass>
+__device__ __forceinline__ void var_walk(const uint32_t* __restrict__ cnt, uint64_t nsites, uint64_t nblocks,
+                                         const uint64_t* __restrict__ off, uint32_t nacc, const unsigned long long* __restrict__ aln,
+                                         Pass& pass) {
   const unsigned lane = threadIdx.x & 63u;
   const uint64_t wave = (uint64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
   const uint64_t nwaves = (uint64_t)gridDim.x * (kBlock / 64);
@@ -126,60 +148,172 @@ __global__ __launch_bounds__(kBlock) void k_var_sites(const uint32_t* __restrict
     const uint64_t t0 = b * kStep, t1 = t0 + kStep < nsites ? t0 + kStep : nsites;
     uint32_t a = mgv::owner_of(off, nacc, t0);  // (off[nacc] = nsites > t0)
     uint64_t s = t0;
-    unsigned long long at = kEmit ? blk[b] : 0ull;  // kEmit: where the block's next polymorphic site goes; else: their count
+    pass.open_block(b);
     while (s < t1) {
       const uint64_t e = off[a + 1] < t1 ? off[a + 1] : t1;
-      if (aln[a]) {  // (an accession without an alignment has no count)
-        unsigned long long c_call = 0, c_poly = 0, c_pairs = 0, c_disc = 0;
+      if (aln[a] && pass.takes(a)) {  // (an accession without an alignment has no count)
+        pass.open_acc();
         for (uint64_t w0 = s; w0 < e; w0 += 64) {  // (uniform: every lane takes part in the ballot)
           const uint64_t w = w0 + lane;
-          bool is_poly = false;
           uint32_t n4[4] = {0, 0, 0, 0};
           if (w < e) {
             const uint4 v = cnt4[w];
             n4[0] = v.x; n4[1] = v.y; n4[2] = v.z; n4[3] = v.w;
-            const mgvar::Site st = mgvar::site_of(n4, min_depth, min_count, permille);
-            is_poly = st.polymorphic;
-            if (!kEmit) {
-              c_call += st.callable_ ? 1u : 0u;
-              c_poly += is_poly ? 1u : 0u;
-              c_pairs += st.pairs;
-              c_disc += st.discordant;
-            }
           }
-          if (kEmit) {
-            const unsigned long long pm = __ballot(is_poly);
-            const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0u));
-            const unsigned long long o = at + below;
-            if (is_poly && o < nout) {
-              mg_variant_site vs;
-              vs.acc = a;
-              vs.pos0 = (uint32_t)(w - off[a]);
-              vs.n[0] = n4[0]; vs.n[1] = n4[1]; vs.n[2] = n4[2]; vs.n[3] = n4[3];
-              out[o] = vs;
-            }
-            at += (unsigned long long)__builtin_popcountll(pm);
-          }
+          pass.site(a, w, w < e, n4);
         }
-        if (!kEmit) {
-          c_call = wave_sum(c_call);
-          c_poly = wave_sum(c_poly);
-          c_pairs = wave_sum(c_pairs);
-          c_disc = wave_sum(c_disc);
-          if (lane == 0) {
-            if (c_call) atomicAdd(&callable_[a], c_call);
-            if (c_poly) atomicAdd(&poly[a], c_poly);
-            if (c_pairs) atomicAdd(&pairs[a], c_pairs);
-            if (c_disc) atomicAdd(&disc[a], c_disc);
-          }
-          at += c_poly;
-        }
+        pass.close_acc(a);
       }
       s = e;
       a = mgv::owner_from(off, nacc, a, s);  // (over the accessions without sites)
     }
+    pass.close_block(b);
+  }
+}
+
+// Both passes of finish: kEmit = false sums and counts, kEmit = true writes the polymorphic sites.
+template <bool kEmit> struct SitesPass {
+  uint32_t min_depth, min_count, permille;
+  const uint64_t* off;
+  unsigned long long *callable_, *poly, *pairs, *disc, *blk;
+  mg_variant_site* out;
+  uint64_t nout;
+  unsigned lane;
+  unsigned long long at, c_call, c_poly, c_pairs, c_disc;  // at — kEmit: where the block's next polymorphic site goes; else: their count
+
+  __device__ __forceinline__ bool takes(uint32_t) const { return true; }
+  __device__ __forceinline__ void open_block(uint64_t b) { at = kEmit ? blk[b] : 0ull; }
+  __device__ __forceinline__ void open_acc() { c_call = c_poly = c_pairs = c_disc = 0; }
+  __device__ __forceinline__ void site(uint32_t a, uint64_t w, bool in, const uint32_t n4[4]) {
+    bool is_poly = false;
+    if (in) {
+      const mgvar::Site st = mgvar::site_of(n4, min_depth, min_count, permille);
+      is_poly = st.polymorphic;
+      if (!kEmit) {
+        c_call += st.callable_ ? 1u : 0u;
+        c_poly += is_poly ? 1u : 0u;
+        c_pairs += st.pairs;
+        c_disc += st.discordant;
+      }
+    }
+    if (kEmit) {
+      const unsigned long long o = ballot_slot(is_poly, at);
+      if (is_poly && o < nout) {
+        mg_variant_site vs;
+        vs.acc = a;
+        vs.pos0 = (uint32_t)(w - off[a]);
+        vs.n[0] = n4[0]; vs.n[1] = n4[1]; vs.n[2] = n4[2]; vs.n[3] = n4[3];
+        out[o] = vs;
+      }
+    }
+  }
+  __device__ __forceinline__ void close_acc(uint32_t a) {
+    if (kEmit) return;
+    c_call = wave_sum(c_call);
+    c_poly = wave_sum(c_poly);
+    c_pairs = wave_sum(c_pairs);
+    c_disc = wave_sum(c_disc);
+    if (lane == 0) {
+      if (c_call) atomicAdd(&callable_[a], c_call);
+      if (c_poly) atomicAdd(&poly[a], c_poly);
+      if (c_pairs) atomicAdd(&pairs[a], c_pairs);
+      if (c_disc) atomicAdd(&disc[a], c_disc);
+    }
+    at += c_poly;
+  }
+  __device__ __forceinline__ void close_block(uint64_t b) {
     if (!kEmit && lane == 0) blk[b] = at;
   }
+};
+
+template <bool kEmit>
+__global__ __launch_bounds__(kBlock) void k_var_sites(const uint32_t* __restrict__ cnt, uint64_t nsites, uint64_t nblocks,
+                                                      const uint64_t* __restrict__ off, uint32_t nacc,
+                                                      const unsigned long long* __restrict__ aln, uint32_t min_depth, uint32_t min_count,
+                                                      uint32_t permille, unsigned long long* __restrict__ callable_,
+                                                      unsigned long long* __restrict__ poly, unsigned long long* __restrict__ pairs,
+                                                      unsigned long long* __restrict__ disc, unsigned long long* __restrict__ blk,
+                                                      mg_variant_site* __restrict__ out, uint64_t nout) {
+  SitesPass<kEmit> pass{min_depth, min_count, permille, off, callable_, poly, pairs, disc, blk, out, nout, threadIdx.x & 63u, 0, 0, 0, 0, 0};
+  var_walk(cnt, nsites, nblocks, off, nacc, aln, pass);
+}
+
+// Both passes of the comparison with the reference (mg_variants_diff; metalign_amd/refdiff.py is the definition, mgvar::diff_of the
+// per-site rule): the accessions with an alignment AND a loaded reference; a site's reference code is ref[w], one byte beside the
+// sixteen of its counts.  kEmit = false sums compared, con_subs, pop_subs and ref_other per accession and counts the block's
+// emitted sites; kEmit = true writes them at the block's base + their rank, so they come out ordered by (accession row, pos0).
+template <bool kEmit> struct DiffPass {
+  uint32_t min_depth, min_count, permille;
+  const uint64_t* off;
+  const uint8_t *ref, *loaded;
+  unsigned long long *compared, *con, *pop, *other, *blk;
+  mg_variant_diff* out;
+  uint64_t nout;
+  unsigned lane;
+  unsigned long long at, c_cmp, c_con, c_pop, c_oth, c_emit;
+
+  __device__ __forceinline__ bool takes(uint32_t a) const { return loaded[a] != 0; }
+  __device__ __forceinline__ void open_block(uint64_t b) { at = kEmit ? blk[b] : 0ull; }
+  __device__ __forceinline__ void open_acc() { c_cmp = c_con = c_pop = c_oth = c_emit = 0; }
+  __device__ __forceinline__ void site(uint32_t a, uint64_t w, bool in, const uint32_t n4[4]) {
+    bool emit = false;
+    uint32_t r = 0;
+    if (in) {
+      r = ref[w];
+      const mgvar::Diff d = mgvar::diff_of(n4, r, min_depth, min_count, permille);
+      emit = d.emitted;
+      if (!kEmit) {
+        c_cmp += d.compared ? 1u : 0u;
+        c_con += d.con_sub ? 1u : 0u;
+        c_pop += d.pop_sub ? 1u : 0u;
+        c_oth += d.ref_other ? 1u : 0u;
+        c_emit += emit ? 1u : 0u;
+      }
+    }
+    if (kEmit) {
+      const unsigned long long o = ballot_slot(emit, at);
+      if (emit && o < nout) {
+        mg_variant_diff vd;
+        vd.acc = a;
+        vd.pos0 = (uint32_t)(w - off[a]);
+        vd.n[0] = n4[0]; vd.n[1] = n4[1]; vd.n[2] = n4[2]; vd.n[3] = n4[3];
+        vd.ref = r;
+        out[o] = vd;
+      }
+    }
+  }
+  __device__ __forceinline__ void close_acc(uint32_t a) {
+    if (kEmit) return;
+    c_cmp = wave_sum(c_cmp);
+    c_con = wave_sum(c_con);
+    c_pop = wave_sum(c_pop);
+    c_oth = wave_sum(c_oth);
+    c_emit = wave_sum(c_emit);
+    if (lane == 0) {
+      if (c_cmp) atomicAdd(&compared[a], c_cmp);
+      if (c_con) atomicAdd(&con[a], c_con);
+      if (c_pop) atomicAdd(&pop[a], c_pop);
+      if (c_oth) atomicAdd(&other[a], c_oth);
+    }
+    at += c_emit;
+  }
+  __device__ __forceinline__ void close_block(uint64_t b) {
+    if (!kEmit && lane == 0) blk[b] = at;
+  }
+};
+
+template <bool kEmit>
+__global__ __launch_bounds__(kBlock) void k_var_diff(const uint32_t* __restrict__ cnt, uint64_t nsites, uint64_t nblocks,
+                                                     const uint64_t* __restrict__ off, uint32_t nacc,
+                                                     const unsigned long long* __restrict__ aln, const uint8_t* __restrict__ ref,
+                                                     const uint8_t* __restrict__ loaded, uint32_t min_depth, uint32_t min_count,
+                                                     uint32_t permille, unsigned long long* __restrict__ compared,
+                                                     unsigned long long* __restrict__ con, unsigned long long* __restrict__ pop,
+                                                     unsigned long long* __restrict__ other, unsigned long long* __restrict__ blk,
+                                                     mg_variant_diff* __restrict__ out, uint64_t nout) {
+  DiffPass<kEmit> pass{min_depth, min_count, permille, off, ref, loaded, compared, con, pop, other, blk, out, nout, threadIdx.x & 63u,
+                       0, 0, 0, 0, 0, 0};
+  var_walk(cnt, nsites, nblocks, off, nacc, aln, pass);
 }
 
 // t[i] = the counts before block i; *total = all of them
@@ -379,6 +513,75 @@ int mg_variants_consensus(mg_variants* h, const uint32_t* rows, uint32_t nrows, 
   }
   MG_HIP(hipMemcpyAsync(out, text.p, total, hipMemcpyDeviceToHost, st));
   MG_HIP(hipStreamSynchronize(st));  // (toff and the caller's rows are free from here)
+  return MG_OK;
+}
+
+int mg_variants_diff(mg_variants* h, const mg_refseq* ref, uint32_t min_depth, uint32_t min_count, uint32_t freq_permille,
+                     uint64_t* compared, uint64_t* con_subs, uint64_t* pop_subs, uint64_t* ref_other, uint64_t* nsites) {
+  MG_REQUIRE_READY();
+  if (!h || !ref || !nsites || (h->nacc && (!compared || !con_subs || !pop_subs || !ref_other))) return fail(MG_ERR_ARG, "null argument");
+  if (min_depth < 2 || min_count < 1 || freq_permille > 500)
+    return fail(MG_ERR_ARG, "min_depth %u (at least 2), min_count %u (at least 1), freq_permille %u (at most 500)", min_depth, min_count,
+                freq_permille);
+  if (ref->nacc != h->nacc) return fail(MG_ERR_ARG, "the reference was parsed for %u accessions, the counts hold %u", ref->nacc, h->nacc);
+  for (uint32_t a = 0; a < h->nacc; ++a)
+    if (ref->h_len[a] != h->h_len[a])
+      return fail(MG_ERR_ARG, "accession %u: the reference was parsed for length %llu, the counts hold %llu", a,
+                  (unsigned long long)ref->h_len[a], (unsigned long long)h->h_len[a]);
+  hipStream_t st = ctx().stream;
+  const uint64_t nacc = h->nacc;
+  h->dsites.release();
+  h->ndiff = 0;
+  h->diffed = false;
+  MG_TRY(h->dsums.alloc((4 * nacc + 1) * sizeof(uint64_t)));
+  MG_TRY(h->dblk.alloc((h->nblocks + 1) * sizeof(uint64_t)));
+  unsigned long long* ds = h->dsums.as<unsigned long long>();
+  unsigned long long* blk = h->dblk.as<unsigned long long>();
+  const unsigned long long* aln = h->sums.as<unsigned long long>();
+  MG_HIP(hipMemsetAsync(ds, 0, (4 * nacc + 1) * sizeof(uint64_t), st));
+  if (h->nblocks) {
+    const unsigned grid = var_grid(h->nblocks, kBlock / 64);
+    {
+      ProfScope ps("var_diff_sums");
+      hipLaunchKernelGGL(k_var_diff<false>, dim3(grid), dim3(kBlock), 0, st, h->cnt, h->nsites, h->nblocks, h->off.as<uint64_t>(), h->nacc,
+                         aln, ref->codes, ref->loaded.as<uint8_t>(), min_depth, min_count, freq_permille, ds, ds + nacc, ds + 2 * nacc,
+                         ds + 3 * nacc, blk + 1, (mg_variant_diff*)nullptr, (uint64_t)0);
+      MG_HIP(hipGetLastError());
+    }
+    {
+      ProfScope ps("var_diff_scan");
+      hipLaunchKernelGGL(k_var_scan, dim3(1), dim3(kScanBlock), 0, st, blk + 1, h->nblocks, blk);
+      MG_HIP(hipGetLastError());
+    }
+    MG_HIP(hipMemcpyAsync(&h->ndiff, blk, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    MG_HIP(hipStreamSynchronize(st));
+    if (h->ndiff) {
+      ProfScope ps("var_diff_emit");
+      MG_TRY(h->dsites.alloc(h->ndiff * sizeof(mg_variant_diff)));
+      hipLaunchKernelGGL(k_var_diff<true>, dim3(grid), dim3(kBlock), 0, st, h->cnt, h->nsites, h->nblocks, h->off.as<uint64_t>(), h->nacc,
+                         aln, ref->codes, ref->loaded.as<uint8_t>(), min_depth, min_count, freq_permille, ds, ds + nacc, ds + 2 * nacc,
+                         ds + 3 * nacc, blk + 1, h->dsites.as<mg_variant_diff>(), h->ndiff);
+      MG_HIP(hipGetLastError());
+    }
+  }
+  uint64_t* const out[4] = {compared, con_subs, pop_subs, ref_other};
+  uint64_t none = 0;
+  MG_TRY(fetch_sums(ds, nacc, out, 4, &none));
+  *nsites = h->ndiff;
+  h->diffed = true;
+  return MG_OK;
+}
+
+int mg_variants_fetch_diffs(mg_variants* h, mg_variant_diff* out) {
+  MG_REQUIRE_READY();
+  if (!h) return fail(MG_ERR_ARG, "null argument");
+  if (!h->diffed) return fail(MG_ERR_STATE, "the differing sites are fetched after mg_variants_diff");
+  if (h->ndiff && !out) return fail(MG_ERR_ARG, "null argument");
+  if (h->ndiff) {
+    hipStream_t st = ctx().stream;
+    MG_HIP(hipMemcpyAsync(out, h->dsites.p, h->ndiff * sizeof(mg_variant_diff), hipMemcpyDeviceToHost, st));
+    MG_HIP(hipStreamSynchronize(st));
+  }
   return MG_OK;
 }
 

@@ -16,6 +16,7 @@
 //   NibblePacker     a sink that packs codes two per byte, the low nibble first; flush() writes a last odd code with a 0 above it
 //   site_of()        one site's four counts against (D, C, F): its depth, whether it is callable, its major allele (ties to the
 //                    lowest code), the mask of its variant alleles, d (d - 1) and d (d - 1) - sum n_i (n_i - 1)
+//   diff_of()        one site's four counts against its reference code (--ani, --vcf; metalign_amd/refdiff.py), over site_of()
 //   consensus_char() one site's character in the consensus sequence (--consensus; metalign_amd/consensus.py), over site_of()
 //   text_bytes()     the bytes of a sequence as text of lines of `width` bases; text_at(): the inverse layout map, which byte of the
 //                    text is a newline and which site every other byte shows; 64-bit throughout
@@ -181,6 +182,29 @@ MGV_HD Site site_of(const uint32_t n[4], uint32_t min_depth, uint32_t min_count,
   s.discordant = s.pairs - same;
   s.polymorphic = s.variants != 0;
   return s;
+}
+
+// One site against its reference code r (--ani, --vcf; metalign_amd/refdiff.py is the definition), over site_of(): compared — the
+// site is callable and r < 4; ref_other — callable and r is kOther; con_sub — compared and the major allele is not r; pop_sub —
+// compared and r is neither the major nor a variant allele; emitted — compared and some present allele is not r.
+struct Diff {
+  bool compared, ref_other, con_sub, pop_sub, emitted;
+};
+
+MGV_HD Diff diff_of(const uint32_t n[4], uint32_t r, uint32_t min_depth, uint32_t min_count, uint32_t permille) {
+  const Site s = site_of(n, min_depth, min_count, permille);
+  Diff d{false, false, false, false, false};
+  if (!s.callable_) return d;
+  if (r >= kOther) {
+    d.ref_other = true;
+    return d;
+  }
+  const uint32_t present = (1u << s.major) | s.variants;
+  d.compared = true;
+  d.con_sub = s.major != r;
+  d.pop_sub = ((present >> r) & 1u) == 0;
+  d.emitted = (present & ~(1u << r)) != 0;
+  return d;
 }
 
 // ---- the consensus text (--consensus; metalign_amd/consensus.py is the definition) --------------------------------------------

@@ -3,7 +3,8 @@
 A family (COVERAGE, DEPTH, IDENTITY, VARIANTS) is a descriptor: its flags, the side array of a batch it reads, its refusals, its header,
 what it holds on the device, and how its device accumulator is opened and turned into the file's block.  ASSIGNMENTS
 (--read_assignments) shares only the flag test, the refusal and the header: its rows come from stage C itself.  --consensus
-(metalign_amd/consensus.py) is no family of its own: it reads VARIANTS' accumulator and opens it by itself too.
+(metalign_amd/consensus.py) is no family of its own: it reads VARIANTS' accumulator and opens it by itself too, and so do --ani and
+--vcf (metalign_amd/refdiff.py), which compare it with the reference FASTA parsed on the device (metalign_amd/refseq.py).
 
 SideOutputs is the families wanted for ONE input file.  map_and_profile opens it, feeds it the records and closes it; the
 order is always coverage, depth, identity, variants, and whatever was opened is freed on every way out.
@@ -17,7 +18,7 @@ import sys
 
 import numpy as np
 
-from . import _hip, assignments, consensus, coverage, depth, identity, side_reads, variants
+from . import _hip, assignments, consensus, coverage, depth, identity, refdiff, refseq, side_reads, variants
 
 
 def _flag(args, name):
@@ -211,22 +212,67 @@ class _Identity(_Family):
 
 
 class _Variants(_Family):
-    """--variants or --variant_sites: either one asks for the per-site allele counts.  --consensus (metalign_amd/consensus.py) reads
-    the same accumulator and opens it by itself too: it is no member of `flags` — the files with a `#reads` line, the refusal texts —
-    but of wanted()."""
+    """--variants or --variant_sites: either one asks for the per-site allele counts.  --consensus (metalign_amd/consensus.py), --ani
+    and --vcf (metalign_amd/refdiff.py) read the same accumulator and open it by themselves too: they are no members of `flags` —
+    the refusal texts of the family — but of wanted(), each with refusal texts of its own."""
     flags, side = ('variants', 'variant_sites'), 'bases'
+    riders = ('consensus', 'ani', 'vcf')
     refuse_world = 'Error: --variants and --variant_sites run in one process on one GPU; start it without torch.distributed.run.'
     refuse_paf = 'Error: --variants and --variant_sites need SAM or BAM alignments: a PAF line has no CIGAR and SEQ columns.'
     refuse_world_consensus = 'Error: --consensus runs in one process on one GPU; start it without torch.distributed.run.'
     refuse_paf_consensus = 'Error: --consensus needs SAM or BAM alignments: a PAF line has no CIGAR and SEQ columns.'
+    refuse_world_ani = 'Error: --ani runs in one process on one GPU; start it without torch.distributed.run.'
+    refuse_paf_ani = 'Error: --ani needs SAM or BAM alignments: a PAF line has no CIGAR and SEQ columns.'
+    refuse_world_vcf = 'Error: --vcf runs in one process on one GPU; start it without torch.distributed.run.'
+    refuse_paf_vcf = 'Error: --vcf needs SAM or BAM alignments: a PAF line has no CIGAR and SEQ columns.'
+    refuse_no_reference = ('Error: --ani and --vcf compare the reads with the FASTA they were aligned to: give it with --reference '
+                           '(or --db).')
+    refuse_reference_missing = 'Error: the reference FASTA of --ani and --vcf does not exist: %s'
+    refuse_vcf_files = ('Error: --vcf takes one input file: a VCF has no place for a block per file. Run the files one by one, '
+                        'each with its own --vcf.')
     nomem = 'Error: --variants keeps sixteen bytes per reference base on the GPU; %d MB for this database do not fit.'
+    _reference = None  # (path, the lengths' bytes, RefSeq): parsed once per run, reused while the lengths are the same
 
     def wanted(self, args):
-        return _Family.wanted(self, args) or _flag(args, 'consensus')
+        return _Family.wanted(self, args) or any(_flag(args, f) for f in self.riders)
 
     def refusal(self, args, what):
-        """--consensus as the family's only flag is refused under its own name."""
-        return getattr(self, 'refuse_' + what + ('' if _Family.wanted(self, args) else '_consensus'))
+        """A rider as the family's only flag is refused under its own name (the first of them that was given)."""
+        if _Family.wanted(self, args):
+            return getattr(self, 'refuse_' + what)
+        return getattr(self, 'refuse_%s_%s' % (what, next(f for f in self.riders if _flag(args, f))))
+
+    def paths(self, args):
+        """... and --ani's, a TSV with the `#reads` line of the others."""
+        return _Family.paths(self, args) + ([args.ani] if _flag(args, 'ani') else [])
+
+    @staticmethod
+    def diffed(args):
+        return _flag(args, 'ani') or _flag(args, 'vcf')
+
+    @staticmethod
+    def reference(args):
+        """--reference, or by default the database FASTA the aligner gets (--db); None where there is neither."""
+        ref = getattr(args, 'reference', 'AUTO')
+        if ref not in (None, 'AUTO', 'NONE'):
+            return ref
+        db = getattr(args, 'db', 'NONE')
+        return db if db not in (None, 'NONE') else None
+
+    def check_reference(self, args):
+        """The refusals of --ani / --vcf that need no GPU.  (`metalign` has no --db: its stages write temp_dir/cmashed_db.fna, which
+        is wired to args.db after this check and exists by the time stage C opens.)"""
+        if not self.diffed(args):
+            return
+        wired_later = hasattr(args, 'reads') and not hasattr(args, 'db') and getattr(args, 'reference', 'AUTO') == 'AUTO'
+        if not wired_later:
+            ref = self.reference(args)
+            if ref is None:
+                sys.exit(self.refuse_no_reference)
+            if not os.path.isfile(ref):
+                sys.exit(self.refuse_reference_missing % ref)
+        if _flag(args, 'vcf') and len(getattr(args, 'infiles', ())) > 1:
+            sys.exit(self.refuse_vcf_files)
 
     @staticmethod
     def params(args):
@@ -250,12 +296,23 @@ class _Variants(_Family):
             variants.write_sites(args.variant_sites, p)
         if _flag(args, 'consensus'):
             consensus.write_consensus(args.consensus)  # (an empty file: FASTA has no comment lines)
+        if _flag(args, 'ani'):
+            refdiff.write_ani(args.ani, p)
+        if _flag(args, 'vcf'):
+            open(args.vcf, 'w').close()  # (the one input file writes it whole: its header names the file's contigs)
 
     def device_bytes(self, args, lengths, nacc, nrec):
         """16 B per reference base and five sums per accession; per record a 16 B entry (and as much again where a collation
         permutes them) and the pool's 4-bit codes — 75 B for a 150-base read, reckoned as 80 B with the entry.  --consensus: a slab
-        of text."""
+        of text.  --ani / --vcf: one byte per reference base, four sums per accession and, while it is parsed, the FASTA text (a
+        .gz reckoned at four times its size) with 40 B of line index per 60 of it."""
         need = 16 * sum(lengths.values()) + 40 * nacc + 16 * nrec + 80 * nrec
+        if self.diffed(args):
+            need += sum(lengths.values()) + 32 * nacc
+            ref = self.reference(args)
+            if ref is not None and os.path.isfile(ref) and self._reference_for(ref, lengths) is None:
+                text = os.path.getsize(ref) * (4 if ref.endswith('.gz') else 1)
+                need += text + 40 * (text // 60 + 1)
         if _flag(args, 'consensus'):
             need += min(consensus.SLAB_BYTES, sum(consensus.text_bytes(n) for n in lengths.values()))
         return need
@@ -273,6 +330,9 @@ class _Variants(_Family):
             aln, call, poly, pairs, disc, unpiled, sites = dev.result(*p)
             if _flag(args, 'consensus'):
                 self.write_consensus_from(args, source, lengths, dev, acc_index, acc2info, aln, call, poly)
+            if self.diffed(args):
+                self.append_diff(args, source, self.diff_from(args, lengths, dev, acc_index, acc2info, aln, call, unpiled), acc2info,
+                                 taxid2info)
         finally:
             dev.free()
         if not _Family.wanted(self, args):
@@ -315,6 +375,60 @@ class _Variants(_Family):
                     out.write(text[at:at + size])
                     at += size
 
+    def _reference_for(self, path, lengths):
+        """The RefSeq kept for this file and these lengths, or None."""
+        kept = self._reference
+        key = (path, tuple(sorted(lengths.items())))
+        return kept[1] if kept is not None and kept[0] == key and kept[1].handle else None
+
+    def reference_on(self, args, hip, lengths, acc_index):
+        """The reference of the run on the device (Hip.refseq_from_file): parsed once, and again only where an input file's lengths
+        differ from those it was parsed for."""
+        path = self.reference(args)
+        ref = self._reference_for(path, lengths)
+        if ref is None:
+            if self._reference is not None:
+                self._reference[1].free()
+                self._reference = None
+            names = [None] * len(acc_index)
+            for a, i in acc_index.items():
+                names[i] = a
+            index = hip.acc_index(names)
+            try:
+                ref = hip.refseq_from_file(path, index, lengths_array(lengths, acc_index))
+            except _hip.HipError as e:
+                if e.code != _hip.ERR_NOMEM:
+                    raise
+                sys.exit('Error: --ani and --vcf keep the reference FASTA and one byte per reference base on the GPU: %s' % e)
+            finally:
+                index.free()
+            self._reference = ((path, tuple(sorted(lengths.items()))), ref)
+        return ref
+
+    def diff_from(self, args, lengths, dev, acc_index, acc2info, aln, call, unpiled):
+        """--ani / --vcf from the open accumulator -> refdiff.RefDiff."""
+        p = self.params(args)
+        ref = self.reference_on(args, dev.hip, lengths, acc_index)
+        comp, con, pop, other, sites = dev.diff(ref, *p)
+        loaded = ref.loaded()
+        emitted = np.bincount(sites['acc'], minlength=len(acc_index)) if len(sites) else np.zeros(len(acc_index), dtype=np.int64)
+        per = {a: [int(aln[i]), int(call[i]), int(comp[i]), int(con[i]), int(pop[i]), int(other[i]), int(emitted[i])]
+               for a, i in acc_index.items() if aln[i] and loaded[i]}
+        no_reference = sum(1 for a, i in acc_index.items() if aln[i] and not loaded[i])
+        names = {i: a for a, i in acc_index.items()}
+        order = {a: k for k, a in enumerate(acc2info)}  # (the device orders by accession row, the files by db_info's order)
+        rows = sorted(((names[int(s['acc'])], int(s['pos0']), tuple(int(x) for x in s['n']), int(s['ref'])) for s in sites),
+                      key=lambda s: (order[s[0]], s[1]))
+        return refdiff.RefDiff(lengths, per, rows, unpiled, no_reference)
+
+    def append_diff(self, args, source, diff, acc2info, taxid2info):
+        p = self.params(args)
+        if _flag(args, 'ani'):
+            refdiff.write_ani(args.ani, p, refdiff.rows(diff, acc2info, taxid2info), diff.unpiled, diff.no_reference,
+                              source=source_label(args, source), append=True)
+        if _flag(args, 'vcf'):
+            refdiff.write_vcf(args.vcf, diff, self.reference(args), acc2info, p, reads_mode(args) == 'unique')
+
     def append(self, args, source, var, acc2info, taxid2info):
         p, source = self.params(args), source_label(args, source)
         if _flag(args, 'variants'):
@@ -323,16 +437,23 @@ class _Variants(_Family):
             variants.write_sites(args.variant_sites, p, var.sites, source=source, append=True)
 
     def append_from_definition(self, args, path, lines, acc2info, taxid2info):
-        if not _flag(args, 'consensus'):
+        if not any(_flag(args, f) for f in self.riders):
             self.append(args, path, variants.variants(lines, acc2info, args.pct_id, self.params(args)), acc2info, taxid2info)
             return
-        # (one pass over the lines, which come as an iterator: variants.variants and consensus.consensus are these two over them)
+        # (one pass over the lines, which come as an iterator: variants.variants, consensus.consensus and refdiff.refdiff are these
+        # over them)
         p, iupac, order = self.params(args), self.iupac(args), list(acc2info)
         n, aln, unpiled, lengths = variants.counts_of_lines(lines, acc2info, args.pct_id)
         if _Family.wanted(self, args):
             self.append(args, path, variants.summarise(n, aln, unpiled, lengths, order, p), acc2info, taxid2info)
-        recs = consensus.records_of(n, aln, unpiled, lengths, order, acc2info, p, iupac, getattr(args, 'consensus_min_called', 0.0))
-        consensus.write_consensus(args.consensus, recs, True, p, iupac, reads_mode(args) == 'unique', source_label(args, path))
+        if _flag(args, 'consensus'):
+            recs = consensus.records_of(n, aln, unpiled, lengths, order, acc2info, p, iupac, getattr(args, 'consensus_min_called', 0.0))
+            consensus.write_consensus(args.consensus, recs, True, p, iupac, reads_mode(args) == 'unique', source_label(args, path))
+        if self.diffed(args):
+            acc_index = {a: i for i, a in enumerate(order)}
+            parsed = refseq.parse(refseq.read_bytes(self.reference(args)), acc_index, [lengths[a] for a in order])
+            ref = refdiff.ref_by_accession(parsed, acc_index)
+            self.append_diff(args, path, refdiff.compare(n, aln, unpiled, lengths, order, ref, p), acc2info, taxid2info)
 
 
 ASSIGNMENTS, COVERAGE, DEPTH, IDENTITY, VARIANTS = _Assignments(), _Coverage(), _Depth(), _Identity(), _Variants()
@@ -350,6 +471,7 @@ def check_flags(args):
             sys.exit(fam.refusal(args, 'world'))
         if paf and fam.refusal(args, 'paf'):
             sys.exit(fam.refusal(args, 'paf'))
+    VARIANTS.check_reference(args)
     if int(getattr(args, 'depth_window_size', 1000)) < 1:
         sys.exit('Error: --depth_window_size must be at least 1.')
     try:
