@@ -115,7 +115,8 @@ int mg_device_count(void);
  *   default 8 MiB, at least 4 KiB), genome_guard (test hook: mg_genomes_parse_dev fills the 16 bytes behind its bases and the
  *   word behind its offsets with 0xa5 before its kernels run); cov_grid (test hook, k3_grid's meaning for k_cov_add /
  *   k_cov_count, mg_coverage.hip); depth_grid (test hook, the same for every grid of mg_depth.hip); ident_grid (test hook, the same for k_ident_add, mg_identity.hip); var_grid (test hook, the same for every grid of mg_variants.hip); mm_hash_bits (test hook, mg_profile_mm_iterate_dev: only this many low bits of a list's hash
- *   are kept, so that different lists collide).
+ *   are kept, so that different lists collide); align_grid (test hook, k3_grid's meaning for the seeding, extension and selection
+ *   grids of mg_align.hip); align_batch_cands (test hook: mg_align_reads_dev halves a batch of reads with more candidates than this).
  * Needs no device and no mg_init.  MG_ERR_ARG for a key that does not exist. */
 int mg_debug_set(const char* key, int64_t value);
 int64_t mg_debug_get(const char* key);
@@ -1151,6 +1152,37 @@ int mg_variants_fetch_diffs(mg_variants* h, mg_variant_diff* out);
  *   behind stage C's; the tile counts come from the library's pool.  n = 0 is legal. */
 int mg_records_mask_unique_dev(const mg_aln_rec* d_recs, uint64_t n, const uint64_t* d_assign, uint64_t nreads,
                                const uint32_t* d_ref2tax, uint32_t nref, mg_aln_rec* d_out, uint64_t* d_stats2);
+
+/* READS ALIGNED ON THE DEVICE (--aligner device; metalign_amd/csrc/mg_align.hip; the definition is metalign_amd/align.py): an
+ * ungapped seed-and-extend aligner of short reads, neither a port of minimap2 nor on a par with it.
+ * index_build: the minimizers (k odd in 11 .. 31, w in 1 .. 32) of every loaded row of the reference, by key, with the table of
+ *   unique keys.  The bytes are checked against mg_mem_info by arithmetic before anything is allocated or launched: MG_ERR_NOMEM
+ *   with the byte count in the message.  MG_ERR_ARG for k or w out of range, or a reference whose diagonals need more than 39 bits.
+ *   Synchronises.  The index reads the reference's lengths only; the reference must outlive the alignment calls, not the index.
+ * index_stats: out4 = entries, unique keys, k, w.
+ * index_download (for tests): keys[entries], vals[entries] by key; vals = (off[a] + (a + 1) * 1024 + p) << 1 | strand bit, off[a]
+ *   the sum of the lengths of the rows in front of a.
+ * reads_dev: the reads at d_bases (the bytes as written, 8-byte aligned) / d_offsets (u64[nreads + 1]), as mg_reads_device_ptrs
+ *   gives them, aligned against `ref`, the reference the index was built from -> their records, behind those *batch holds already
+ *   (*batch == NULL: a new batch).  want_mask: MG_BATCH_PLACES, MG_BATCH_EDITS, MG_BATCH_BASES (any other bit: MG_ERR_ARG; a batch to
+ *   append to must have been made with the same mask, else MG_ERR_STATE).  The batch is neither keyed nor named; every primary
+ *   carries MG_REC_NEW_BIT.  stats5 (optional): reads, aligned reads, distinct candidates, accepted candidates, records of THIS call.
+ *   A range of reads whose candidates do not fit is halved; MG_ERR_NOMEM when one read's do not.  Synchronises. */
+typedef struct mg_align_params {
+  uint32_t k, w;           /* as the index's */
+  uint32_t max_occ;        /* a minimizer with more entries than this seeds nothing (1 .. 65535) */
+  uint32_t min_score;      /* 1 .. 1024 */
+  uint32_t mismatch;       /* what a column that does not match subtracts (1 .. 64) */
+  uint32_t max_secondary;  /* 0 .. 15 */
+  uint32_t sec_pct;        /* a secondary has at least this share of the primary's score, in percent (0 .. 100) */
+} mg_align_params;
+typedef struct mg_align_index mg_align_index;
+int mg_align_index_build(const mg_refseq* ref, uint32_t k, uint32_t w, mg_align_index** out);
+int mg_align_index_stats(const mg_align_index* ix, uint64_t out4[4]);
+int mg_align_index_download(const mg_align_index* ix, uint64_t* keys, uint64_t* vals);
+void mg_align_index_free(mg_align_index* ix);
+int mg_align_reads_dev(const mg_align_index* ix, const mg_refseq* ref, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t nreads,
+                       const mg_align_params* params, unsigned want_mask, mg_sam_batch** batch, uint64_t stats5[5]);
 
 /* Host-buffer convenience, single shard = whole stream. Capacities: mm_* as
  * above with mm_cap_reads / mm_cap_entries entries available. */

@@ -57,6 +57,7 @@ EXPORTS = [
     "mg_variants_free", "mg_variants_diff", "mg_variants_fetch_diffs",
     "mg_refseq_parse_dev", "mg_refseq_stats", "mg_refseq_loaded", "mg_refseq_download", "mg_refseq_free",
     "mg_records_mask_unique_dev",
+    "mg_align_index_build", "mg_align_index_stats", "mg_align_index_download", "mg_align_index_free", "mg_align_reads_dev",
     "mg_gunzip_open", "mg_gunzip_read", "mg_gunzip_close", "mg_zcat_files", "mg_stream_thin_file",
     "mg_inflate_dev", "mg_inflated_bytes", "mg_inflated_download", "mg_inflated_free", "mg_inflate_config", "mg_inflate_stats",
     "mg_sketch_genomes", "mg_sketch_genomes_prefix", "mg_db_upload", "mg_db_upload_sorted", "mg_db_ngenomes", "mg_db_max_hash", "mg_db_free",
@@ -157,6 +158,7 @@ def load_library(path=LIB_PATH):
     lib.mg_identity_free.restype = None
     lib.mg_variants_free.restype = None
     lib.mg_refseq_free.restype = None
+    lib.mg_align_index_free.restype = None
     lib.mg_variants_consensus.argtypes = [_vp, _u32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                           ctypes.c_uint32, _u8p, ctypes.c_uint64]
     lib.mg_shutdown.restype = None
@@ -1424,6 +1426,49 @@ class RefSeq:
             pass
 
 
+class _AlignParams(ctypes.Structure):
+    """mg_align_params: the fields of align.Params, in their order."""
+    _fields_ = [(name, ctypes.c_uint32) for name in ("k", "w", "max_occ", "min_score", "mismatch", "max_secondary", "sec_pct")]
+
+
+class AlignIndex:
+    """The minimizer index of a RefSeq on the device (mg_align_index_*; metalign_amd/align.py is the definition): what
+    Hip.align_reads_dev seeds the reads in.  Made by Hip.align_index.  It keeps the RefSeq it was built from."""
+
+    def __init__(self, hip, handle, ref):
+        self.hip, self.handle, self.ref = hip, handle, ref
+
+    def stats(self):
+        """-> (entries, unique keys, k, w)."""
+        out = np.zeros(4, dtype=np.uint64)
+        self.hip._chk(self.hip.lib.mg_align_index_stats(self.handle, _np(out, ctypes.c_uint64)))
+        return tuple(int(x) for x in out)
+
+    def download(self):
+        """-> the entries as align.index_entries gives them: the sorted list of (key, accession row, position, strand bit)."""
+        n = self.stats()[0]
+        keys, vals = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+        self.hip._chk(self.hip.lib.mg_align_index_download(self.handle, _np(keys, ctypes.c_uint64), _np(vals, ctypes.c_uint64)))
+        off = np.concatenate([[0], np.cumsum(self.ref.lengths)]).astype(np.uint64)
+        lo = off[:-1] + np.arange(self.ref.nacc, dtype=np.uint64) * np.uint64(1024)  # (a row's padded values start above this)
+        out = []
+        for key, v in zip(keys[:n].tolist(), vals[:n].tolist()):
+            a = int(np.searchsorted(lo, v >> 1, side="right")) - 1
+            out.append((key, a, (v >> 1) - int(off[a]) - (a + 1) * 1024, v & 1))
+        return sorted(out)
+
+    def free(self):
+        if self.handle:
+            self.hip.lib.mg_align_index_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:  # noqa: BLE001
+            pass
+
+
 class Depth(_SideAccumulator):
     """One int32 slot per reference base (and one per accession) on the device: per-base depth as a histogram per accession and as
     windows of `window` bases (mg_depth_*; metalign_amd/depth.py is the definition).  lengths: one per accession row; window = 0:
@@ -1607,6 +1652,38 @@ class Hip:
             return self.refseq_parse(dev.ptr, size, acc_index, lengths)
         finally:
             dev.free()
+
+    def align_index(self, ref, k, w):
+        """The aligner's minimizer index of a RefSeq (mg_align_index_build).  HipError with code ERR_NOMEM, the bytes in its text,
+        when the index cannot fit: decided by arithmetic, before anything is allocated."""
+        h = _vp()
+        self._chk(self.lib.mg_align_index_build(ref.handle, ctypes.c_uint32(int(k)), ctypes.c_uint32(int(w)), ctypes.byref(h)))
+        return AlignIndex(self, h, ref)
+
+    def align_reads_dev(self, index, d_bases, d_offsets, nreads, params, placed=False, edited=False, based=False, batch=None):
+        """Reads in HBM (Reads.device_ptrs) aligned against index.ref -> (SamBatch, align.Stats of this call)
+        (mg_align_reads_dev).  params: align.Params.  batch: a SamBatch of an earlier call with the same side arrays, which the
+        records are appended to (the same object comes back, its count and pointer brought up to date)."""
+        from .align import Stats
+        p = _AlignParams(*(int(x) for x in params))
+        h = _vp(batch.handle.value if batch is not None else None)
+        stats = np.zeros(5, dtype=np.uint64)
+        self._chk(self.lib.mg_align_reads_dev(index.handle, index.ref.handle, _vp(d_bases), _vp(d_offsets), ctypes.c_uint64(int(nreads)),
+                                              ctypes.byref(p), _want(placed=placed, edited=edited, based=based), ctypes.byref(h),
+                                              _np(stats, ctypes.c_uint64)))
+        if batch is None:
+            batch = SamBatch(self, h)
+        else:
+            batch.__init__(self, batch.handle)  # (the arrays may have moved)
+        return batch, Stats(*(int(x) for x in stats))
+
+    def parse_reads_prefix_dev(self, d_text, nbytes, fmt, final):
+        """A piece of a reads file in HBM that begins on a record boundary -> (Reads of its whole records, the bytes they take)
+        (mg_reads_parse_prefix_dev): the caller carries the rest to the front of the next piece."""
+        h, used = _vp(), ctypes.c_uint64(0)
+        self._chk(self.lib.mg_reads_parse_prefix_dev(_vp(d_text), ctypes.c_uint64(int(nbytes)), ctypes.c_int(_READS_FORMAT[fmt]),
+                                                     ctypes.c_int(1 if final else 0), ctypes.byref(used), ctypes.byref(h)))
+        return Reads(self, h), int(used.value)
 
     def depth(self, lengths, window=0):
         """A Depth over accessions of these lengths, with windows of `window` bases (mg_depth_create)."""

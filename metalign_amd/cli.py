@@ -104,6 +104,23 @@ _OPTIONS = {
                                 'the definition). Default 1: the single step, in proportion to uniquely mapped bases.'),
     'multimap_tol': dict(type=float, default=1e-8, help='Stop iterating once no genome\'s bases change by more than this fraction '
                          '(default 1e-8, a tenth of the last digit the profile prints); 0 runs all --multimap_iterations.'),
+    'aligner': dict(default='minimap2', choices=['minimap2', 'device'],
+                    help='What aligns a reads file: "minimap2" (default: the external program, started as the reference starts it) or '
+                         '"device": the seed-and-extend aligner on the GPU (metalign_amd/align.py is the definition), which needs no '
+                         'minimap2 installed and ignores --threads. It is ungapped, single-end, gives no MAPQ, keeps no read names '
+                         '(no --read_assignments) and runs on one GPU; it is not minimap2 and does not reproduce its alignments. '
+                         'No effect on SAM / BAM / PAF input.'),
+    'align_k': dict(type=int, default=15, help='--aligner device: the k-mer length of the seeds (default 15; odd, 11 to 31).'),
+    'align_w': dict(type=int, default=5, help='--aligner device: the minimizer window, in k-mers (default 5; 1 to 32).'),
+    'align_max_occ': dict(type=int, default=64, help='--aligner device: a minimizer that occurs more often than this in the '
+                          'reference seeds nothing (default 64).'),
+    'align_min_score': dict(type=int, default=30, help='--aligner device: an alignment scores at least this (default 30; a match '
+                            'adds 1).'),
+    'align_mismatch': dict(type=int, default=4, help='--aligner device: what a mismatch subtracts (default 4).'),
+    'align_secondary': dict(type=int, default=5, help='--aligner device: at most this many secondary alignments per read '
+                            '(default 5; 0 to 15).'),
+    'align_secondary_pct': dict(type=int, default=80, help='--aligner device: a secondary alignment has at least this percentage '
+                                'of the primary\'s score (default 80).'),
     'device_multimap': dict(action='store_true', help='Resolve multimapped reads on the GPU (their lists never leave '
                             'the device; abundances equal the default path to ~1e-15 relative, not byte for byte).'),
 }
@@ -122,7 +139,9 @@ _TOOLS = {
                  'sketch_table', 'min_count', 'sketch_size', 'kmer_match', 'device_multimap', 'collate', 'read_assignments', 'coverage',
                  'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size', 'identity', 'side_reads',
                  'variants', 'variant_sites', 'variant_min_depth', 'variant_min_count', 'variant_min_freq',
-                 'consensus', 'consensus_ambiguity', 'consensus_min_called', 'ani', 'vcf', 'reference']),
+                 'consensus', 'consensus_ambiguity', 'consensus_min_called', 'ani', 'vcf', 'reference',
+                 'aligner', 'align_k', 'align_w', 'align_max_occ', 'align_min_score', 'align_mismatch', 'align_secondary',
+                 'align_secondary_pct']),
     'select_db': dict(
         description='Run CMash and select a subset of the whole database to align to.',
         positionals=[('reads', dict(help='Reads file (FASTA / FASTQ, optionally .gz, or a BAM of reads).')),
@@ -132,7 +151,7 @@ _TOOLS = {
                  'temp_dir', 'threads', 'sketch_table', 'min_count', 'sketch_size', 'kmer_match']),
     'map_and_profile': dict(
         description='Compute abundance estimations for species in a sample.',
-        positionals=[('infiles', dict(nargs='+', help='SAM file(s), or reads file(s) to align with minimap2.')),
+        positionals=[('infiles', dict(nargs='+', help='SAM file(s), or reads file(s) to align (--aligner: with minimap2, or on the GPU).')),
                      ('data', dict(help='data/ directory.'))],
         options=[('db', 'NONE', 'Database FASTA from select_db (needed unless the inputs are SAM files).'), 'dbinfo',
                  ('input_type', ['fastq', 'fasta', 'sam', 'AUTO']), 'length_normalize', 'low_mem', 'min_abundance',
@@ -140,7 +159,9 @@ _TOOLS = {
                  'verbose', 'device_multimap', 'collate', 'read_assignments', 'coverage',
                  'multimap_iterations', 'multimap_tol', 'depth', 'depth_windows', 'depth_window_size', 'identity', 'side_reads',
                  'variants', 'variant_sites', 'variant_min_depth', 'variant_min_count', 'variant_min_freq',
-                 'consensus', 'consensus_ambiguity', 'consensus_min_called', 'ani', 'vcf', 'reference']),
+                 'consensus', 'consensus_ambiguity', 'consensus_min_called', 'ani', 'vcf', 'reference',
+                 'aligner', 'align_k', 'align_w', 'align_max_occ', 'align_min_score', 'align_mismatch', 'align_secondary',
+                 'align_secondary_pct']),
 }
 
 

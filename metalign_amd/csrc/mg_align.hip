@@ -1,0 +1,701 @@
+// mg_align.hip — short reads aligned to the reference codes by seed and extend (--aligner device; metalign_amd/align.py is the
+// definition, mg_align_core.h holds the per-position rules, shared with the host check).  Reads (mg_reads) and reference
+// (mg_refseq) are in HBM already; what comes out is an mg_sam_batch, as the tokenisers leave one.  No SAM text exists.
+//
+//   the index (mg_align_index_build)
+//     k_al_ref<false>   one thread per reference base: is its k-mer position a minimizer (mga::minimizer_at)?  Counts them.
+//     k_al_ref<true>    ... and writes (key, value), value = (pad(a) + p) << 1 | strand bit, through a cursor a wave moves once
+//     sort_pairs_u64    by key; rle_keys + a scan: the unique keys with their runs' starts and lengths
+//   a batch of reads (mg_align_reads_dev; the host halves a batch whose candidates do not fit)
+//     k_al_seed<false>  one thread per read base: a minimizer?  Its key's run in the unique-key table; counts the entries
+//     k_al_seed<true>   ... and writes one 64-bit candidate per entry: read << 40 | strand << 39 | (pad(a) + d)
+//     sort_keys + rle   the DISTINCT candidates
+//     k_al_extend       THE HOT PATH: one lane per distinct candidate scans its diagonal eight columns per step
+//     compaction, two stable sorts: the accepted alignments by (read, score descending, a, pos0, strand, d)
+//     k_al_select<false / true>   one thread per read walks its list (overlap and secondary rules), counts, then writes records,
+//                       places, edits, base entries and the pool
+//
+// pad(a) = off[a] + (a + 1) * 1024 keeps the diagonals of neighbouring accessions apart: d reaches from -(L - k) >= -1009 up to
+// len[a] - 1, so pad(a) + d names (a, d) uniquely and a read never aligns across a boundary.  Everything is integers.
+#include <memory>
+#include <vector>
+
+#include "mg_align_core.h"
+#include "mg_internal.h"
+
+using namespace mg;
+
+struct mg_align_index {
+  uint32_t k = 0, w = 0, nacc = 0;
+  uint64_t nsites = 0, nent = 0, nuniq = 0;
+  DevBuf off;           // u64[nacc + 1]: the site offsets of the rows
+  DevBuf keys, vals;    // u64[nent] each, by key
+  DevBuf ukey, ustart;  // u64[nuniq] / u64[nuniq + 1]
+  DevBuf ucount;        // u32[nuniq]
+};
+
+namespace {
+
+constexpr int kAB = 256;
+constexpr uint64_t kPad = 1024;
+constexpr unsigned kReadShift = 40, kStrandShift = 39;
+constexpr uint64_t kDiagMask = (1ull << kStrandShift) - 1;
+constexpr uint64_t kMaxBatchReads = 1ull << 24;
+
+struct Accepted {  // one accepted alignment
+  uint32_t read, a, pos0, score;
+  uint16_t b, e;
+  uint32_t strand;
+};
+
+__device__ __forceinline__ uint64_t pad_of(const uint64_t* __restrict__ off, uint64_t a) { return off[a] + (a + 1) * kPad; }
+
+// the largest s in [lo, hi) with offs[s] <= g (offs[lo] <= g is the caller's)
+__device__ __forceinline__ uint64_t seq_of(const uint64_t* __restrict__ offs, uint64_t lo, uint64_t hi, uint64_t g) {
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (offs[mid] <= g) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// Every lane of the wave: reserves `mine` slots behind *cursor, one atomic per wave; -> this lane's first slot.
+__device__ __forceinline__ uint64_t wave_reserve(uint32_t mine, unsigned long long* cursor) {
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t x = mine;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t y = __shfl_up(x, d, 64);
+    if (lane >= d) x += y;
+  }
+  const uint32_t total = __shfl(x, 63, 64);
+  unsigned long long base = 0;
+  if (lane == 63 && total) base = atomicAdd(cursor, (unsigned long long)total);
+  const uint32_t blo = __shfl((uint32_t)base, 63, 64), bhi = __shfl((uint32_t)(base >> 32), 63, 64);
+  return (((uint64_t)bhi << 32) | blo) + (x - mine);
+}
+
+struct CodesAt {  // the reference: one code per byte
+  const uint8_t* p;
+  __device__ uint32_t operator()(uint64_t i) const { return p[i]; }
+};
+struct BasesAt {  // a read: the bytes as written
+  const uint8_t* p;
+  __device__ uint32_t operator()(uint64_t i) const { return mga::code_of(p[i]); }
+};
+
+template <bool kEmit>
+__global__ __launch_bounds__(kAB) void k_al_ref(const uint8_t* __restrict__ codes, const uint64_t* __restrict__ off,
+                                                const uint8_t* __restrict__ loaded, uint64_t nacc, uint64_t nsites, uint32_t k, uint32_t w,
+                                                unsigned long long* __restrict__ cursor, uint64_t* __restrict__ keys,
+                                                uint64_t* __restrict__ vals) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t g0 = (uint64_t)blockIdx.x * blockDim.x; g0 < nsites; g0 += stride) {  // (uniform trips: the wave reserves together)
+    const uint64_t g = g0 + threadIdx.x;
+    bool is_min = false;
+    mga::Key key{0, 0, false};
+    uint64_t a = 0, p = 0;
+    if (g < nsites) {
+      a = seq_of(off, 0, nacc, g);
+      const uint64_t n = off[a + 1] - off[a];
+      p = g - off[a];
+      if (loaded[a] && n >= k && p < n - k + 1) is_min = mga::minimizer_at(CodesAt{codes + off[a]}, n, p, k, w, &key);
+    }
+    const uint64_t at = wave_reserve(is_min ? 1u : 0u, cursor);
+    if (kEmit && is_min) {
+      keys[at] = key.key;
+      vals[at] = ((pad_of(off, a) + p) << 1) | key.strand;
+    }
+  }
+}
+
+// the run of `key` in the unique-key table, or nuniq
+__device__ __forceinline__ uint64_t find_key(const uint64_t* __restrict__ ukey, uint64_t nuniq, uint64_t key) {
+  uint64_t lo = 0, hi = nuniq;
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (ukey[mid] < key) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < nuniq && ukey[lo] == key ? lo : nuniq;
+}
+
+// reads [r0, r1), whose bases are [g_lo, g_hi) of `bases`
+template <bool kEmit>
+__global__ __launch_bounds__(kAB) void k_al_seed(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ offs, uint64_t r0,
+                                                 uint64_t r1, uint64_t g_lo, uint64_t g_hi, uint32_t k, uint32_t w, uint32_t max_occ,
+                                                 const uint64_t* __restrict__ ukey, const uint64_t* __restrict__ ustart,
+                                                 const uint32_t* __restrict__ ucount, uint64_t nuniq, const uint64_t* __restrict__ vals,
+                                                 unsigned long long* __restrict__ cursor, uint64_t* __restrict__ cand) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t g0 = g_lo + (uint64_t)blockIdx.x * blockDim.x; g0 < g_hi; g0 += stride) {
+    const uint64_t g = g0 + threadIdx.x;
+    uint32_t occ = 0, L = 0, i = 0;
+    uint64_t r = 0, run = 0;
+    mga::Key key{0, 0, false};
+    if (g < g_hi) {
+      r = seq_of(offs, r0, r1, g);
+      const uint64_t n = offs[r + 1] - offs[r], p = g - offs[r];
+      if (n >= k && n <= mga::kMaxRead && p < n - k + 1 && mga::minimizer_at(BasesAt{bases + offs[r]}, n, p, k, w, &key)) {
+        const uint64_t u = find_key(ukey, nuniq, key.key);
+        if (u < nuniq && ucount[u] <= max_occ) {
+          occ = ucount[u];
+          run = ustart[u];
+          L = (uint32_t)n;
+          i = (uint32_t)p;
+        }
+      }
+    }
+    const uint64_t at = wave_reserve(occ, cursor);
+    if (kEmit) {
+      for (uint32_t t = 0; t < occ; ++t) {
+        const uint64_t v = vals[run + t];
+        const uint64_t strand = (v & 1ull) ^ key.strand;
+        const uint64_t shift = strand ? L - k - i : i;
+        cand[at + t] = ((r - r0) << kReadShift) | (strand << kStrandShift) | ((v >> 1) - shift);
+      }
+    }
+  }
+}
+
+// n <= 8 bytes at p, any alignment, from aligned 8-byte words: every word loaded holds one of the bytes
+__device__ __forceinline__ uint64_t ld_bytes(const uint8_t* p, uint32_t n) {
+  const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 7u);
+  const uint64_t* a = reinterpret_cast<const uint64_t*>(p - sh);
+  uint64_t v = a[0] >> (8u * sh);
+  if (sh + n > 8u) v |= a[1] << (64u - 8u * sh);
+  return v;
+}
+
+// the row of pad(a) + d: the largest a with off[a] + a * 1024 <= G
+__device__ __forceinline__ uint64_t row_of(const uint64_t* __restrict__ off, uint64_t nacc, uint64_t G) {
+  uint64_t lo = 0, hi = nacc;
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (off[mid] + mid * kPad <= G) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// One lane per distinct candidate.  The columns outside the accession only reset the scan, and none of them lies between two inside
+// columns, so the scan runs over the inside columns [j_lo, j_hi) alone, starting there.  Eight columns per step: the reference codes
+// and the read's bytes each come as one 64-bit value (the read's reversed for strand 1).
+__global__ __launch_bounds__(kAB) void k_al_extend(const uint64_t* __restrict__ cand, uint64_t ncand, uint64_t r0,
+                                                   const uint8_t* __restrict__ bases, const uint64_t* __restrict__ offs,
+                                                   const uint8_t* __restrict__ codes, const uint64_t* __restrict__ off, uint64_t nacc,
+                                                   int32_t P, uint32_t min_score, uint2* __restrict__ ext, uint32_t* __restrict__ flag) {
+  uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (; c < ncand; c += stride) {
+    const uint64_t cv = cand[c];
+    const uint64_t r = r0 + (cv >> kReadShift), G = cv & kDiagMask;
+    const bool rev = (cv >> kStrandShift) & 1ull;
+    const uint64_t a = row_of(off, nacc, G);
+    const int64_t d = (int64_t)G - (int64_t)pad_of(off, a);
+    const int64_t len = (int64_t)(off[a + 1] - off[a]);
+    const uint8_t* read = bases + offs[r];
+    const int32_t L = (int32_t)(offs[r + 1] - offs[r]);
+    const uint8_t* ref = codes + off[a];
+    const int32_t j_lo = d < 0 ? (int32_t)-d : 0;
+    const int32_t j_hi = len - d < (int64_t)L ? (int32_t)(len - d) : L;
+    mga::Scan s;
+    s.start = j_lo;
+    for (int32_t j = j_lo; j < j_hi; j += 8) {
+      const uint32_t n = j_hi - j < 8 ? (uint32_t)(j_hi - j) : 8u;
+      uint64_t gw = ld_bytes(ref + (d + j), n), rw;
+      if (rev) rw = __builtin_bswap64(ld_bytes(read + (L - j - (int32_t)n), n) << (8u * (8u - n)));
+      else rw = ld_bytes(read + j, n);
+#pragma unroll
+      for (uint32_t t = 0; t < 8; ++t) {
+        if (t < n) {
+          uint32_t rc = mga::code_of((uint32_t)(rw >> (8u * t)) & 0xffu);
+          if (rev) rc = mga::comp(rc);
+          mga::step(s, j + (int32_t)t, true, rc < 4 && rc == ((uint32_t)(gw >> (8u * t)) & 0xffu), P);
+        }
+      }
+    }
+    ext[c] = make_uint2((uint32_t)s.best, ((uint32_t)s.b << 16) | (uint32_t)s.e);
+    flag[c] = (uint32_t)s.best >= min_score ? 1u : 0u;
+  }
+}
+
+// the accepted candidates, compacted: their alignments, the first sort's keys ((a, pos0) << 11 | strand << 10 | 1023 - b: a's
+// pos0, then strand, then d = pos0 - b ascending) and their own indices as the values
+__global__ __launch_bounds__(kAB) void k_al_compact(const uint64_t* __restrict__ cand, const uint2* __restrict__ ext,
+                                                    const uint32_t* __restrict__ flag, const uint64_t* __restrict__ at, uint64_t ncand,
+                                                    const uint64_t* __restrict__ off, uint64_t nacc, Accepted* __restrict__ acc,
+                                                    uint64_t* __restrict__ key1, uint64_t* __restrict__ val) {
+  uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (; c < ncand; c += stride) {
+    if (!flag[c]) continue;
+    const uint64_t cv = cand[c], G = cv & kDiagMask, o = at[c];
+    const uint64_t a = row_of(off, nacc, G);
+    const int64_t d = (int64_t)G - (int64_t)pad_of(off, a);
+    const uint2 x = ext[c];
+    Accepted al;
+    al.read = (uint32_t)(cv >> kReadShift);
+    al.a = (uint32_t)a;
+    al.b = (uint16_t)(x.y >> 16);
+    al.e = (uint16_t)(x.y & 0xffffu);
+    al.pos0 = (uint32_t)(d + al.b);
+    al.score = x.x;
+    al.strand = (uint32_t)((cv >> kStrandShift) & 1ull);
+    acc[o] = al;
+    key1[o] = ((off[a] + al.pos0) << 11) | ((uint64_t)al.strand << 10) | (1023u - al.b);
+    val[o] = o;
+  }
+}
+
+// the second sort's keys, in the first sort's order: read << 11 | 1024 - score
+__global__ __launch_bounds__(kAB) void k_al_key2(const Accepted* __restrict__ acc, const uint64_t* __restrict__ order, uint64_t n,
+                                                 uint64_t* __restrict__ key2) {
+  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    const Accepted al = acc[order[i]];
+    key2[i] = ((uint64_t)al.read << 11) | (1024u - al.score);
+  }
+}
+
+__device__ __forceinline__ uint64_t lower_bound(const uint64_t* __restrict__ v, uint64_t n, uint64_t x) {
+  uint64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (v[mid] < x) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+struct BatchOut {  // where the batch's arrays go on from: the records in front of this call's, the pool bytes likewise
+  mg_aln_rec* recs;
+  mg_aln_place* places;
+  mg_aln_edit* edits;
+  mg_aln_bases* bases;
+  uint8_t* pool;
+  uint64_t pool_base;
+};
+
+// One thread per read of the batch walks its accepted alignments in order.  kEmit = false: nkept[r], npool[r] = the bytes its
+// primary's codes take.  kEmit = true: the records and their side arrays at rec_at[r], the codes at pool_at[r].
+template <bool kEmit>
+__global__ __launch_bounds__(kAB) void k_al_select(const Accepted* __restrict__ acc, const uint64_t* __restrict__ key2,
+                                                   const uint64_t* __restrict__ order, uint64_t nacc_aln, uint64_t r0, uint64_t nreads,
+                                                   const uint8_t* __restrict__ bases, const uint64_t* __restrict__ offs, uint32_t P,
+                                                   uint32_t max_secondary, uint32_t sec_pct, uint32_t* __restrict__ nkept,
+                                                   uint32_t* __restrict__ npool, unsigned long long* __restrict__ aligned,
+                                                   const uint64_t* __restrict__ rec_at, const uint64_t* __restrict__ pool_at, BatchOut out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t q0 = (uint64_t)blockIdx.x * blockDim.x; q0 < nreads; q0 += stride) {  // (uniform trips: the ballot)
+    const uint64_t q = q0 + threadIdx.x;
+    uint32_t kept = 0;
+    if (q < nreads) {
+      const uint64_t lo = lower_bound(key2, nacc_aln, q << 11), hi = lower_bound(key2, nacc_aln, (q + 1) << 11);
+      const uint32_t L = (uint32_t)(offs[r0 + q + 1] - offs[r0 + q]);
+      uint32_t ka[mga::kMaxSecondary + 1], ks[mga::kMaxSecondary + 1], kp[mga::kMaxSecondary + 1], ke[mga::kMaxSecondary + 1];
+      uint32_t best = 0, pool_bytes = 0;
+      for (uint64_t i = lo; i < hi && kept < 1 + max_secondary; ++i) {
+        const Accepted al = acc[order[i]];
+        const uint32_t span = (uint32_t)al.e - al.b, end = al.pos0 + span;
+        bool ok = kept == 0 || mga::secondary_ok(al.score, best, sec_pct);
+        for (uint32_t t = 0; ok && t < kept; ++t) ok = !mga::overlaps(ka[t], ks[t], kp[t], ke[t], al.a, al.strand, al.pos0, end);
+        if (!ok) continue;
+        if (kept == 0) {
+          best = al.score;
+          pool_bytes = (span + 1) / 2;
+        }
+        if (kEmit) {
+          const uint64_t o = rec_at[q] + kept;
+          mg_aln_rec rec;
+          rec.ref_new = al.a | (kept == 0 ? MG_REC_NEW_BIT : 0u);
+          rec.matched = span;
+          rec.total = L;
+          rec.flag_len = (16u * al.strand + (kept ? 256u : 0u)) | ((kept ? 0u : L) << MG_REC_LEN_SHIFT);
+          out.recs[o] = rec;
+          if (out.places) out.places[o] = mg_aln_place{al.pos0, span};
+          if (out.edits) out.edits[o] = mg_aln_edit{mga::nm_of(span, al.score, P), span};
+          if (out.bases) {
+            if (kept) {
+              out.bases[o] = mg_aln_bases{0, 0, 0};
+            } else {
+              const uint64_t pa = pool_at[q];
+              out.bases[o] = mg_aln_bases{out.pool_base + pa, al.pos0, span};
+              const uint8_t* read = bases + offs[r0 + q];
+              uint8_t* dst = out.pool + out.pool_base + pa;
+              for (uint32_t j = 0; j < span; j += 2) {
+                uint32_t byte = 0;
+                for (uint32_t t = 0; t < 2 && j + t < span; ++t) {
+                  const uint32_t col = al.b + j + t;
+                  const uint32_t cd = al.strand ? mga::comp(mga::code_of(read[L - 1 - col])) : mga::code_of(read[col]);
+                  byte |= cd << (4u * t);
+                }
+                dst[j >> 1] = (uint8_t)byte;
+              }
+            }
+          }
+        }
+        ka[kept] = al.a;
+        ks[kept] = al.strand;
+        kp[kept] = al.pos0;
+        ke[kept] = end;
+        ++kept;
+      }
+      if (!kEmit) {
+        nkept[q] = kept;
+        npool[q] = pool_bytes;
+      }
+    }
+    if (!kEmit) {
+      const unsigned long long m = __ballot(kept != 0);
+      if (m && (threadIdx.x & 63u) == 0) atomicAdd(aligned, (unsigned long long)__builtin_popcountll(m));
+    }
+  }
+}
+
+unsigned al_grid(uint64_t items) { return grid_cap(grid_for(items, kAB, (unsigned)ctx().num_cus * 8), "align_grid"); }
+
+int fetch_u64(const void* d, uint64_t* h) {
+  hipStream_t st = ctx().stream;
+  MG_HIP(hipMemcpyAsync(h, d, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  MG_HIP(hipStreamSynchronize(st));
+  return MG_OK;
+}
+
+// what the library may still take: free memory and its own cached blocks
+int mem_room(uint64_t* room) {
+  uint64_t f = 0, t = 0, pooled = 0;
+  MG_TRY(mg_mem_info(&f, &t, &pooled));
+  *room = f + pooled;
+  return MG_OK;
+}
+
+// A side array of the batch grown to hold `need` bytes, its first `have` bytes kept.
+int grow(DevBuf& buf, uint64_t have, uint64_t need) {
+  if (buf.p && buf.bytes >= need) return MG_OK;
+  DevBuf nb;
+  const uint64_t want = buf.p ? (need > 2 * buf.bytes ? need : 2 * buf.bytes) : need;
+  if (nb.alloc(want < 256 ? 256 : want) != MG_OK) return MG_ERR_NOMEM;
+  if (have) MG_HIP(hipMemcpyAsync(nb.p, buf.p, have, hipMemcpyDeviceToDevice, ctx().stream));
+  MG_HIP(hipStreamSynchronize(ctx().stream));  // (the old block goes back to the pool behind the copy)
+  buf = std::move(nb);
+  return MG_OK;
+}
+
+struct AlignJob {
+  const mg_align_index* ix;
+  const mg_refseq* ref;
+  const uint8_t* d_bases;
+  const uint64_t* d_offs;
+  mg_align_params p;
+  unsigned want;
+  mg_sam_batch* sb;
+  uint64_t stats[5] = {0, 0, 0, 0, 0};
+};
+
+constexpr uint64_t kBytesPerCand = 64;  // the candidate, its sorted copy, the distinct one and its count, the radix sort's own, the scan result and flag, the scan's words
+
+// reads [r0, r1) -> their records behind the batch's; halves the range while its candidates do not fit
+int align_range(AlignJob& j, uint64_t r0, uint64_t r1) {
+  if (r1 - r0 > kMaxBatchReads) {
+    for (uint64_t r = r0; r < r1; r += kMaxBatchReads) MG_TRY(align_range(j, r, r + kMaxBatchReads < r1 ? r + kMaxBatchReads : r1));
+    return MG_OK;
+  }
+  Context& c = ctx();
+  hipStream_t st = c.stream;
+  const mg_align_index* ix = j.ix;
+  const uint64_t nreads = r1 - r0;
+  uint64_t g[2] = {0, 0};
+  MG_TRY(fetch_u64(j.d_offs + r0, &g[0]));
+  MG_TRY(fetch_u64(j.d_offs + r1, &g[1]));
+  DevBuf small;  // [0] the cursor, [1] the distinct candidates, [2] the aligned reads
+  MG_TRY(small.alloc(4 * sizeof(uint64_t)));
+  unsigned long long* d_cursor = small.as<unsigned long long>();
+  MG_HIP(hipMemsetAsync(small.p, 0, 4 * sizeof(uint64_t), st));
+  uint64_t ncand = 0;
+  if (g[1] > g[0] && ix->nuniq) {
+    ProfScope ps("align_seed");
+    hipLaunchKernelGGL(k_al_seed<false>, dim3(al_grid(g[1] - g[0])), dim3(kAB), 0, st, j.d_bases, j.d_offs, r0, r1, g[0], g[1], j.p.k,
+                       j.p.w, j.p.max_occ, ix->ukey.as<uint64_t>(), ix->ustart.as<uint64_t>(), ix->ucount.as<uint32_t>(), ix->nuniq,
+                       ix->vals.as<uint64_t>(), d_cursor, (uint64_t*)nullptr);
+    MG_HIP(hipGetLastError());
+    MG_TRY(fetch_u64(d_cursor, &ncand));
+  }
+  uint64_t room = 0;
+  MG_TRY(mem_room(&room));
+  uint64_t budget = room / 2 / kBytesPerCand;
+  if (budget > 0xfffffff0ull) budget = 0xfffffff0ull;  // (the run-length encoder counts in 32 bits)
+  if (dbg("align_batch_cands") > 0) budget = (uint64_t)dbg("align_batch_cands");
+  if (ncand > budget) {
+    if (nreads < 2)
+      return fail(MG_ERR_NOMEM, "the %llu candidates of one read (%llu bytes) do not fit on the device", (unsigned long long)ncand,
+                  (unsigned long long)(ncand * kBytesPerCand));
+    small.release();
+    const uint64_t mid = r0 + nreads / 2;
+    MG_TRY(align_range(j, r0, mid));
+    return align_range(j, mid, r1);
+  }
+  j.stats[0] += nreads;
+  mg_sam_batch* sb = j.sb;
+  uint64_t ndist = 0, nacc_aln = 0;
+  DevBuf cand, sorted, dist, counts, ext, flag, at, acc, k1, v1, k2, v2;
+  if (ncand) {
+    if (cand.alloc(ncand * 8) != MG_OK || sorted.alloc(ncand * 8) != MG_OK || dist.alloc(ncand * 8) != MG_OK ||
+        counts.alloc(ncand * 4) != MG_OK)
+      return fail(MG_ERR_NOMEM, "the %llu candidates of a batch (%llu bytes) do not fit on the device", (unsigned long long)ncand,
+                  (unsigned long long)(ncand * kBytesPerCand));
+    MG_HIP(hipMemsetAsync(d_cursor, 0, sizeof(uint64_t), st));
+    {
+      ProfScope ps("align_seed");
+      hipLaunchKernelGGL(k_al_seed<true>, dim3(al_grid(g[1] - g[0])), dim3(kAB), 0, st, j.d_bases, j.d_offs, r0, r1, g[0], g[1], j.p.k,
+                         j.p.w, j.p.max_occ, ix->ukey.as<uint64_t>(), ix->ustart.as<uint64_t>(), ix->ucount.as<uint32_t>(), ix->nuniq,
+                         ix->vals.as<uint64_t>(), d_cursor, cand.as<uint64_t>());
+      MG_HIP(hipGetLastError());
+    }
+    {
+      ProfScope ps("align_unique");
+      MG_TRY(sort_keys(cand.as<uint64_t>(), sorted.as<uint64_t>(), ncand, 64));
+      MG_TRY(rle_keys(sorted.as<uint64_t>(), ncand, dist.as<uint64_t>(), counts.as<uint32_t>(), small.as<uint64_t>() + 1));
+    }
+    MG_TRY(fetch_u64(small.as<uint64_t>() + 1, &ndist));
+    cand.release();
+    sorted.release();
+    counts.release();
+  }
+  if (ndist) {
+    if (ext.alloc(ndist * sizeof(uint2)) != MG_OK || flag.alloc(ndist * 4) != MG_OK || at.alloc((ndist + 1) * 8) != MG_OK)
+      return fail(MG_ERR_NOMEM, "the %llu distinct candidates of a batch do not fit on the device", (unsigned long long)ndist);
+    {
+      ProfScope ps("align_extend");
+      hipLaunchKernelGGL(k_al_extend, dim3(al_grid(ndist)), dim3(kAB), 0, st, dist.as<uint64_t>(), ndist, r0, j.d_bases, j.d_offs,
+                         j.ref->codes, ix->off.as<uint64_t>(), (uint64_t)ix->nacc, (int32_t)j.p.mismatch, j.p.min_score, ext.as<uint2>(),
+                         flag.as<uint32_t>());
+      MG_HIP(hipGetLastError());
+    }
+    MG_TRY(exclusive_sum_u32_to_u64(flag.as<uint32_t>(), at.as<uint64_t>(), ndist, &nacc_aln));
+  }
+  j.stats[2] += ndist;
+  j.stats[3] += nacc_aln;
+  ProfScope ps("align_select");
+  if (nacc_aln) {
+    if (acc.alloc(nacc_aln * sizeof(Accepted)) != MG_OK || k1.alloc(nacc_aln * 8) != MG_OK || v1.alloc(nacc_aln * 8) != MG_OK ||
+        k2.alloc(nacc_aln * 8) != MG_OK || v2.alloc(nacc_aln * 8) != MG_OK)
+      return fail(MG_ERR_NOMEM, "the %llu accepted alignments of a batch do not fit on the device", (unsigned long long)nacc_aln);
+    hipLaunchKernelGGL(k_al_compact, dim3(al_grid(ndist)), dim3(kAB), 0, st, dist.as<uint64_t>(), ext.as<uint2>(), flag.as<uint32_t>(),
+                       at.as<uint64_t>(), ndist, ix->off.as<uint64_t>(), (uint64_t)ix->nacc, acc.as<Accepted>(), k1.as<uint64_t>(),
+                       v1.as<uint64_t>());
+    MG_HIP(hipGetLastError());
+    // stable, least significant part first: (a, pos0, strand, d), then (read, score descending)
+    MG_TRY(sort_pairs_u64(k1.as<uint64_t>(), k2.as<uint64_t>(), v1.as<uint64_t>(), v2.as<uint64_t>(), nacc_aln, 51));
+    hipLaunchKernelGGL(k_al_key2, dim3(al_grid(nacc_aln)), dim3(kAB), 0, st, acc.as<Accepted>(), v2.as<uint64_t>(), nacc_aln,
+                       k1.as<uint64_t>());
+    MG_HIP(hipGetLastError());
+    MG_TRY(sort_pairs_u64(k1.as<uint64_t>(), k2.as<uint64_t>(), v2.as<uint64_t>(), v1.as<uint64_t>(), nacc_aln, 36));
+  }
+  dist.release();
+  ext.release();
+  flag.release();
+  at.release();
+  // (k2: the sorted keys, v1: the alignments' indices in that order)
+  DevBuf nkept, npool, rec_at, pool_at;
+  MG_TRY(nkept.alloc(nreads * 4));
+  MG_TRY(npool.alloc(nreads * 4));
+  MG_TRY(rec_at.alloc((nreads + 1) * 8));
+  MG_TRY(pool_at.alloc((nreads + 1) * 8));
+  BatchOut none{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  hipLaunchKernelGGL(k_al_select<false>, dim3(al_grid(nreads)), dim3(kAB), 0, st, acc.as<Accepted>(), k2.as<uint64_t>(), v1.as<uint64_t>(),
+                     nacc_aln, r0, nreads, j.d_bases, j.d_offs, j.p.mismatch, j.p.max_secondary, j.p.sec_pct, nkept.as<uint32_t>(),
+                     npool.as<uint32_t>(), d_cursor + 2, (const uint64_t*)nullptr, (const uint64_t*)nullptr, none);
+  MG_HIP(hipGetLastError());
+  uint64_t nrec = 0, npool_bytes = 0, aligned = 0;
+  MG_TRY(exclusive_sum_u32_to_u64(nkept.as<uint32_t>(), rec_at.as<uint64_t>(), nreads, &nrec));
+  MG_TRY(exclusive_sum_u32_to_u64(npool.as<uint32_t>(), pool_at.as<uint64_t>(), nreads, &npool_bytes));
+  MG_TRY(fetch_u64(d_cursor + 2, &aligned));
+  j.stats[1] += aligned;
+  j.stats[4] += nrec;
+  if (!nrec) return MG_OK;
+  const uint64_t have = sb->nrecs, total = have + nrec;
+  if (grow(sb->recs, have * sizeof(mg_aln_rec), total * sizeof(mg_aln_rec)) != MG_OK ||
+      ((j.want & MG_BATCH_PLACES) && grow(sb->places, have * sizeof(mg_aln_place), total * sizeof(mg_aln_place)) != MG_OK) ||
+      ((j.want & MG_BATCH_EDITS) && grow(sb->edits, have * sizeof(mg_aln_edit), total * sizeof(mg_aln_edit)) != MG_OK) ||
+      ((j.want & MG_BATCH_BASES) && (grow(sb->bases, have * sizeof(mg_aln_bases), total * sizeof(mg_aln_bases)) != MG_OK ||
+                                     grow(sb->pool, sb->npool, sb->npool + npool_bytes + 16) != MG_OK)))
+    return fail(MG_ERR_NOMEM, "the %llu records of the reads aligned so far (%llu bytes) do not fit on the device",
+                (unsigned long long)total, (unsigned long long)(total * 48));
+  BatchOut out{sb->recs.as<mg_aln_rec>() + have,
+               (j.want & MG_BATCH_PLACES) ? sb->places.as<mg_aln_place>() + have : nullptr,
+               (j.want & MG_BATCH_EDITS) ? sb->edits.as<mg_aln_edit>() + have : nullptr,
+               (j.want & MG_BATCH_BASES) ? sb->bases.as<mg_aln_bases>() + have : nullptr,
+               (j.want & MG_BATCH_BASES) ? sb->pool.as<uint8_t>() : nullptr,
+               sb->npool};
+  hipLaunchKernelGGL(k_al_select<true>, dim3(al_grid(nreads)), dim3(kAB), 0, st, acc.as<Accepted>(), k2.as<uint64_t>(), v1.as<uint64_t>(),
+                     nacc_aln, r0, nreads, j.d_bases, j.d_offs, j.p.mismatch, j.p.max_secondary, j.p.sec_pct, (uint32_t*)nullptr,
+                     (uint32_t*)nullptr, (unsigned long long*)nullptr, rec_at.as<uint64_t>(), pool_at.as<uint64_t>(), out);
+  MG_HIP(hipGetLastError());
+  MG_HIP(hipStreamSynchronize(st));  // (the scratch of this batch goes back to the pool behind its kernels)
+  sb->nrecs = total;
+  if (j.want & MG_BATCH_BASES) sb->npool += npool_bytes;
+  return MG_OK;
+}
+
+int check_params(const mg_align_params* p) {
+  if (p->k < mga::kMinK || p->k > mga::kMaxK || p->k % 2 == 0) return fail(MG_ERR_ARG, "k = %u: odd and within 11 to 31", p->k);
+  if (p->w < 1 || p->w > mga::kMaxW) return fail(MG_ERR_ARG, "w = %u: within 1 to 32", p->w);
+  if (p->max_occ < 1 || p->max_occ > 65535) return fail(MG_ERR_ARG, "max_occ = %u: within 1 to 65535", p->max_occ);
+  if (p->min_score < 1 || p->min_score > mga::kMaxRead) return fail(MG_ERR_ARG, "min_score = %u: within 1 to 1024", p->min_score);
+  if (p->mismatch < 1 || p->mismatch > 64) return fail(MG_ERR_ARG, "mismatch = %u: within 1 to 64", p->mismatch);
+  if (p->max_secondary > mga::kMaxSecondary) return fail(MG_ERR_ARG, "max_secondary = %u: within 0 to 15", p->max_secondary);
+  if (p->sec_pct > 100) return fail(MG_ERR_ARG, "sec_pct = %u: within 0 to 100", p->sec_pct);
+  return MG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mg_align_index_build(const mg_refseq* ref, uint32_t k, uint32_t w, mg_align_index** out) {
+  MG_REQUIRE_READY();
+  if (!ref || !out) return fail(MG_ERR_ARG, "null argument");
+  *out = nullptr;
+  if (k < mga::kMinK || k > mga::kMaxK || k % 2 == 0) return fail(MG_ERR_ARG, "k = %u: odd and within 11 to 31", k);
+  if (w < 1 || w > mga::kMaxW) return fail(MG_ERR_ARG, "w = %u: within 1 to 32", w);
+  Context& c = ctx();
+  hipStream_t st = c.stream;
+  std::unique_ptr<mg_align_index> h(new mg_align_index());
+  h->k = k;
+  h->w = w;
+  h->nacc = ref->nacc;
+  h->nsites = ref->nsites;
+  std::vector<uint64_t> h_off(ref->nacc + 1ull, 0);
+  uint64_t positions = 0;
+  for (uint32_t a = 0; a < ref->nacc; ++a) {
+    h_off[a + 1] = h_off[a] + ref->h_len[a];
+    if (ref->h_len[a] >= k) positions += ref->h_len[a] - k + 1;
+  }
+  if (h->nsites + (ref->nacc + 2ull) * kPad >= (1ull << kStrandShift))
+    return fail(MG_ERR_ARG, "%llu reference bases in %u accessions: the diagonals need more than 39 bits", (unsigned long long)h->nsites,
+                ref->nacc);
+  // by arithmetic, before anything is allocated or launched: 2 / (w + 1) of the positions are expected as entries, each 16 bytes
+  // twice (unsorted and sorted) and 16 bytes of the radix sort's own
+  const uint64_t expect = 2 * positions / (w + 1ull), need = expect * 48;
+  uint64_t room = 0;
+  MG_TRY(mem_room(&room));
+  if (need > room)
+    return fail(MG_ERR_NOMEM, "the aligner's index (%llu bytes for about %llu minimizers) does not fit on the device",
+                (unsigned long long)need, (unsigned long long)expect);
+  MG_TRY(h->off.alloc((ref->nacc + 1ull) * sizeof(uint64_t)));
+  MG_HIP(hipMemcpyAsync(h->off.p, h_off.data(), (ref->nacc + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  MG_HIP(hipStreamSynchronize(st));
+  ProfScope ps("align_index");
+  DevBuf small;
+  MG_TRY(small.alloc(2 * sizeof(uint64_t)));
+  MG_HIP(hipMemsetAsync(small.p, 0, 2 * sizeof(uint64_t), st));
+  unsigned long long* d_cursor = small.as<unsigned long long>();
+  uint64_t nent = 0;
+  const unsigned grid = grid_for(h->nsites, kAB, (unsigned)c.num_cus * 8);
+  if (h->nsites && ref->nacc) {
+    hipLaunchKernelGGL(k_al_ref<false>, dim3(grid), dim3(kAB), 0, st, ref->codes, h->off.as<uint64_t>(), ref->loaded.as<uint8_t>(),
+                       (uint64_t)ref->nacc, h->nsites, k, w, d_cursor, (uint64_t*)nullptr, (uint64_t*)nullptr);
+    MG_HIP(hipGetLastError());
+    MG_TRY(fetch_u64(d_cursor, &nent));
+  }
+  h->nent = nent;
+  if (nent > 0xfffffff0ull) return fail(MG_ERR_ARG, "%llu minimizers: the index holds fewer than 2^32", (unsigned long long)nent);
+  if (nent) {
+    DevBuf ukeys, uvals, rkeys, rcounts;
+    if (ukeys.alloc(nent * 8) != MG_OK || uvals.alloc(nent * 8) != MG_OK || h->keys.alloc(nent * 8) != MG_OK ||
+        h->vals.alloc(nent * 8) != MG_OK)
+      return fail(MG_ERR_NOMEM, "the aligner's index (%llu bytes for %llu minimizers) does not fit on the device",
+                  (unsigned long long)(nent * 48), (unsigned long long)nent);
+    MG_HIP(hipMemsetAsync(d_cursor, 0, sizeof(uint64_t), st));
+    hipLaunchKernelGGL(k_al_ref<true>, dim3(grid), dim3(kAB), 0, st, ref->codes, h->off.as<uint64_t>(), ref->loaded.as<uint8_t>(),
+                       (uint64_t)ref->nacc, h->nsites, k, w, d_cursor, ukeys.as<uint64_t>(), uvals.as<uint64_t>());
+    MG_HIP(hipGetLastError());
+    MG_TRY(sort_pairs_u64(ukeys.as<uint64_t>(), h->keys.as<uint64_t>(), uvals.as<uint64_t>(), h->vals.as<uint64_t>(), nent, 64));
+    MG_HIP(hipStreamSynchronize(st));
+    ukeys.release();
+    uvals.release();
+    // the unique keys: as many as entries at the most, trimmed to their number below
+    if (rkeys.alloc(nent * 8) != MG_OK || rcounts.alloc(nent * 4) != MG_OK)
+      return fail(MG_ERR_NOMEM, "the aligner's unique-key table (%llu bytes) does not fit on the device", (unsigned long long)(nent * 20));
+    MG_TRY(rle_keys(h->keys.as<uint64_t>(), nent, rkeys.as<uint64_t>(), rcounts.as<uint32_t>(), small.as<uint64_t>() + 1));
+    MG_TRY(fetch_u64(small.as<uint64_t>() + 1, &h->nuniq));
+    if (h->ukey.alloc(h->nuniq * 8) != MG_OK || h->ucount.alloc(h->nuniq * 4) != MG_OK || h->ustart.alloc((h->nuniq + 1) * 8) != MG_OK)
+      return fail(MG_ERR_NOMEM, "the aligner's unique-key table (%llu bytes) does not fit on the device",
+                  (unsigned long long)(h->nuniq * 20));
+    MG_HIP(hipMemcpyAsync(h->ukey.p, rkeys.p, h->nuniq * 8, hipMemcpyDeviceToDevice, st));
+    MG_HIP(hipMemcpyAsync(h->ucount.p, rcounts.p, h->nuniq * 4, hipMemcpyDeviceToDevice, st));
+    uint64_t total = 0;
+    MG_TRY(exclusive_sum_u32_to_u64(h->ucount.as<uint32_t>(), h->ustart.as<uint64_t>(), h->nuniq, &total));  // (synchronises)
+    if (total != nent) return fail(MG_ERR_STATE, "the unique-key table counts %llu entries of %llu", (unsigned long long)total,
+                                   (unsigned long long)nent);
+  } else {
+    MG_HIP(hipStreamSynchronize(st));
+  }
+  *out = h.release();
+  return MG_OK;
+}
+
+int mg_align_index_stats(const mg_align_index* ix, uint64_t out4[4]) {
+  if (!ix || !out4) return fail(MG_ERR_ARG, "null argument");
+  out4[0] = ix->nent;
+  out4[1] = ix->nuniq;
+  out4[2] = ix->k;
+  out4[3] = ix->w;
+  return MG_OK;
+}
+
+int mg_align_index_download(const mg_align_index* ix, uint64_t* keys, uint64_t* vals) {
+  MG_REQUIRE_READY();
+  if (!ix || (ix->nent && (!keys || !vals))) return fail(MG_ERR_ARG, "null argument");
+  if (ix->nent) {
+    MG_TRY(mg_memcpy_d2h(keys, ix->keys.p, ix->nent * 8));
+    MG_TRY(mg_memcpy_d2h(vals, ix->vals.p, ix->nent * 8));
+  }
+  return MG_OK;
+}
+
+void mg_align_index_free(mg_align_index* ix) { delete ix; }
+
+int mg_align_reads_dev(const mg_align_index* ix, const mg_refseq* ref, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t nreads,
+                       const mg_align_params* params, unsigned want_mask, mg_sam_batch** batch, uint64_t stats5[5]) {
+  MG_REQUIRE_READY();
+  if (!ix || !ref || !params || !batch || (nreads && (!d_bases || !d_offsets))) return fail(MG_ERR_ARG, "null argument");
+  MG_TRY(check_params(params));
+  if (params->k != ix->k || params->w != ix->w)
+    return fail(MG_ERR_ARG, "the index was built for k = %u, w = %u, not %u, %u", ix->k, ix->w, params->k, params->w);
+  if (ref->nacc != ix->nacc || ref->nsites != ix->nsites) return fail(MG_ERR_ARG, "the index was built for another reference");
+  if (want_mask & ~(MG_BATCH_PLACES | MG_BATCH_EDITS | MG_BATCH_BASES))
+    return fail(MG_ERR_ARG, "an aligned batch carries places, edits and bases only: it is neither keyed nor named");
+  if (reinterpret_cast<uintptr_t>(d_bases) & 7u) return fail(MG_ERR_ARG, "the reads' bases must be 8-byte aligned");
+  std::unique_ptr<mg_sam_batch> fresh;
+  mg_sam_batch* sb = *batch;
+  if (!sb) {
+    fresh.reset(new mg_sam_batch());
+    sb = fresh.get();
+    MG_TRY(sb->recs.alloc(256));
+    sb->placed = (want_mask & MG_BATCH_PLACES) != 0;
+    sb->edited = (want_mask & MG_BATCH_EDITS) != 0;
+    sb->based = (want_mask & MG_BATCH_BASES) != 0;
+    if (sb->placed) MG_TRY(sb->places.alloc(256));
+    if (sb->edited) MG_TRY(sb->edits.alloc(256));
+    if (sb->based) {
+      MG_TRY(sb->bases.alloc(256));
+      MG_TRY(sb->pool.alloc(256));
+    }
+  } else if (sb->keyed || sb->named || sb->placed != ((want_mask & MG_BATCH_PLACES) != 0) ||
+             sb->edited != ((want_mask & MG_BATCH_EDITS) != 0) || sb->based != ((want_mask & MG_BATCH_BASES) != 0)) {
+    return fail(MG_ERR_STATE, "the batch to append to carries other side arrays than this call asks for");
+  }
+  AlignJob j{ix, ref, d_bases, d_offsets, *params, want_mask, sb};
+  if (nreads) MG_TRY(align_range(j, 0, nreads));  // (on failure a fresh batch goes; one handed in keeps what it had)
+  else j.stats[0] = 0;
+  if (stats5)
+    for (int i = 0; i < 5; ++i) stats5[i] = j.stats[i];
+  if (fresh) *batch = fresh.release();
+  return MG_OK;
+}
+
+}  // extern "C"

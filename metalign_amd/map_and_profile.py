@@ -29,8 +29,9 @@ import time
 
 import numpy as np
 
-from . import _hip, assignments, bam, cli, collate, coverage, identity, side_reads, variants
-from .side_outputs import ASSIGNMENTS, COVERAGE, DEPTH, IDENTITY, FAMILIES, SideOutputs, check_flags, write_headers
+from . import _hip, assignments, bam, cli, collate, coverage, identity, refseq, side_reads, variants
+from .side_outputs import (ASSIGNMENTS, COVERAGE, DEPTH, IDENTITY, FAMILIES, SideOutputs, align_params, aligner_is_device, check_flags,
+                           lengths_array, write_headers)
 
 start = time.time()
 RANKS = ['superkingdom', 'phylum', 'class', 'order', 'family', 'genus', 'species', 'strain']
@@ -1027,8 +1028,121 @@ def tree_results_cami(args, taxids2abs):
     return clades2abs
 
 
+ALIGN_PIECE_BYTES = 64 << 20  # --aligner device: the text of a reads file goes up in pieces of this size
+_ALIGN_INDEX = None  # (key, AlignIndex with its RefSeq, the accessions' lengths): built once per run
+
+
+def _reads_pieces(path, piece_bytes):
+    """The text of a reads file, plain or gzip (every member), in pieces of piece_bytes; the last one flagged."""
+    import gzip
+    with (gzip.open(path, 'rb') if _is_gzip(path) else open(path, 'rb')) as fh:
+        prev = fh.read(piece_bytes)
+        while True:
+            nxt = fh.read(piece_bytes)
+            yield prev, not nxt
+            if not nxt:
+                return
+            prev = nxt
+
+
+def _fasta_lengths(path, lengths):
+    """lengths with the length of every accession's first record in the FASTA: what the @SQ lines of an aligner's header say."""
+    out = dict(lengths)
+    for name, bases in reversed(refseq.records_of(refseq.read_bytes(path))):
+        name = name.decode('utf-8', 'replace')
+        if name in out:
+            out[name] = len(bases)
+    return out
+
+
+def _align_index_for(args, hip, acc2info, acc_index, params):
+    """The reference FASTA (--db) parsed on the device and the aligner's index of it, with the accessions' lengths: once per run, and
+    again only for other parameters.  The lengths are db_info's, as coverage.lengths_of gives them without a header.  Where a record
+    of the FASTA has another length than db_info says — the subset db_info of select_db gives every accession of a genome its first
+    row's length, as the reference writes it — the FASTA's own lengths take their place, as the @SQ lines of an aligner's SAM header
+    would, and the reference is parsed again: no accession is left without its bases."""
+    global _ALIGN_INDEX
+    key = (args.db, tuple((a, info[0]) for a, info in acc2info.items()), params.k, params.w)
+    if _ALIGN_INDEX is not None and _ALIGN_INDEX[0] == key and _ALIGN_INDEX[1].handle and _ALIGN_INDEX[1].ref.handle:
+        return _ALIGN_INDEX[1], _ALIGN_INDEX[2]
+    if _ALIGN_INDEX is not None:
+        _ALIGN_INDEX[1].free()
+        _ALIGN_INDEX[1].ref.free()
+        _ALIGN_INDEX = None
+    if not os.path.isfile(args.db):
+        sys.exit('Error: --aligner device aligns to the database FASTA: --db %s does not exist.' % args.db)
+    lengths = coverage.lengths_of([], acc2info)
+    names = _acc_index_of(hip, acc_index)
+    ref = None
+    try:
+        ref = hip.refseq_from_file(args.db, names, lengths_array(lengths, acc_index))
+        if ref.stats().mismatched:
+            ref.free()
+            lengths = _fasta_lengths(args.db, lengths)
+            ref = hip.refseq_from_file(args.db, names, lengths_array(lengths, acc_index))
+        index = hip.align_index(ref, params.k, params.w)
+    except _hip.HipError as e:
+        if ref is not None:
+            ref.free()
+        if e.code != _hip.ERR_NOMEM:
+            raise
+        sys.exit('Error: --aligner device keeps the reference FASTA, one byte per reference base and its minimizer index on the GPU: '
+                 '%s' % e)
+    finally:
+        names.free()
+    _ALIGN_INDEX = (key, index, lengths)
+    return index, lengths
+
+
+def align_file_device(args, path, fmt, acc2info, acc_index, sides):
+    """A reads file (fmt 'fastq' / 'fasta', plain or gzip) aligned on the device (--aligner device; align.py is the definition) ->
+    (ONE SamBatch of all its reads' records, with the side arrays `sides` asks for; the accessions' lengths).  The text goes up piece
+    by piece through the reads ingest (mg_reads_parse_prefix_dev: what a piece leaves of its last record is carried to the next), so
+    neither the text nor the candidates of the whole file are resident at once; the library halves a piece whose candidates do not
+    fit."""
+    hip = _hip.Hip.get()
+    params = align_params(args)
+    index, lengths = _align_index_for(args, hip, acc2info, acc_index, params)
+    fmt = 'fasta_ml' if fmt == 'fasta' else fmt
+    batch, carry = None, b''
+    try:
+        for piece, final in _reads_pieces(path, ALIGN_PIECE_BYTES):
+            text = np.frombuffer(carry + piece, dtype=np.uint8)
+            d_text = hip.array(text if text.size else np.zeros(1, np.uint8))
+            reads = None
+            try:
+                reads, used = hip.parse_reads_prefix_dev(d_text.ptr, text.size, fmt, final)
+                d_text.free()
+                carry = text[used:].tobytes()
+                d_bases, d_offsets = reads.device_ptrs()
+                batch, _ = hip.align_reads_dev(index, d_bases, d_offsets, reads.count, params, placed=sides.placed, edited=sides.edited,
+                                               based=sides.based, batch=batch)
+            finally:
+                d_text.free()
+                if reads is not None:
+                    reads.free()
+    except BaseException:
+        if batch is not None:
+            batch.free()
+        raise
+    return batch, lengths
+
+
+def _compute_abundances_aligned(args, infile, acc2info, tax2info, on_device):
+    """--aligner device: the reads are aligned on the GPU and their records go to stage C where the aligner left them.  No minimap2 is
+    started and --threads is ignored."""
+    sides = SideOutputs.of(args, infile)
+    tables = dense_tables(acc2info, tax2info)
+    _ = tax2info['Unmapped']  # KeyError here, as at :197, when db_info lacks the Unmapped row
+    batch, lengths = align_file_device(args, infile, args.input_type, acc2info, tables[0], sides)
+    taxids2abs, mm, _ = _stage_c(args, batch, sides, lengths, tables, acc2info, tax2info, on_device, False, False)
+    return _abundances_tail(args, taxids2abs, mm, tax2info, on_device)
+
+
 def compute_abundances(args, infile, acc2info, tax2info):
     """One input file -> clade abundances (:404-433)."""
+    if args.input_type != 'sam' and aligner_is_device(args):
+        return _compute_abundances_aligned(args, infile, acc2info, tax2info, bool(getattr(args, 'device_multimap', False)))
     if args.input_type == 'sam':
         instream = open(infile, 'rb')  # bytes go to the device tokeniser as they are
     else:  # stream minimap2's SAM, exactly the reference's invocation (:413-416)

@@ -460,9 +460,41 @@ ASSIGNMENTS, COVERAGE, DEPTH, IDENTITY, VARIANTS = _Assignments(), _Coverage(), 
 FAMILIES = (COVERAGE, DEPTH, IDENTITY, VARIANTS)  # (the order of every open, add and close)
 
 
+def aligner_is_device(args):
+    """--aligner device (callers build Namespaces without it: minimap2)."""
+    return getattr(args, 'aligner', 'minimap2') == 'device'
+
+
+def align_params(args):
+    """--align_* -> align.Params; ValueError names the first value out of its range."""
+    from . import align
+    return align.params(getattr(args, 'align_k', align.K), getattr(args, 'align_w', align.W), getattr(args, 'align_max_occ', align.MAX_OCC),
+                        getattr(args, 'align_min_score', align.MIN_SCORE), getattr(args, 'align_mismatch', align.MISMATCH),
+                        getattr(args, 'align_secondary', align.MAX_SECONDARY), getattr(args, 'align_secondary_pct', align.SEC_PCT))
+
+
+def check_aligner_flags(args):
+    """--aligner device: what it cannot be combined with, and the ranges of its parameters.  Alignment files (SAM / BAM / PAF, by
+    --input_type or the first file's name, as map_main decides) are not aligned: the flag is a no-op there."""
+    if not aligner_is_device(args):
+        return
+    files = getattr(args, 'infiles', ())
+    if getattr(args, 'input_type', 'AUTO') == 'sam' or (files and files[0].endswith(('sam', 'paf', 'bam')) and not hasattr(args, 'reads')):
+        return
+    if ASSIGNMENTS.wanted(args):
+        sys.exit('Error: --aligner device keeps no read names: --read_assignments needs --aligner minimap2 or an alignment file.')
+    if getattr(args, 'collate', 'never') != 'never':
+        sys.exit('Error: --aligner device writes a read\'s alignments next to each other: --collate must stay "never".')
+    try:
+        align_params(args)
+    except ValueError as e:
+        sys.exit('Error: %s' % e)
+
+
 def check_flags(args):
     """What map_main and metalign.main refuse before a process group, the library or a GPU is touched."""
     world = int(os.environ.get('WORLD_SIZE', '1'))
+    check_aligner_flags(args)
     paf = getattr(args, 'paf_input', False) or any(f.endswith('.paf') for f in getattr(args, 'infiles', ()))
     for fam in (ASSIGNMENTS,) + FAMILIES:
         if not fam.wanted(args):
