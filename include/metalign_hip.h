@@ -115,8 +115,9 @@ int mg_device_count(void);
  *   default 8 MiB, at least 4 KiB), genome_guard (test hook: mg_genomes_parse_dev fills the 16 bytes behind its bases and the
  *   word behind its offsets with 0xa5 before its kernels run); cov_grid (test hook, k3_grid's meaning for k_cov_add /
  *   k_cov_count, mg_coverage.hip); depth_grid (test hook, the same for every grid of mg_depth.hip); ident_grid (test hook, the same for k_ident_add, mg_identity.hip); var_grid (test hook, the same for every grid of mg_variants.hip); mm_hash_bits (test hook, mg_profile_mm_iterate_dev: only this many low bits of a list's hash
- *   are kept, so that different lists collide); align_grid (test hook, k3_grid's meaning for the seeding, extension and selection
- *   grids of mg_align.hip); align_batch_cands (test hook: mg_align_reads_dev halves a batch of reads with more candidates than this).
+ *   are kept, so that different lists collide); align_grid (test hook, k3_grid's meaning for the seeding, extension, refinement and selection
+ *   grids of mg_align.hip); align_batch_cands (test hook: mg_align_reads_dev halves a batch of reads with more candidates than this);
+ *   align_gap_bytes (test hook: mg_align_reads_gapped_dev halves a batch whose refined candidates' workspace takes more bytes than this).
  * Needs no device and no mg_init.  MG_ERR_ARG for a key that does not exist. */
 int mg_debug_set(const char* key, int64_t value);
 int64_t mg_debug_get(const char* key);
@@ -1154,7 +1155,8 @@ int mg_records_mask_unique_dev(const mg_aln_rec* d_recs, uint64_t n, const uint6
                                const uint32_t* d_ref2tax, uint32_t nref, mg_aln_rec* d_out, uint64_t* d_stats2);
 
 /* READS ALIGNED ON THE DEVICE (--aligner device; metalign_amd/csrc/mg_align.hip; the definition is metalign_amd/align.py): an
- * ungapped seed-and-extend aligner of short reads, neither a port of minimap2 nor on a par with it.
+ * seed-and-extend aligner of short reads (ungapped unless mg_align_reads_gapped_dev is given a band), neither a port of minimap2
+ * nor on a par with it.
  * index_build: the minimizers (k odd in 11 .. 31, w in 1 .. 32) of every loaded row of the reference, by key, with the table of
  *   unique keys.  The bytes are checked against mg_mem_info by arithmetic before anything is allocated or launched: MG_ERR_NOMEM
  *   with the byte count in the message.  MG_ERR_ARG for k or w out of range, or a reference whose diagonals need more than 39 bits.
@@ -1167,7 +1169,16 @@ int mg_records_mask_unique_dev(const mg_aln_rec* d_recs, uint64_t n, const uint6
  *   (*batch == NULL: a new batch).  want_mask: MG_BATCH_PLACES, MG_BATCH_EDITS, MG_BATCH_BASES (any other bit: MG_ERR_ARG; a batch to
  *   append to must have been made with the same mask, else MG_ERR_STATE).  The batch is neither keyed nor named; every primary
  *   carries MG_REC_NEW_BIT.  stats5 (optional): reads, aligned reads, distinct candidates, accepted candidates, records of THIS call.
- *   A range of reads whose candidates do not fit is halved; MG_ERR_NOMEM when one read's do not.  Synchronises. */
+ *   A range of reads whose candidates do not fit is halved; MG_ERR_NOMEM when one read's do not.  Synchronises.
+ * reads_gapped_dev (--align_band): reads_dev with the gapped extension of mg_align_gap.  band 0 is reads_dev itself.  With band B in
+ *   1 .. 31 every accepted candidate whose ungapped segment is shorter than its read is REFINED: a local alignment with affine gaps
+ *   (a gap of g bases costs gap_open + g * gap_extend; gap_open 0 .. 64, gap_extend 1 .. 64) over the cells within B of the
+ *   candidate's diagonal takes the place of its scan (align.py: extend_gapped), so that insertions and deletions of up to B bases
+ *   are found.  A refined record's matched = its M columns, its total = the read's length + its D columns (every
+ *   CIGAR operation, as the tokenisers count a SAM line), its place = the reference span, its edit = (mismatches + I + D columns,
+ *   M + I + D columns), its pile = the read's code per M column and the gap code 5 per D column.  The workspace of the refined
+ *   candidates (4 + 2 L + 2 B bytes each) joins the arithmetic that halves a range of reads.  A value out of range: MG_ERR_ARG.
+ *   stats6 (optional): stats5, then the refined candidates. */
 typedef struct mg_align_params {
   uint32_t k, w;           /* as the index's */
   uint32_t max_occ;        /* a minimizer with more entries than this seeds nothing (1 .. 65535) */
@@ -1183,6 +1194,14 @@ int mg_align_index_download(const mg_align_index* ix, uint64_t* keys, uint64_t* 
 void mg_align_index_free(mg_align_index* ix);
 int mg_align_reads_dev(const mg_align_index* ix, const mg_refseq* ref, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t nreads,
                        const mg_align_params* params, unsigned want_mask, mg_sam_batch** batch, uint64_t stats5[5]);
+typedef struct mg_align_gap {
+  uint32_t band;        /* 0: no gapped extension; else the cells within this many diagonals of the candidate's (1 .. 31) */
+  uint32_t gap_open;    /* 0 .. 64 */
+  uint32_t gap_extend;  /* 1 .. 64 */
+} mg_align_gap;
+int mg_align_reads_gapped_dev(const mg_align_index* ix, const mg_refseq* ref, const uint8_t* d_bases, const uint64_t* d_offsets,
+                              uint64_t nreads, const mg_align_params* params, const mg_align_gap* gap, unsigned want_mask,
+                              mg_sam_batch** batch, uint64_t stats6[6]);
 
 /* Host-buffer convenience, single shard = whole stream. Capacities: mm_* as
  * above with mm_cap_reads / mm_cap_entries entries available. */

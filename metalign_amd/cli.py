@@ -107,7 +107,7 @@ _OPTIONS = {
     'aligner': dict(default='minimap2', choices=['minimap2', 'device'],
                     help='What aligns a reads file: "minimap2" (default: the external program, started as the reference starts it) or '
                          '"device": the seed-and-extend aligner on the GPU (metalign_amd/align.py is the definition), which needs no '
-                         'minimap2 installed and ignores --threads. It is ungapped, single-end, gives no MAPQ, keeps no read names '
+                         'minimap2 installed and ignores --threads. It is ungapped unless --align_band is given, single-end, gives no MAPQ, keeps no read names '
                          '(no --read_assignments) and runs on one GPU; it is not minimap2 and does not reproduce its alignments. '
                          'No effect on SAM / BAM / PAF input.'),
     'align_k': dict(type=int, default=15, help='--aligner device: the k-mer length of the seeds (default 15; odd, 11 to 31).'),
@@ -121,6 +121,12 @@ _OPTIONS = {
                             '(default 5; 0 to 15).'),
     'align_secondary_pct': dict(type=int, default=80, help='--aligner device: a secondary alignment has at least this percentage '
                                 'of the primary\'s score (default 80).'),
+    'align_band': dict(type=int, default=0, help='--aligner device: gapped extension. 0 (default): none, the aligner is ungapped. '
+                       'B in 1 to 31: an alignment that does not cover its whole read is redone with affine gaps within B diagonals '
+                       'of its seed\'s, which finds insertions and deletions of up to B bases (8 is a good value for short reads).'),
+    'align_gap_open': dict(type=int, default=6, help='--align_band: what opening a gap subtracts (default 6; 0 to 64). A gap of g '
+                           'bases costs --align_gap_open + g * --align_gap_extend.'),
+    'align_gap_extend': dict(type=int, default=1, help='--align_band: what each base of a gap subtracts (default 1; 1 to 64).'),
     'device_multimap': dict(action='store_true', help='Resolve multimapped reads on the GPU (their lists never leave '
                             'the device; abundances equal the default path to ~1e-15 relative, not byte for byte).'),
 }
@@ -141,7 +147,7 @@ _TOOLS = {
                  'variants', 'variant_sites', 'variant_min_depth', 'variant_min_count', 'variant_min_freq',
                  'consensus', 'consensus_ambiguity', 'consensus_min_called', 'ani', 'vcf', 'reference',
                  'aligner', 'align_k', 'align_w', 'align_max_occ', 'align_min_score', 'align_mismatch', 'align_secondary',
-                 'align_secondary_pct']),
+                 'align_secondary_pct', 'align_band', 'align_gap_open', 'align_gap_extend']),
     'select_db': dict(
         description='Run CMash and select a subset of the whole database to align to.',
         positionals=[('reads', dict(help='Reads file (FASTA / FASTQ, optionally .gz, or a BAM of reads).')),
@@ -161,7 +167,7 @@ _TOOLS = {
                  'variants', 'variant_sites', 'variant_min_depth', 'variant_min_count', 'variant_min_freq',
                  'consensus', 'consensus_ambiguity', 'consensus_min_called', 'ani', 'vcf', 'reference',
                  'aligner', 'align_k', 'align_w', 'align_max_occ', 'align_min_score', 'align_mismatch', 'align_secondary',
-                 'align_secondary_pct']),
+                 'align_secondary_pct', 'align_band', 'align_gap_open', 'align_gap_extend']),
 }
 
 

@@ -11,16 +11,23 @@
 //     k_al_seed<true>   ... and writes one 64-bit candidate per entry: read << 40 | strand << 39 | (pad(a) + d)
 //     sort_keys + rle   the DISTINCT candidates
 //     k_al_extend       THE HOT PATH: one lane per distinct candidate scans its diagonal eight columns per step
-//     compaction, two stable sorts: the accepted alignments by (read, score descending, a, pos0, strand, d)
+//     compaction (k_al_compact): the accepted alignments
+//     band > 0 (--align_band; mg_align_gap_core.h holds the per-cell rules):
+//       k_al_gap_mark<false / true>   the REFINED ones (segment shorter than the read): counted with their workspace, then listed
+//       k_al_gap        one wavefront per refined candidate: the banded table with affine gaps row by row, lane = band offset,
+//                       four remembered bits per cell in LDS, then the walk back, which leaves the alignment's columns in HBM
+//     two stable sorts: the accepted alignments by (read, score descending, a, pos0, strand, d)
 //     k_al_select<false / true>   one thread per read walks its list (overlap and secondary rules), counts, then writes records,
 //                       places, edits, base entries and the pool
 //
 // pad(a) = off[a] + (a + 1) * 1024 keeps the diagonals of neighbouring accessions apart: d reaches from -(L - k) >= -1009 up to
 // len[a] - 1, so pad(a) + d names (a, d) uniquely and a read never aligns across a boundary.  Everything is integers.
 #include <memory>
+#include <optional>
 #include <vector>
 
 #include "mg_align_core.h"
+#include "mg_align_gap_core.h"
 #include "mg_internal.h"
 
 using namespace mg;
@@ -42,11 +49,18 @@ constexpr unsigned kReadShift = 40, kStrandShift = 39;
 constexpr uint64_t kDiagMask = (1ull << kStrandShift) - 1;
 constexpr uint64_t kMaxBatchReads = 1ull << 24;
 
-struct Accepted {  // one accepted alignment
-  uint32_t read, a, pos0, score;
-  uint16_t b, e;
-  uint32_t strand;
+struct Accepted {  // one accepted alignment: [b, e) of the oriented read on [pos0, pos0 + span) of row a
+  uint32_t read, a, pos0;
+  uint16_t score, b, e, span, nm, matched;  // nm: the edits; matched: the M columns
+  uint16_t nops, strand;                    // nops: the columns of a refined alignment (0: ungapped, span M columns)
+  uint64_t ops;                             // a refined one's columns in the workspace, the LAST column first
 };
+
+// the first sort's key: (a, pos0), then strand, then d ascending.  pos0 - d is b without gaps and within the band of it with them.
+constexpr uint32_t kDiagOrder = 1023u + mga::kMaxBand;
+__device__ __forceinline__ uint64_t key1_of(uint64_t site, uint32_t strand, int64_t pos0_minus_d) {
+  return (site << 12) | ((uint64_t)strand << 11) | (uint64_t)((int64_t)kDiagOrder - pos0_minus_d);
+}
 
 __device__ __forceinline__ uint64_t pad_of(const uint64_t* __restrict__ off, uint64_t a) { return off[a] + (a + 1) * kPad; }
 
@@ -221,12 +235,12 @@ __global__ __launch_bounds__(kAB) void k_al_extend(const uint64_t* __restrict__ 
   }
 }
 
-// the accepted candidates, compacted: their alignments, the first sort's keys ((a, pos0) << 11 | strand << 10 | 1023 - b: a's
-// pos0, then strand, then d = pos0 - b ascending) and their own indices as the values
+// the accepted candidates, compacted: their alignments, the first sort's keys (key1_of) and their own indices as the values
 __global__ __launch_bounds__(kAB) void k_al_compact(const uint64_t* __restrict__ cand, const uint2* __restrict__ ext,
                                                     const uint32_t* __restrict__ flag, const uint64_t* __restrict__ at, uint64_t ncand,
-                                                    const uint64_t* __restrict__ off, uint64_t nacc, Accepted* __restrict__ acc,
-                                                    uint64_t* __restrict__ key1, uint64_t* __restrict__ val) {
+                                                    const uint64_t* __restrict__ off, uint64_t nacc, uint32_t P,
+                                                    Accepted* __restrict__ acc, uint64_t* __restrict__ key1,
+                                                    uint64_t* __restrict__ val) {
   uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (; c < ncand; c += stride) {
@@ -241,11 +255,170 @@ __global__ __launch_bounds__(kAB) void k_al_compact(const uint64_t* __restrict__
     al.b = (uint16_t)(x.y >> 16);
     al.e = (uint16_t)(x.y & 0xffffu);
     al.pos0 = (uint32_t)(d + al.b);
-    al.score = x.x;
-    al.strand = (uint32_t)((cv >> kStrandShift) & 1ull);
+    al.score = (uint16_t)x.x;
+    al.span = al.matched = (uint16_t)(al.e - al.b);
+    al.nm = (uint16_t)mga::nm_of(al.span, x.x, P);
+    al.nops = 0;
+    al.strand = (uint16_t)((cv >> kStrandShift) & 1ull);
+    al.ops = 0;
     acc[o] = al;
-    key1[o] = ((off[a] + al.pos0) << 11) | ((uint64_t)al.strand << 10) | (1023u - al.b);
+    key1[o] = key1_of(off[a] + al.pos0, al.strand, al.b);
     val[o] = o;
+  }
+}
+
+// the most columns a refined alignment of an L-base read takes: M + I <= L, and D <= 2B + I (the band)
+__device__ __forceinline__ uint32_t gap_ops_cap(uint32_t L, uint32_t B) { return 2u * L + 2u * B; }
+
+// The refined candidates among the accepted: the segment is shorter than the read.  kEmit = false counts them (cur[0]), their
+// workspace bytes (cur[1]) and their longest read (cur[2]); kEmit = true lists them and gives each its place in the workspace.
+template <bool kEmit>
+__global__ __launch_bounds__(kAB) void k_al_gap_mark(Accepted* __restrict__ acc, uint64_t n, uint64_t r0,
+                                                     const uint64_t* __restrict__ offs, uint32_t B,
+                                                     unsigned long long* __restrict__ cur, uint32_t* __restrict__ list) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t o0 = (uint64_t)blockIdx.x * blockDim.x; o0 < n; o0 += stride) {  // (uniform trips: the wave reserves together)
+    const uint64_t o = o0 + threadIdx.x;
+    uint32_t cap = 0, L = 0;
+    if (o < n) {
+      const uint64_t r = r0 + acc[o].read;
+      L = (uint32_t)(offs[r + 1] - offs[r]);
+      if ((uint32_t)acc[o].e - acc[o].b < L) cap = gap_ops_cap(L, B);
+    }
+    const uint64_t at = wave_reserve(cap ? 1u : 0u, cur), at_ops = wave_reserve(cap, cur + 1);
+    if (!cap) continue;
+    if (kEmit) {
+      list[at] = (uint32_t)o;
+      acc[o].ops = at_ops;
+    } else {
+      atomicMax(cur + 2, (unsigned long long)L);
+    }
+  }
+}
+
+constexpr uint32_t kNoCell = 0xffu;  // in the staged window of the reference: a column outside the accession
+
+// what a wavefront of k_al_gap keeps in LDS for reads of up to max_len bases: the remembered bits (eight rows of a lane in one
+// word), the oriented read's codes, and the window [d - B, d + L + B) of the reference
+__host__ __device__ inline uint32_t gap_tb_words(uint32_t max_len) { return (max_len + 7u) / 8u * 64u; }
+__host__ __device__ inline uint32_t gap_read_bytes(uint32_t max_len) { return (max_len + 3u) & ~3u; }
+__host__ __device__ inline uint32_t gap_lds_bytes(uint32_t max_len, uint32_t B) {
+  return gap_tb_words(max_len) * 4u + gap_read_bytes(max_len) + ((max_len + 2u * B + 3u) & ~3u);
+}
+
+// One wavefront per refined candidate, lane t = the band offset j - i - d + B, one read row per step.  X takes the lane's own H of the
+// row before, I the H and I of lane t + 1's (one move down the lanes), D the largest offer of the lanes below in this row (an
+// exclusive prefix maximum: log2 of the band steps up the lanes).  Each cell's four bits go to LDS, eight rows of a lane per
+// word; the walk back reads them, every lane alike, and lane 0 writes the columns.  Strand 1 is reversed and complemented while
+// the read is staged.  Nothing outside [0, n) of the candidate's accession is read: the window is staged under that test.
+__global__ __launch_bounds__(64) void k_al_gap(const uint32_t* __restrict__ list, uint64_t nref, uint64_t r0,
+                                               const uint8_t* __restrict__ bases, const uint64_t* __restrict__ offs,
+                                               const uint8_t* __restrict__ codes, const uint64_t* __restrict__ off, int32_t P, int32_t B,
+                                               int32_t O, int32_t E, uint32_t max_len, Accepted* __restrict__ acc,
+                                               uint64_t* __restrict__ key1, uint8_t* __restrict__ ops) {
+  extern __shared__ uint32_t gap_lds[];
+  uint32_t* tb = gap_lds;
+  uint8_t* rd = reinterpret_cast<uint8_t*>(gap_lds + gap_tb_words(max_len));
+  uint8_t* gw = rd + gap_read_bytes(max_len);
+  const int32_t t = (int32_t)threadIdx.x;
+  const bool in_band = t <= 2 * B;
+  for (uint64_t x = blockIdx.x; x < nref; x += gridDim.x) {
+    const uint32_t o = list[x];
+    const Accepted al = acc[o];
+    const uint64_t r = r0 + al.read;
+    const uint8_t* read = bases + offs[r];
+    const int32_t L = (int32_t)(offs[r + 1] - offs[r]);
+    const uint8_t* ref = codes + off[al.a];
+    const int64_t n = (int64_t)(off[al.a + 1] - off[al.a]);
+    const int64_t d = (int64_t)al.pos0 - (int64_t)al.b;
+    __syncthreads();  // (the walk of the candidate before has read the LDS)
+    if ((uint32_t)L <= max_len) {
+      for (int32_t i = t; i < L; i += 64) {
+        const uint32_t c = mga::code_of(read[al.strand ? L - 1 - i : i]);
+        rd[i] = (uint8_t)(al.strand ? mga::comp(c) : c);
+      }
+      for (int32_t u = t; u < L + 2 * B; u += 64) {
+        const int64_t j = d - B + u;
+        gw[u] = j >= 0 && j < n ? ref[j] : (uint8_t)kNoCell;
+      }
+    }
+    __syncthreads();
+    if ((uint32_t)L > max_len) continue;  // (never: max_len is the longest refined read's)
+    int32_t Hp = 0, Ip = mga::kGapNone;
+    uint32_t best = 0, word = 0;
+    for (int32_t i = 0; i < L; ++i) {
+      const uint32_t oc = rd[i], gc = in_band ? gw[i + t] : kNoCell;
+      const bool ex = gc != kNoCell;
+      const int32_t h_up = __shfl_down(Hp, 1, 64), i_up = __shfl_down(Ip, 1, 64);
+      const bool up_ex = ex && i > 0 && t < 2 * B;  // cell (i - 1, j): the same column, a row above, offset t + 1
+      const int32_t X = Hp + mga::gap_sub(oc, gc, P);
+      const int32_t I = mga::gap_ins(up_ex, h_up, i_up, O, E);
+      const int32_t Hq = mga::gap_max(mga::gap_max(0, X), I);
+      int32_t pm = __shfl_up(mga::gap_del_offer(ex, Hq, t, E), 1, 64);
+      if (t == 0) pm = mga::kGapNone;
+      for (int32_t s = 1; s <= 2 * B; s <<= 1) {
+        const int32_t y = __shfl_up(pm, s, 64);
+        if (t >= s) pm = mga::gap_max(pm, y);
+      }
+      const int32_t D = ex ? mga::gap_del_prefix(pm, t, O, E) : mga::kGapNone;
+      const int32_t H = ex ? mga::gap_h(X, I, D) : 0;
+      const int32_t h_left = __shfl_up(H, 1, 64);
+      word |= mga::gap_bits(H, X, I, D, Hp, h_up, h_left, O, E) << (4u * ((uint32_t)i & 7u));
+      if (((uint32_t)i & 7u) == 7u || i == L - 1) {
+        tb[((uint32_t)i >> 3) * 64u + (uint32_t)t] = word;
+        word = 0;
+      }
+      if (ex && H > 0) {
+        const uint32_t key = mga::gap_best_pack(H, i, t);
+        best = key > best ? key : best;
+      }
+      Hp = H;
+      Ip = ex ? I : mga::kGapNone;
+    }
+#pragma unroll
+    for (int32_t s = 32; s > 0; s >>= 1) {
+      const uint32_t y = (uint32_t)__shfl_xor((int32_t)best, s, 64);
+      best = y > best ? y : best;
+    }
+    __syncthreads();  // (the bits of every lane are in LDS)
+    if (best == 0) continue;  // (never: the band holds the diagonal, whose scan was accepted)
+    mga::GapWalk w;
+    w.i = mga::gap_best_i(best);
+    w.t = mga::gap_best_t(best);
+    const int32_t e = w.i + 1;
+    const int64_t j_end = w.i + d + w.t - B;
+    const uint32_t cap = gap_ops_cap((uint32_t)L, (uint32_t)B);
+    uint32_t nops = 0, nm = 0, matched = 0;
+    uint8_t* out = ops + al.ops;
+    while (!w.done && w.i >= 0 && w.t >= 0 && w.t <= 2 * B && nops < cap) {
+      const int32_t ci = w.i, ct = w.t;
+      const uint32_t nib = (uint32_t)__builtin_amdgcn_readfirstlane(
+          (int32_t)((tb[((uint32_t)ci >> 3) * 64u + (uint32_t)ct] >> (4u * ((uint32_t)ci & 7u))) & 15u));
+      const int32_t op = mga::gap_walk(w, nib);
+      if (op < 0) continue;
+      if (op == (int32_t)mga::kOpM) {
+        ++matched;
+        if (mga::gap_sub(rd[ci], gw[ci + ct], P) < 0) ++nm;
+      } else {
+        ++nm;
+      }
+      if (t == 0) out[nops] = (uint8_t)op;
+      ++nops;
+    }
+    if (t == 0) {
+      const int64_t pos0 = w.i + d + w.t - B;
+      Accepted up = al;
+      up.pos0 = (uint32_t)pos0;
+      up.score = (uint16_t)mga::gap_best_h(best);
+      up.b = (uint16_t)w.i;
+      up.e = (uint16_t)e;
+      up.span = (uint16_t)(j_end - pos0 + 1);
+      up.nm = (uint16_t)nm;
+      up.matched = (uint16_t)matched;
+      up.nops = (uint16_t)nops;
+      acc[o] = up;
+      key1[o] = key1_of(off[al.a] + up.pos0, al.strand, pos0 - d);
+    }
   }
 }
 
@@ -270,6 +443,8 @@ __device__ __forceinline__ uint64_t lower_bound(const uint64_t* __restrict__ v, 
   return lo;
 }
 
+constexpr uint32_t kGapCode = 5;  // a reference base under a deletion, in the pile (mg_variants_core.h)
+
 struct BatchOut {  // where the batch's arrays go on from: the records in front of this call's, the pool bytes likewise
   mg_aln_rec* recs;
   mg_aln_place* places;
@@ -284,8 +459,8 @@ struct BatchOut {  // where the batch's arrays go on from: the records in front 
 template <bool kEmit>
 __global__ __launch_bounds__(kAB) void k_al_select(const Accepted* __restrict__ acc, const uint64_t* __restrict__ key2,
                                                    const uint64_t* __restrict__ order, uint64_t nacc_aln, uint64_t r0, uint64_t nreads,
-                                                   const uint8_t* __restrict__ bases, const uint64_t* __restrict__ offs, uint32_t P,
-                                                   uint32_t max_secondary, uint32_t sec_pct, uint32_t* __restrict__ nkept,
+                                                   const uint8_t* __restrict__ bases, const uint64_t* __restrict__ offs,
+                                                   const uint8_t* __restrict__ ops, uint32_t max_secondary, uint32_t sec_pct, uint32_t* __restrict__ nkept,
                                                    uint32_t* __restrict__ npool, unsigned long long* __restrict__ aligned,
                                                    const uint64_t* __restrict__ rec_at, const uint64_t* __restrict__ pool_at, BatchOut out) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -299,7 +474,7 @@ __global__ __launch_bounds__(kAB) void k_al_select(const Accepted* __restrict__ 
       uint32_t best = 0, pool_bytes = 0;
       for (uint64_t i = lo; i < hi && kept < 1 + max_secondary; ++i) {
         const Accepted al = acc[order[i]];
-        const uint32_t span = (uint32_t)al.e - al.b, end = al.pos0 + span;
+        const uint32_t span = al.span, end = al.pos0 + span;
         bool ok = kept == 0 || mga::secondary_ok(al.score, best, sec_pct);
         for (uint32_t t = 0; ok && t < kept; ++t) ok = !mga::overlaps(ka[t], ks[t], kp[t], ke[t], al.a, al.strand, al.pos0, end);
         if (!ok) continue;
@@ -311,12 +486,12 @@ __global__ __launch_bounds__(kAB) void k_al_select(const Accepted* __restrict__ 
           const uint64_t o = rec_at[q] + kept;
           mg_aln_rec rec;
           rec.ref_new = al.a | (kept == 0 ? MG_REC_NEW_BIT : 0u);
-          rec.matched = span;
-          rec.total = L;
+          rec.matched = al.matched;
+          rec.total = L + (span - al.matched);  // (every CIGAR operation, as the tokenisers count a line: L and the D columns)
           rec.flag_len = (16u * al.strand + (kept ? 256u : 0u)) | ((kept ? 0u : L) << MG_REC_LEN_SHIFT);
           out.recs[o] = rec;
           if (out.places) out.places[o] = mg_aln_place{al.pos0, span};
-          if (out.edits) out.edits[o] = mg_aln_edit{mga::nm_of(span, al.score, P), span};
+          if (out.edits) out.edits[o] = mg_aln_edit{al.nm, al.nops ? al.nops : span};
           if (out.bases) {
             if (kept) {
               out.bases[o] = mg_aln_bases{0, 0, 0};
@@ -325,14 +500,34 @@ __global__ __launch_bounds__(kAB) void k_al_select(const Accepted* __restrict__ 
               out.bases[o] = mg_aln_bases{out.pool_base + pa, al.pos0, span};
               const uint8_t* read = bases + offs[r0 + q];
               uint8_t* dst = out.pool + out.pool_base + pa;
-              for (uint32_t j = 0; j < span; j += 2) {
-                uint32_t byte = 0;
-                for (uint32_t t = 0; t < 2 && j + t < span; ++t) {
-                  const uint32_t col = al.b + j + t;
-                  const uint32_t cd = al.strand ? mga::comp(mga::code_of(read[L - 1 - col])) : mga::code_of(read[col]);
-                  byte |= cd << (4u * t);
+              if (al.nops) {  // a refined alignment: M gives the read's code, D the gap's, I is skipped; span codes in all
+                uint32_t col = al.b, j = 0, byte = 0;
+                for (uint32_t c = al.nops; c-- > 0;) {
+                  const uint32_t op = ops[al.ops + c];
+                  if (op != mga::kOpI) {
+                    const uint32_t cd = op == mga::kOpD ? kGapCode
+                                        : al.strand     ? mga::comp(mga::code_of(read[L - 1 - col]))
+                                                        : mga::code_of(read[col]);
+                    byte |= cd << (4u * (j & 1u));
+                    if (j & 1u) {
+                      dst[j >> 1] = (uint8_t)byte;
+                      byte = 0;
+                    }
+                    ++j;
+                  }
+                  if (op != mga::kOpD) ++col;
                 }
-                dst[j >> 1] = (uint8_t)byte;
+                if (j & 1u) dst[j >> 1] = (uint8_t)byte;
+              } else {
+                for (uint32_t j = 0; j < span; j += 2) {
+                  uint32_t byte = 0;
+                  for (uint32_t t = 0; t < 2 && j + t < span; ++t) {
+                    const uint32_t col = al.b + j + t;
+                    const uint32_t cd = al.strand ? mga::comp(mga::code_of(read[L - 1 - col])) : mga::code_of(read[col]);
+                    byte |= cd << (4u * t);
+                  }
+                  dst[j >> 1] = (uint8_t)byte;
+                }
               }
             }
           }
@@ -390,9 +585,10 @@ struct AlignJob {
   const uint8_t* d_bases;
   const uint64_t* d_offs;
   mg_align_params p;
+  mg_align_gap gap;
   unsigned want;
   mg_sam_batch* sb;
-  uint64_t stats[5] = {0, 0, 0, 0, 0};
+  uint64_t stats[6] = {0, 0, 0, 0, 0, 0};  // [5] the refined candidates
 };
 
 constexpr uint64_t kBytesPerCand = 64;  // the candidate, its sorted copy, the distinct one and its count, the radix sort's own, the scan result and flag, the scan's words
@@ -410,10 +606,10 @@ int align_range(AlignJob& j, uint64_t r0, uint64_t r1) {
   uint64_t g[2] = {0, 0};
   MG_TRY(fetch_u64(j.d_offs + r0, &g[0]));
   MG_TRY(fetch_u64(j.d_offs + r1, &g[1]));
-  DevBuf small;  // [0] the cursor, [1] the distinct candidates, [2] the aligned reads
-  MG_TRY(small.alloc(4 * sizeof(uint64_t)));
+  DevBuf small;  // [0] the cursor, [1] the distinct candidates, [2] the aligned reads, [4 .. 6] the refined: their number, workspace bytes, longest read
+  MG_TRY(small.alloc(8 * sizeof(uint64_t)));
   unsigned long long* d_cursor = small.as<unsigned long long>();
-  MG_HIP(hipMemsetAsync(small.p, 0, 4 * sizeof(uint64_t), st));
+  MG_HIP(hipMemsetAsync(small.p, 0, 8 * sizeof(uint64_t), st));
   uint64_t ncand = 0;
   if (g[1] > g[0] && ix->nuniq) {
     ProfScope ps("align_seed");
@@ -440,7 +636,7 @@ int align_range(AlignJob& j, uint64_t r0, uint64_t r1) {
   j.stats[0] += nreads;
   mg_sam_batch* sb = j.sb;
   uint64_t ndist = 0, nacc_aln = 0;
-  DevBuf cand, sorted, dist, counts, ext, flag, at, acc, k1, v1, k2, v2;
+  DevBuf cand, sorted, dist, counts, ext, flag, at, acc, k1, v1, k2, v2, gap_list, gap_ops;
   if (ncand) {
     if (cand.alloc(ncand * 8) != MG_OK || sorted.alloc(ncand * 8) != MG_OK || dist.alloc(ncand * 8) != MG_OK ||
         counts.alloc(ncand * 4) != MG_OK)
@@ -476,24 +672,70 @@ int align_range(AlignJob& j, uint64_t r0, uint64_t r1) {
     }
     MG_TRY(exclusive_sum_u32_to_u64(flag.as<uint32_t>(), at.as<uint64_t>(), ndist, &nacc_aln));
   }
-  j.stats[2] += ndist;
-  j.stats[3] += nacc_aln;
-  ProfScope ps("align_select");
+  std::optional<ProfScope> ps;  // (the selection's family; the refinement between its launches is a family of its own)
+  ps.emplace("align_select");
   if (nacc_aln) {
     if (acc.alloc(nacc_aln * sizeof(Accepted)) != MG_OK || k1.alloc(nacc_aln * 8) != MG_OK || v1.alloc(nacc_aln * 8) != MG_OK ||
         k2.alloc(nacc_aln * 8) != MG_OK || v2.alloc(nacc_aln * 8) != MG_OK)
       return fail(MG_ERR_NOMEM, "the %llu accepted alignments of a batch do not fit on the device", (unsigned long long)nacc_aln);
     hipLaunchKernelGGL(k_al_compact, dim3(al_grid(ndist)), dim3(kAB), 0, st, dist.as<uint64_t>(), ext.as<uint2>(), flag.as<uint32_t>(),
-                       at.as<uint64_t>(), ndist, ix->off.as<uint64_t>(), (uint64_t)ix->nacc, acc.as<Accepted>(), k1.as<uint64_t>(),
-                       v1.as<uint64_t>());
+                       at.as<uint64_t>(), ndist, ix->off.as<uint64_t>(), (uint64_t)ix->nacc, j.p.mismatch, acc.as<Accepted>(),
+                       k1.as<uint64_t>(), v1.as<uint64_t>());
     MG_HIP(hipGetLastError());
+    if (j.gap.band) {
+      // the refined candidates: counted with their workspace first, which joins the arithmetic of a range that does not fit
+      ps.reset();
+      std::optional<ProfScope> pg;
+      pg.emplace("align_refine");
+      uint64_t g3[3] = {0, 0, 0};
+      hipLaunchKernelGGL(k_al_gap_mark<false>, dim3(al_grid(nacc_aln)), dim3(kAB), 0, st, acc.as<Accepted>(), nacc_aln, r0, j.d_offs,
+                         j.gap.band, d_cursor + 4, (uint32_t*)nullptr);
+      MG_HIP(hipGetLastError());
+      MG_HIP(hipMemcpyAsync(g3, d_cursor + 4, sizeof(g3), hipMemcpyDeviceToHost, st));
+      MG_HIP(hipStreamSynchronize(st));
+      const uint64_t nrefined = g3[0], ops_bytes = g3[1], need = nrefined * 4 + ops_bytes;
+      if (nrefined) {
+        MG_TRY(mem_room(&room));
+        uint64_t ws_budget = room / 2;
+        if (dbg("align_gap_bytes") > 0) ws_budget = (uint64_t)dbg("align_gap_bytes");
+        if (need > ws_budget) {
+          if (nreads < 2)
+            return fail(MG_ERR_NOMEM, "the %llu refined candidates of one read (%llu bytes) do not fit on the device",
+                        (unsigned long long)nrefined, (unsigned long long)need);
+          j.stats[0] -= nreads;
+          pg.reset();  // (the halves' own families are theirs)
+          for (DevBuf* b : {&small, &dist, &ext, &flag, &at, &acc, &k1, &v1, &k2, &v2}) b->release();
+          const uint64_t mid = r0 + nreads / 2;
+          MG_TRY(align_range(j, r0, mid));
+          return align_range(j, mid, r1);
+        }
+        if (gap_list.alloc(nrefined * 4) != MG_OK || gap_ops.alloc(ops_bytes) != MG_OK)
+          return fail(MG_ERR_NOMEM, "the %llu refined candidates of a batch (%llu bytes) do not fit on the device",
+                      (unsigned long long)nrefined, (unsigned long long)need);
+        MG_HIP(hipMemsetAsync(d_cursor + 4, 0, 2 * sizeof(uint64_t), st));
+        hipLaunchKernelGGL(k_al_gap_mark<true>, dim3(al_grid(nacc_aln)), dim3(kAB), 0, st, acc.as<Accepted>(), nacc_aln, r0, j.d_offs,
+                           j.gap.band, d_cursor + 4, gap_list.as<uint32_t>());
+        MG_HIP(hipGetLastError());
+        const uint32_t max_len = (uint32_t)g3[2];
+        const unsigned grid = grid_cap(grid_for(nrefined, 1, (unsigned)c.num_cus * 32), "align_grid");
+        hipLaunchKernelGGL(k_al_gap, dim3(grid), dim3(64), gap_lds_bytes(max_len, j.gap.band), st, gap_list.as<uint32_t>(), nrefined, r0,
+                           j.d_bases, j.d_offs, j.ref->codes, ix->off.as<uint64_t>(), (int32_t)j.p.mismatch, (int32_t)j.gap.band,
+                           (int32_t)j.gap.gap_open, (int32_t)j.gap.gap_extend, max_len, acc.as<Accepted>(), k1.as<uint64_t>(),
+                           gap_ops.as<uint8_t>());
+        MG_HIP(hipGetLastError());
+      }
+      j.stats[5] += nrefined;
+    }
+    if (!ps) ps.emplace("align_select");
     // stable, least significant part first: (a, pos0, strand, d), then (read, score descending)
-    MG_TRY(sort_pairs_u64(k1.as<uint64_t>(), k2.as<uint64_t>(), v1.as<uint64_t>(), v2.as<uint64_t>(), nacc_aln, 51));
+    MG_TRY(sort_pairs_u64(k1.as<uint64_t>(), k2.as<uint64_t>(), v1.as<uint64_t>(), v2.as<uint64_t>(), nacc_aln, 52));
     hipLaunchKernelGGL(k_al_key2, dim3(al_grid(nacc_aln)), dim3(kAB), 0, st, acc.as<Accepted>(), v2.as<uint64_t>(), nacc_aln,
                        k1.as<uint64_t>());
     MG_HIP(hipGetLastError());
     MG_TRY(sort_pairs_u64(k1.as<uint64_t>(), k2.as<uint64_t>(), v2.as<uint64_t>(), v1.as<uint64_t>(), nacc_aln, 36));
   }
+  j.stats[2] += ndist;
+  j.stats[3] += nacc_aln;
   dist.release();
   ext.release();
   flag.release();
@@ -506,7 +748,7 @@ int align_range(AlignJob& j, uint64_t r0, uint64_t r1) {
   MG_TRY(pool_at.alloc((nreads + 1) * 8));
   BatchOut none{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
   hipLaunchKernelGGL(k_al_select<false>, dim3(al_grid(nreads)), dim3(kAB), 0, st, acc.as<Accepted>(), k2.as<uint64_t>(), v1.as<uint64_t>(),
-                     nacc_aln, r0, nreads, j.d_bases, j.d_offs, j.p.mismatch, j.p.max_secondary, j.p.sec_pct, nkept.as<uint32_t>(),
+                     nacc_aln, r0, nreads, j.d_bases, j.d_offs, gap_ops.as<uint8_t>(), j.p.max_secondary, j.p.sec_pct, nkept.as<uint32_t>(),
                      npool.as<uint32_t>(), d_cursor + 2, (const uint64_t*)nullptr, (const uint64_t*)nullptr, none);
   MG_HIP(hipGetLastError());
   uint64_t nrec = 0, npool_bytes = 0, aligned = 0;
@@ -531,7 +773,7 @@ int align_range(AlignJob& j, uint64_t r0, uint64_t r1) {
                (j.want & MG_BATCH_BASES) ? sb->pool.as<uint8_t>() : nullptr,
                sb->npool};
   hipLaunchKernelGGL(k_al_select<true>, dim3(al_grid(nreads)), dim3(kAB), 0, st, acc.as<Accepted>(), k2.as<uint64_t>(), v1.as<uint64_t>(),
-                     nacc_aln, r0, nreads, j.d_bases, j.d_offs, j.p.mismatch, j.p.max_secondary, j.p.sec_pct, (uint32_t*)nullptr,
+                     nacc_aln, r0, nreads, j.d_bases, j.d_offs, gap_ops.as<uint8_t>(), j.p.max_secondary, j.p.sec_pct, (uint32_t*)nullptr,
                      (uint32_t*)nullptr, (unsigned long long*)nullptr, rec_at.as<uint64_t>(), pool_at.as<uint64_t>(), out);
   MG_HIP(hipGetLastError());
   MG_HIP(hipStreamSynchronize(st));  // (the scratch of this batch goes back to the pool behind its kernels)
@@ -548,6 +790,13 @@ int check_params(const mg_align_params* p) {
   if (p->mismatch < 1 || p->mismatch > 64) return fail(MG_ERR_ARG, "mismatch = %u: within 1 to 64", p->mismatch);
   if (p->max_secondary > mga::kMaxSecondary) return fail(MG_ERR_ARG, "max_secondary = %u: within 0 to 15", p->max_secondary);
   if (p->sec_pct > 100) return fail(MG_ERR_ARG, "sec_pct = %u: within 0 to 100", p->sec_pct);
+  return MG_OK;
+}
+
+int check_gap(const mg_align_gap* g) {
+  if (g->band > mga::kMaxBand) return fail(MG_ERR_ARG, "band = %u: within 0 to 31", g->band);
+  if (g->gap_open > 64) return fail(MG_ERR_ARG, "gap_open = %u: within 0 to 64", g->gap_open);
+  if (g->gap_extend < 1 || g->gap_extend > 64) return fail(MG_ERR_ARG, "gap_extend = %u: within 1 to 64", g->gap_extend);
   return MG_OK;
 }
 
@@ -661,9 +910,21 @@ void mg_align_index_free(mg_align_index* ix) { delete ix; }
 
 int mg_align_reads_dev(const mg_align_index* ix, const mg_refseq* ref, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t nreads,
                        const mg_align_params* params, unsigned want_mask, mg_sam_batch** batch, uint64_t stats5[5]) {
+  const mg_align_gap off{0, 6, 1};
+  uint64_t stats6[6];
+  const int rc = mg_align_reads_gapped_dev(ix, ref, d_bases, d_offsets, nreads, params, &off, want_mask, batch, stats6);
+  if (rc == MG_OK && stats5)
+    for (int i = 0; i < 5; ++i) stats5[i] = stats6[i];
+  return rc;
+}
+
+int mg_align_reads_gapped_dev(const mg_align_index* ix, const mg_refseq* ref, const uint8_t* d_bases, const uint64_t* d_offsets,
+                              uint64_t nreads, const mg_align_params* params, const mg_align_gap* gap, unsigned want_mask,
+                              mg_sam_batch** batch, uint64_t stats6[6]) {
   MG_REQUIRE_READY();
-  if (!ix || !ref || !params || !batch || (nreads && (!d_bases || !d_offsets))) return fail(MG_ERR_ARG, "null argument");
+  if (!ix || !ref || !params || !gap || !batch || (nreads && (!d_bases || !d_offsets))) return fail(MG_ERR_ARG, "null argument");
   MG_TRY(check_params(params));
+  MG_TRY(check_gap(gap));
   if (params->k != ix->k || params->w != ix->w)
     return fail(MG_ERR_ARG, "the index was built for k = %u, w = %u, not %u, %u", ix->k, ix->w, params->k, params->w);
   if (ref->nacc != ix->nacc || ref->nsites != ix->nsites) return fail(MG_ERR_ARG, "the index was built for another reference");
@@ -689,11 +950,11 @@ int mg_align_reads_dev(const mg_align_index* ix, const mg_refseq* ref, const uin
              sb->edited != ((want_mask & MG_BATCH_EDITS) != 0) || sb->based != ((want_mask & MG_BATCH_BASES) != 0)) {
     return fail(MG_ERR_STATE, "the batch to append to carries other side arrays than this call asks for");
   }
-  AlignJob j{ix, ref, d_bases, d_offsets, *params, want_mask, sb};
+  AlignJob j{ix, ref, d_bases, d_offsets, *params, *gap, want_mask, sb};
   if (nreads) MG_TRY(align_range(j, 0, nreads));  // (on failure a fresh batch goes; one handed in keeps what it had)
   else j.stats[0] = 0;
-  if (stats5)
-    for (int i = 0; i < 5; ++i) stats5[i] = j.stats[i];
+  if (stats6)
+    for (int i = 0; i < 6; ++i) stats6[i] = j.stats[i];
   if (fresh) *batch = fresh.release();
   return MG_OK;
 }

@@ -30,7 +30,7 @@ import time
 import numpy as np
 
 from . import _hip, assignments, bam, cli, collate, coverage, identity, refseq, side_reads, variants
-from .side_outputs import (ASSIGNMENTS, COVERAGE, DEPTH, IDENTITY, FAMILIES, SideOutputs, align_params, aligner_is_device, check_flags,
+from .side_outputs import (ASSIGNMENTS, COVERAGE, DEPTH, IDENTITY, FAMILIES, SideOutputs, align_gap_params, align_params, aligner_is_device, check_flags,
                            lengths_array, write_headers)
 
 start = time.time()
@@ -1101,7 +1101,7 @@ def align_file_device(args, path, fmt, acc2info, acc_index, sides):
     neither the text nor the candidates of the whole file are resident at once; the library halves a piece whose candidates do not
     fit."""
     hip = _hip.Hip.get()
-    params = align_params(args)
+    params, gap = align_params(args), align_gap_params(args)
     index, lengths = _align_index_for(args, hip, acc2info, acc_index, params)
     fmt = 'fasta_ml' if fmt == 'fasta' else fmt
     batch, carry = None, b''
@@ -1115,8 +1115,8 @@ def align_file_device(args, path, fmt, acc2info, acc_index, sides):
                 d_text.free()
                 carry = text[used:].tobytes()
                 d_bases, d_offsets = reads.device_ptrs()
-                batch, _ = hip.align_reads_dev(index, d_bases, d_offsets, reads.count, params, placed=sides.placed, edited=sides.edited,
-                                               based=sides.based, batch=batch)
+                batch, _, _ = hip.align_reads_gapped_dev(index, d_bases, d_offsets, reads.count, params, gap, placed=sides.placed,
+                                                         edited=sides.edited, based=sides.based, batch=batch)
             finally:
                 d_text.free()
                 if reads is not None:

@@ -473,6 +473,13 @@ def align_params(args):
                         getattr(args, 'align_secondary', align.MAX_SECONDARY), getattr(args, 'align_secondary_pct', align.SEC_PCT))
 
 
+def align_gap_params(args):
+    """--align_band, --align_gap_open, --align_gap_extend -> align.GapParams; ValueError names the first value out of its range."""
+    from . import align
+    return align.gap_params(getattr(args, 'align_band', align.BAND), getattr(args, 'align_gap_open', align.GAP_OPEN),
+                            getattr(args, 'align_gap_extend', align.GAP_EXTEND))
+
+
 def check_aligner_flags(args):
     """--aligner device: what it cannot be combined with, and the ranges of its parameters.  Alignment files (SAM / BAM / PAF, by
     --input_type or the first file's name, as map_main decides) are not aligned: the flag is a no-op there."""
@@ -487,6 +494,7 @@ def check_aligner_flags(args):
         sys.exit('Error: --aligner device writes a read\'s alignments next to each other: --collate must stay "never".')
     try:
         align_params(args)
+        align_gap_params(args)
     except ValueError as e:
         sys.exit('Error: %s' % e)
 
