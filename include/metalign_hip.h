@@ -117,7 +117,8 @@ int mg_device_count(void);
  *   k_cov_count, mg_coverage.hip); depth_grid (test hook, the same for every grid of mg_depth.hip); ident_grid (test hook, the same for k_ident_add, mg_identity.hip); var_grid (test hook, the same for every grid of mg_variants.hip); mm_hash_bits (test hook, mg_profile_mm_iterate_dev: only this many low bits of a list's hash
  *   are kept, so that different lists collide); align_grid (test hook, k3_grid's meaning for the seeding, extension, refinement and selection
  *   grids of mg_align.hip); align_batch_cands (test hook: mg_align_reads_dev halves a batch of reads with more candidates than this);
- *   align_gap_bytes (test hook: mg_align_reads_gapped_dev halves a batch whose refined candidates' workspace takes more bytes than this).
+ *   align_gap_bytes (test hook: mg_align_reads_gapped_dev halves a batch whose refined candidates' workspace takes more bytes than this);
+ *   align_rescue_bytes (test hook: mg_align_reads_paired_dev halves a batch whose rescue tasks take more bytes than this, 72 each).
  * Needs no device and no mg_init.  MG_ERR_ARG for a key that does not exist. */
 int mg_debug_set(const char* key, int64_t value);
 int64_t mg_debug_get(const char* key);
@@ -1178,7 +1179,15 @@ int mg_records_mask_unique_dev(const mg_aln_rec* d_recs, uint64_t n, const uint6
  *   CIGAR operation, as the tokenisers count a SAM line), its place = the reference span, its edit = (mismatches + I + D columns,
  *   M + I + D columns), its pile = the read's code per M column and the gap code 5 per D column.  The workspace of the refined
  *   candidates (4 + 2 L + 2 B bytes each) joins the arithmetic that halves a range of reads.  A value out of range: MG_ERR_ARG.
- *   stats6 (optional): stats5, then the refined candidates. */
+ *   stats6 (optional): stats5, then the refined candidates.
+ * reads_paired_dev (--align_pairs interleaved): reads_gapped_dev with pairs.  pairs == NULL or interleaved == 0 (whatever the other
+ *   fields hold) is reads_gapped_dev itself.  With interleaved == 1 reads 2i and 2i + 1 are mates 1 and 2 of pair i, by position:
+ *   an odd nreads is MG_ERR_ARG, and so is max_insert outside 1 .. 8192 or rescue outside 0 .. 8.  The mates' accepted candidates
+ *   rescue each other (align.py: rescue_pair; rescue anchors per mate, 0: none), the records are chosen per pair (select_pair) and
+ *   carry the pair's FLAG bits (1, 2, 8, 32, 64, 128 beside 16 and 256); a pair's records are mate 1's, then mate 2's, only the first
+ *   of them carries MG_REC_NEW_BIT, and each mate's primary carries its own len(SEQ) and pile.  A range of reads is cut and halved
+ *   at even reads only; the rescue tasks (72 bytes each) join the arithmetic that halves it; MG_ERR_NOMEM when one pair does not fit.
+ *   stats8 (optional): stats6 ("accepted" includes the rescued), then the distinct rescued candidates accepted, then the proper pairs. */
 typedef struct mg_align_params {
   uint32_t k, w;           /* as the index's */
   uint32_t max_occ;        /* a minimizer with more entries than this seeds nothing (1 .. 65535) */
@@ -1202,6 +1211,14 @@ typedef struct mg_align_gap {
 int mg_align_reads_gapped_dev(const mg_align_index* ix, const mg_refseq* ref, const uint8_t* d_bases, const uint64_t* d_offsets,
                               uint64_t nreads, const mg_align_params* params, const mg_align_gap* gap, unsigned want_mask,
                               mg_sam_batch** batch, uint64_t stats6[6]);
+typedef struct mg_align_pairs {
+  uint32_t interleaved;  /* 0: no pairs; 1: reads 2i and 2i + 1 are the mates of pair i */
+  uint32_t max_insert;   /* the largest outer distance of a proper pair (1 .. 8192) */
+  uint32_t rescue;       /* the anchors per mate that may rescue the partner (0 .. 8; 0: no rescue) */
+} mg_align_pairs;
+int mg_align_reads_paired_dev(const mg_align_index* ix, const mg_refseq* ref, const uint8_t* d_bases, const uint64_t* d_offsets,
+                              uint64_t nreads, const mg_align_params* params, const mg_align_gap* gap, const mg_align_pairs* pairs,
+                              unsigned want_mask, mg_sam_batch** batch, uint64_t stats8[8]);
 
 /* Host-buffer convenience, single shard = whole stream. Capacities: mm_* as
  * above with mm_cap_reads / mm_cap_entries entries available. */

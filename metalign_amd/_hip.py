@@ -57,7 +57,7 @@ EXPORTS = [
     "mg_variants_free", "mg_variants_diff", "mg_variants_fetch_diffs",
     "mg_refseq_parse_dev", "mg_refseq_stats", "mg_refseq_loaded", "mg_refseq_download", "mg_refseq_free",
     "mg_records_mask_unique_dev",
-    "mg_align_index_build", "mg_align_index_stats", "mg_align_index_download", "mg_align_index_free", "mg_align_reads_dev", "mg_align_reads_gapped_dev",
+    "mg_align_index_build", "mg_align_index_stats", "mg_align_index_download", "mg_align_index_free", "mg_align_reads_dev", "mg_align_reads_gapped_dev", "mg_align_reads_paired_dev",
     "mg_gunzip_open", "mg_gunzip_read", "mg_gunzip_close", "mg_zcat_files", "mg_stream_thin_file",
     "mg_inflate_dev", "mg_inflated_bytes", "mg_inflated_download", "mg_inflated_free", "mg_inflate_config", "mg_inflate_stats",
     "mg_sketch_genomes", "mg_sketch_genomes_prefix", "mg_db_upload", "mg_db_upload_sorted", "mg_db_ngenomes", "mg_db_max_hash", "mg_db_free",
@@ -1436,6 +1436,11 @@ class _AlignGap(ctypes.Structure):
     _fields_ = [(name, ctypes.c_uint32) for name in ("band", "gap_open", "gap_extend")]
 
 
+class _AlignPairs(ctypes.Structure):
+    """mg_align_pairs: the fields of align.PairParams, in their order."""
+    _fields_ = [(name, ctypes.c_uint32) for name in ("interleaved", "max_insert", "rescue")]
+
+
 class AlignIndex:
     """The minimizer index of a RefSeq on the device (mg_align_index_*; metalign_amd/align.py is the definition): what
     Hip.align_reads_dev seeds the reads in.  Made by Hip.align_index.  It keeps the RefSeq it was built from."""
@@ -1698,6 +1703,27 @@ class Hip:
         else:
             batch.__init__(self, batch.handle)  # (the arrays may have moved)
         return batch, Stats(*(int(x) for x in stats[:5])), int(stats[5])
+
+    def align_reads_paired_dev(self, index, d_bases, d_offsets, nreads, params, gap, pairs, placed=False, edited=False, based=False,
+                               batch=None):
+        """align_reads_gapped_dev with interleaved pairs (align.PairParams, or None; mg_align_reads_paired_dev) -> (SamBatch,
+        align.Stats of this call, align.PairStats of this call: refined candidates, rescued candidates accepted, proper pairs).
+        pairs None or interleaved 0 is align_reads_gapped_dev."""
+        from .align import PairStats, Stats
+        p, g = _AlignParams(*(int(x) for x in params)), _AlignGap(*(int(x) for x in gap))
+        pp = _AlignPairs(*(int(x) for x in pairs)) if pairs is not None else None
+        h = _vp(batch.handle.value if batch is not None else None)
+        stats = np.zeros(8, dtype=np.uint64)
+        self._chk(self.lib.mg_align_reads_paired_dev(index.handle, index.ref.handle, _vp(d_bases), _vp(d_offsets),
+                                                     ctypes.c_uint64(int(nreads)), ctypes.byref(p), ctypes.byref(g),
+                                                     ctypes.byref(pp) if pp is not None else None,
+                                                     _want(placed=placed, edited=edited, based=based), ctypes.byref(h),
+                                                     _np(stats, ctypes.c_uint64)))
+        if batch is None:
+            batch = SamBatch(self, h)
+        else:
+            batch.__init__(self, batch.handle)  # (the arrays may have moved)
+        return batch, Stats(*(int(x) for x in stats[:5])), PairStats(*(int(x) for x in stats[5:]))
 
     def parse_reads_prefix_dev(self, d_text, nbytes, fmt, final):
         """A piece of a reads file in HBM that begins on a record boundary -> (Reads of its whole records, the bytes they take)

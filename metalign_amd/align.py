@@ -4,9 +4,10 @@ This is NOT a port of minimap2 and claims no parity with it: it is a small align
 (mg_align.hip; the per-position rules are in mg_align_core.h and mg_align_gap_core.h) can be held to it exactly.  Without
 --align_band it is UNGAPPED: a read whose only good alignment needs an insertion or deletion aligns in part or not at all.  With
 --align_band B > 0 a candidate whose ungapped segment is shorter than its read is refined by a banded local alignment with affine
-gaps (extend_gapped), which finds insertions and deletions of up to B bases.  It knows no pairs, keeps no names and gives no MAPQ.
-Every read counts as its own read: each primary record carries the new-read bit, whatever the read's name — two reads of one
-name (the mates of a pair in one file) are two reads.
+gaps (extend_gapped), which finds insertions and deletions of up to B bases.  It keeps no names and gives no MAPQ.  Without
+--align_pairs it knows no pairs: every read counts as its own read, each primary record carries the new-read bit, whatever the
+read's name — two reads of one name (the mates of a pair in one file) are two reads.  With --align_pairs interleaved reads 2i and
+2i + 1 are the mates of pair i, BY POSITION (no name is compared): see "Pairs" below.
 
   Codes.  refseq.codes_of: A a 0, C c 1, G g 2, T t 3, every other byte 4.  The complement of a code c < 4 is 3 - c, of 4 it is 4.
   k-mers.  k odd, 11 .. 31.  A k-mer with a code 4 has no key.  Otherwise f = its 2k-bit value (first base most significant), r =
@@ -38,6 +39,26 @@ name (the mates of a pair in one file) are two reads.
       Two candidates either side of one indel refine to overlapping alignments and collapse to one.
   Records.  records(): what the device leaves in its batch.  A record's matched = its M columns and its total = every CIGAR
       operation's length, clips included, as stage C's tokenisers count a SAM line: L without gaps, L + the D columns with them.  sam_lines(): the same alignments as SAM text.
+  Pairs (PairParams: interleaved, max_insert I, rescue R).  The place of an alignment x of a read of L bases is [u, v): u = pos0 - b,
+      v = pos0 + span + (L - e), the whole oriented read, clips included (ungapped: u = d, v = d + L).
+      concordant(): x of mate 1 and y of mate 2 on one accession and on different strands, and with f the strand-0 and r the
+      strand-1 one: u(f) <= u(r), v(f) <= v(r), v(r) - u(f) <= I.
+      Rescue (rescue_pair), after the ungapped extension and before the refinement, judged on the accepted sets A1, A2 as they
+      were BEFORE any rescue: the anchors of mate m are the first R of A_m by order_key.  An anchor (a, s, d) of a mate of L
+      bases, whose partner has k <= L' <= 1024 bases, seeks the partner on strand 1 - s of a over the diagonals rescue_window():
+      s = 0: [d + max(0, L - L'), d + I - L'], s = 1: [d + L - I, d + min(0, L - L')], clipped to [1 - L', n - 1]; an empty
+      range is no task, and neither is one where the partner's set holds a candidate (a, 1 - s, d'') with lo - B <= d'' <= hi + B
+      (B: the band).  Otherwise extend() runs on every d' of the window; the best score wins, the smallest d' among equals, and
+      joins the partner's accepted set if it reaches min_score (a set by (a, strand, d): found twice, added once).  With a band
+      every accepted candidate with e - b < L is then refined, seeded or rescued.
+      Selection (select_pair): C_m = pair_list(): the accepted set of mate m by order_key under the overlap rule, its first 16
+      (select() is C_m filtered by sec_pct and cut at 1 + max_secondary).  The best concordant pair has the highest sum of scores,
+      then the smallest place of x in C1, then of y in C2; x and y are the primaries, a secondary of a mate is another entry of
+      its list whose best concordant partner gives 100 (x.score + y.score) >= sec_pct * best, at most max_secondary, and every
+      record carries FLAG 1 + 2.  Without a concordant pair each mate is selected alone (select()) and carries FLAG 1, and 8
+      where the partner has no record.  Always 64 / 128 for mate 1 / 2, 16 for the own strand, 32 where the partner's primary
+      is on strand 1, 256 on secondaries.  The pair's records are mate 1's, then mate 2's; the new-read bit is on the first of
+      them only; each mate's primary carries its own len(SEQ) and pile.  RNEXT, PNEXT and TLEN are not given.
 """
 import re
 from collections import namedtuple
@@ -61,6 +82,11 @@ BAND, GAP_OPEN, GAP_EXTEND, MAX_BAND = 0, 6, 1, 31
 # a refined alignment: what Aln has (d: the candidate's diagonal), [pos0, pos0 + span) on the reference, one of M I D per column
 GapAln = namedtuple('GapAln', 'a strand d score b e nm pos0 span ops')
 GAP_CODE = 5  # (variants.GAP: a reference base under a deletion, in the pile)
+# (the order of the fields of mg_align_pairs) interleaved 0: no pairs; max_insert: the largest outer distance of a proper pair;
+# rescue: the anchors per mate that may rescue, 0: none
+PairParams = namedtuple('PairParams', 'interleaved max_insert rescue')
+MAX_INSERT, RESCUE, MAX_INSERT_LIMIT, MAX_RESCUE, PAIR_LIST = 1000, 2, 8192, 8, 16
+PairStats = namedtuple('PairStats', 'refined rescued proper')
 
 
 def params(k=K, w=W, max_occ=MAX_OCC, min_score=MIN_SCORE, mismatch=MISMATCH, max_secondary=MAX_SECONDARY, sec_pct=SEC_PCT):
@@ -93,6 +119,20 @@ def gap_params(band=BAND, gap_open=GAP_OPEN, gap_extend=GAP_EXTEND):
     if g.gap_extend < 1 or g.gap_extend > 64:
         raise ValueError('--align_gap_extend must be within 1 to 64.')
     return g
+
+
+def pair_params(interleaved=0, max_insert=MAX_INSERT, rescue=RESCUE):
+    """-> PairParams; ValueError names the first value out of its range."""
+    if interleaved in ('none', 'interleaved'):
+        interleaved = int(interleaved == 'interleaved')
+    pp = PairParams(int(interleaved), int(max_insert), int(rescue))
+    if pp.interleaved not in (0, 1):
+        raise ValueError('--align_pairs must be "none" or "interleaved".')
+    if pp.max_insert < 1 or pp.max_insert > MAX_INSERT_LIMIT:
+        raise ValueError('--align_max_insert must be within 1 to %d.' % MAX_INSERT_LIMIT)
+    if pp.rescue < 0 or pp.rescue > MAX_RESCUE:
+        raise ValueError('--align_rescue must be within 0 to %d.' % MAX_RESCUE)
+    return pp
 
 
 def fmix64(x):
@@ -347,20 +387,184 @@ def align_reads(seqs, ref, p, index=None):
     return align_reads_gapped(seqs, ref, p, GapParams(0, GAP_OPEN, GAP_EXTEND), index)[:2]
 
 
-def records(seqs, alns):
+def place_of(al, L):
+    """-> (u, v): where the whole oriented read of L bases lies on the reference, clips included."""
+    pos0 = pos0_of(al)
+    return pos0 - al.b, pos0 + span_of(al) + (L - al.e)
+
+
+def concordant(x, Lx, y, Ly, I):
+    """x of one mate (Lx bases) and y of the other: a proper pair within the outer distance I?"""
+    if x.a != y.a or x.strand == y.strand:
+        return False
+    (uf, vf), (ur, vr) = (place_of(x, Lx), place_of(y, Ly)) if x.strand == 0 else (place_of(y, Ly), place_of(x, Lx))
+    return uf <= ur and vf <= vr and vr - uf <= I
+
+
+def rescue_window(strand, d, L, Lp, n, I):
+    """An anchor on (strand, d) of a mate of L bases, its partner of Lp bases, an accession of n bases -> (lo, hi): the diagonals
+    of strand 1 - strand on which the partner is sought, or None for an empty range."""
+    lo, hi = (d + max(0, L - Lp), d + I - Lp) if strand == 0 else (d + L - I, d + min(0, L - Lp))
+    lo, hi = max(lo, 1 - Lp), min(hi, n - 1)
+    return (lo, hi) if lo <= hi else None
+
+
+def window_scores(o, ref_codes, lo, hi, P):
+    """extend(o, ref_codes, d, P)[0] for every d of [lo, hi], all diagonals at once (tests hold it to extend())."""
+    n, Lp, W = len(ref_codes), len(o), hi - lo + 1
+    g = np.full(W + Lp - 1, 255, dtype=np.uint8)
+    s, e = max(lo, 0), min(hi + Lp, n)
+    if s < e:
+        g[s - lo:e - lo] = np.frombuffer(bytes(ref_codes), dtype=np.uint8)[s:e]
+    cur, best = np.zeros(W, dtype=np.int32), np.zeros(W, dtype=np.int32)
+    for j, c in enumerate(o):
+        col = g[j:j + W]
+        step = np.where(col == c, 1, -P).astype(np.int32) if c < 4 else np.full(W, -P, dtype=np.int32)
+        cur = np.where(col != 255, np.maximum(cur + step, 0), 0).astype(np.int32)
+        np.maximum(best, cur, out=best)
+    return best
+
+
+def rescue_pair(codes, accepted, ref, p, gp, pp):
+    """codes: the two mates' codes; accepted: their accepted sets before any rescue (lists of Aln) -> ([the alignments rescue
+    adds to mate 1's set, to mate 2's], the tasks)."""
+    added, tasks = [{}, {}], 0
+    for m in (0, 1):
+        L, Lp = len(codes[m]), len(codes[1 - m])
+        if Lp < p.k or Lp > MAX_READ:
+            continue
+        for x in sorted(accepted[m], key=order_key)[:pp.rescue]:
+            win = rescue_window(x.strand, x.d, L, Lp, len(ref.codes[x.a]), pp.max_insert)
+            if win is None:
+                continue
+            lo, hi = win
+            sp = 1 - x.strand
+            if any(y.a == x.a and y.strand == sp and lo - gp.band <= y.d <= hi + gp.band for y in accepted[1 - m]):
+                continue
+            tasks += 1
+            o = revcomp_codes(codes[1 - m]) if sp else codes[1 - m]
+            scores = window_scores(o, ref.codes[x.a], lo, hi, p.mismatch)
+            d = lo + int(np.argmax(scores))  # (the first of the largest: the smallest d')
+            if int(scores[d - lo]) >= p.min_score:
+                score, b, e, nm = extend(o, ref.codes[x.a], d, p.mismatch)
+                assert score == int(scores[d - lo]) and all((y.a, y.strand, y.d) != (x.a, sp, d) for y in accepted[1 - m])
+                added[1 - m][(x.a, sp, d)] = Aln(x.a, sp, d, score, b, e, nm)
+    return [list(added[0].values()), list(added[1].values())], tasks
+
+
+def pair_list(accepted):
+    """C_m: the accepted alignments of one mate by order_key under the overlap rule, the first PAIR_LIST of them."""
+    kept = []
+    for al in sorted(accepted, key=order_key):
+        pos0, span = pos0_of(al), span_of(al)
+        if any(x.a == al.a and x.strand == al.strand and pos0_of(x) < pos0 + span and pos0 < pos0_of(x) + span_of(x) for x in kept):
+            continue
+        kept.append(al)
+        if len(kept) == PAIR_LIST:
+            break
+    return kept
+
+
+def select_pair(acc1, L1, acc2, L2, p, pp):
+    """The accepted alignments of the two mates (of L1 and L2 bases) -> (mate 1's kept ones, mate 2's, proper pair?)."""
+    C, Ls, I = (pair_list(acc1), pair_list(acc2)), (L1, L2), pp.max_insert
+    best = None
+    for i, x in enumerate(C[0]):
+        for j, y in enumerate(C[1]):
+            if concordant(x, L1, y, L2, I) and (best is None or x.score + y.score > best[0]):
+                best = (x.score + y.score, i, j)
+    if best is None:
+        return select(acc1, p), select(acc2, p), False
+    out = []
+    for m in (0, 1):
+        kept = [C[m][best[1 + m]]]
+        for t, x in enumerate(C[m]):
+            if t == best[1 + m] or len(kept) == 1 + p.max_secondary:
+                continue
+            partners = [y.score for y in C[1 - m] if concordant(x, Ls[m], y, Ls[1 - m], I)]
+            if partners and 100 * (x.score + max(partners)) >= p.sec_pct * best[0]:
+                kept.append(x)
+        out.append(kept)
+    return out[0], out[1], True
+
+
+def accepted_of(codes, index, ref, p):
+    """One read's codes -> (its distinct candidates, its accepted alignments: ungapped Aln, in no order)."""
+    cands = candidates(codes, index, p)
+    rc, out = revcomp_codes(codes), []
+    for a, strand, d in cands:
+        score, b, e, nm = extend(rc if strand else codes, ref.codes[a], d, p.mismatch)
+        if score >= p.min_score:
+            out.append(Aln(a, strand, d, score, b, e, nm))
+    return len(cands), out
+
+
+def align_pair(seq1, seq2, index, ref, p, gp, pp):
+    """The two mates' bytes -> (mate 1's kept alignments, mate 2's, proper pair?, distinct candidates, accepted candidates the
+    rescued among them, refined candidates, rescued candidates, rescue tasks)."""
+    codes = [refseq.codes_of(seq1), refseq.codes_of(seq2)]
+    ncand, accepted = 0, []
+    for c in codes:
+        n, acc = accepted_of(c, index, ref, p)
+        ncand += n
+        accepted.append(acc)
+    added, tasks = rescue_pair(codes, accepted, ref, p, gp, pp) if pp.rescue else ([[], []], 0)
+    refined = 0
+    for m in (0, 1):
+        accepted[m] = accepted[m] + added[m]
+        if gp.band > 0:
+            for t, al in enumerate(accepted[m]):
+                if al.e - al.b < len(codes[m]):
+                    o = revcomp_codes(codes[m]) if al.strand else codes[m]
+                    g = extend_gapped(o, ref.codes[al.a], al.d, p.mismatch, gp)
+                    assert g[0] >= al.score, (g, al)
+                    accepted[m][t] = GapAln(al.a, al.strand, al.d, *g)
+                    refined += 1
+    k1, k2, proper = select_pair(accepted[0], len(seq1), accepted[1], len(seq2), p, pp)
+    return k1, k2, proper, ncand, len(accepted[0]) + len(accepted[1]), refined, len(added[0]) + len(added[1]), tasks
+
+
+def align_reads_paired(seqs, ref, p, gp, pp, index=None):
+    """Interleaved mates (an even number of reads) -> ([kept alignments per read], [proper? per pair], Stats, PairStats)."""
+    if len(seqs) % 2:
+        raise ValueError('an odd number of reads cannot be interleaved pairs')
+    if index is None:
+        index = build_index(ref, p.k, p.w)
+    out, proper, ncand, nacc, nref, nres = [], [], 0, 0, 0, 0
+    for i in range(0, len(seqs), 2):
+        k1, k2, pr, c, a, r, x, _ = align_pair(seqs[i], seqs[i + 1], index, ref, p, gp, pp)
+        out += [k1, k2]
+        proper.append(pr)
+        ncand += c
+        nacc += a
+        nref += r
+        nres += x
+    stats = Stats(len(seqs), sum(1 for x in out if x), ncand, nacc, sum(len(x) for x in out))
+    return out, proper, stats, PairStats(nref, nres, sum(proper))
+
+
+def pair_flag(mate, t, al, partner, proper):
+    """The FLAG of record t (0: the primary) of mate `mate` (0 / 1); partner: the other mate's kept alignments."""
+    return (1 + (2 if proper else 0) + (0 if partner else 8) + 16 * al.strand + (32 if partner and partner[0].strand else 0)
+            + (128 if mate else 64) + (256 if t else 0))
+
+
+def records(seqs, alns, proper=None):
     """What the device's batch holds for these reads and their kept alignments: (recs REC_DTYPE[], places, edits, bases entries,
-    the pool's bytes)."""
+    the pool's bytes).  proper: None, or for interleaved pairs one flag per pair (align_reads_paired)."""
     from ._hip import BASES_DTYPE, EDIT_DTYPE, PLACE_DTYPE, REC_DTYPE
     n = sum(len(x) for x in alns)
     recs, places = np.zeros(n, dtype=REC_DTYPE), np.zeros(n, dtype=PLACE_DTYPE)
     edits, entries = np.zeros(n, dtype=EDIT_DTYPE), np.zeros(n, dtype=BASES_DTYPE)
     pool = bytearray()
     r = 0
-    for seq, kept in zip(seqs, alns):
+    for q, (seq, kept) in enumerate(zip(seqs, alns)):
         L = len(seq)
         for t, al in enumerate(kept):
             span, pos0, ops = span_of(al), pos0_of(al), ops_of(al)
-            recs[r] = ((al.a | 0x80000000) if t == 0 else al.a, ops.count('M'), L + ops.count('D'), (16 * al.strand + (256 if t else 0)) | ((0 if t else L) << 12))
+            flag = 16 * al.strand + (256 if t else 0) if proper is None else pair_flag(q % 2, t, al, alns[q ^ 1], proper[q // 2])
+            new = t == 0 and (proper is None or q % 2 == 0 or not alns[q - 1])  # (pairs: the first record of the pair)
+            recs[r] = ((al.a | 0x80000000) if new else al.a, ops.count('M'), L + ops.count('D'), flag | ((0 if t else L) << 12))
             places[r] = (pos0, span)
             edits[r] = (al.nm, len(ops))
             if t == 0:
@@ -382,12 +586,18 @@ _COMP = bytes.maketrans(b'ACGTacgt', b'TGCAtgca')
 _LETTER = bytes(b if b in b'ACGTacgt' else ord('N') for b in range(256))
 
 
-def sam_lines(headers, seqs, quals, names, lengths, alns):
+def sam_lines(headers, seqs, quals, names, lengths, alns, proper=None):
     """The alignments as SAM text (bytes lines with their newline).  headers: the reads' header lines without their first byte
-    (QNAME: up to the first white byte); quals: the reads' qualities, or None for `*`; names, lengths: per accession row."""
+    (QNAME: up to the first white byte); quals: the reads' qualities, or None for `*`; names, lengths: per accession row.
+    proper: None, or for interleaved pairs one flag per pair: both mates get mate 1's QNAME without a trailing /1 or /2 and
+    the pair's FLAG bits; RNEXT, PNEXT and TLEN stay `*`, 0, 0 and MAPQ 255."""
     out = [b'@SQ\tSN:%s\tLN:%d\n' % (nm.encode() if isinstance(nm, str) else nm, int(ln)) for nm, ln in zip(names, lengths)]
-    for hdr, seq, qual, kept in zip(headers, seqs, quals if quals is not None else [None] * len(seqs), alns):
+    for r, (hdr, seq, qual, kept) in enumerate(zip(headers, seqs, quals if quals is not None else [None] * len(seqs), alns)):
+        if proper is not None:
+            hdr = headers[r - r % 2]
         qname = bytes(hdr).split(None, 1)[0] if bytes(hdr).split(None, 1) else b'*'
+        if proper is not None and qname[-2:] in (b'/1', b'/2') and len(qname) > 2:
+            qname = qname[:-2]
         L = len(seq)
         for t, al in enumerate(kept):
             runs = [(m.group(0)[0], len(m.group(0))) for m in re.finditer(r'M+|I+|D+', ops_of(al))]
@@ -401,6 +611,7 @@ def sam_lines(headers, seqs, quals, names, lengths, alns):
             else:
                 s = q = b'*'
             rname = names[al.a].encode() if isinstance(names[al.a], str) else names[al.a]
-            out.append(b'\t'.join([qname, b'%d' % (16 * al.strand + (256 if t else 0)), rname, b'%d' % (pos0_of(al) + 1), b'255', cigar,
+            flag = 16 * al.strand + (256 if t else 0) if proper is None else pair_flag(r % 2, t, al, alns[r ^ 1], proper[r // 2])
+            out.append(b'\t'.join([qname, b'%d' % flag, rname, b'%d' % (pos0_of(al) + 1), b'255', cigar,
                                    b'*', b'0', b'0', s, q, b'NM:i:%d' % al.nm]) + b'\n')
     return out

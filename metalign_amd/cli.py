@@ -107,7 +107,7 @@ _OPTIONS = {
     'aligner': dict(default='minimap2', choices=['minimap2', 'device'],
                     help='What aligns a reads file: "minimap2" (default: the external program, started as the reference starts it) or '
                          '"device": the seed-and-extend aligner on the GPU (metalign_amd/align.py is the definition), which needs no '
-                         'minimap2 installed and ignores --threads. It is ungapped unless --align_band is given, single-end, gives no MAPQ, keeps no read names '
+                         'minimap2 installed and ignores --threads. It is ungapped unless --align_band is given, single-end unless --align_pairs is given, gives no MAPQ, keeps no read names '
                          '(no --read_assignments) and runs on one GPU; it is not minimap2 and does not reproduce its alignments. '
                          'No effect on SAM / BAM / PAF input.'),
     'align_k': dict(type=int, default=15, help='--aligner device: the k-mer length of the seeds (default 15; odd, 11 to 31).'),
@@ -127,6 +127,15 @@ _OPTIONS = {
     'align_gap_open': dict(type=int, default=6, help='--align_band: what opening a gap subtracts (default 6; 0 to 64). A gap of g '
                            'bases costs --align_gap_open + g * --align_gap_extend.'),
     'align_gap_extend': dict(type=int, default=1, help='--align_band: what each base of a gap subtracts (default 1; 1 to 64).'),
+    'align_pairs': dict(default='none', choices=['none', 'interleaved'],
+                        help='--aligner device: paired-end reads. "none" (default): every read is a read of its own. "interleaved": '
+                             'reads 2i and 2i + 1 of the file are mates 1 and 2 of pair i; the mates rescue each other, the records are '
+                             'chosen per pair and carry the pair\'s FLAG bits. Pairing is BY POSITION: the aligner keeps no read names '
+                             'and compares none. An odd number of reads is an error. Not for a BAM of reads.'),
+    'align_max_insert': dict(type=int, default=1000, help='--align_pairs: the largest outer distance of a proper pair, in bases '
+                             '(default 1000; 1 to 8192).'),
+    'align_rescue': dict(type=int, default=2, help='--align_pairs: how many of a mate\'s best alignments may each rescue the other mate '
+                         'within --align_max_insert of them (default 2; 0 to 8, 0: no rescue).'),
     'device_multimap': dict(action='store_true', help='Resolve multimapped reads on the GPU (their lists never leave '
                             'the device; abundances equal the default path to ~1e-15 relative, not byte for byte).'),
 }
@@ -147,7 +156,8 @@ _TOOLS = {
                  'variants', 'variant_sites', 'variant_min_depth', 'variant_min_count', 'variant_min_freq',
                  'consensus', 'consensus_ambiguity', 'consensus_min_called', 'ani', 'vcf', 'reference',
                  'aligner', 'align_k', 'align_w', 'align_max_occ', 'align_min_score', 'align_mismatch', 'align_secondary',
-                 'align_secondary_pct', 'align_band', 'align_gap_open', 'align_gap_extend']),
+                 'align_secondary_pct', 'align_band', 'align_gap_open', 'align_gap_extend', 'align_pairs', 'align_max_insert',
+                 'align_rescue']),
     'select_db': dict(
         description='Run CMash and select a subset of the whole database to align to.',
         positionals=[('reads', dict(help='Reads file (FASTA / FASTQ, optionally .gz, or a BAM of reads).')),
@@ -167,7 +177,8 @@ _TOOLS = {
                  'variants', 'variant_sites', 'variant_min_depth', 'variant_min_count', 'variant_min_freq',
                  'consensus', 'consensus_ambiguity', 'consensus_min_called', 'ani', 'vcf', 'reference',
                  'aligner', 'align_k', 'align_w', 'align_max_occ', 'align_min_score', 'align_mismatch', 'align_secondary',
-                 'align_secondary_pct', 'align_band', 'align_gap_open', 'align_gap_extend']),
+                 'align_secondary_pct', 'align_band', 'align_gap_open', 'align_gap_extend', 'align_pairs', 'align_max_insert',
+                 'align_rescue']),
 }
 
 

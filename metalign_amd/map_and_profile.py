@@ -30,7 +30,7 @@ import time
 import numpy as np
 
 from . import _hip, assignments, bam, cli, collate, coverage, identity, refseq, side_reads, variants
-from .side_outputs import (ASSIGNMENTS, COVERAGE, DEPTH, IDENTITY, FAMILIES, SideOutputs, align_gap_params, align_params, aligner_is_device, check_flags,
+from .side_outputs import (ASSIGNMENTS, COVERAGE, DEPTH, IDENTITY, FAMILIES, SideOutputs, align_gap_params, align_pair_params, align_params, aligner_is_device, check_flags,
                            lengths_array, write_headers)
 
 start = time.time()
@@ -1094,29 +1094,50 @@ def _align_index_for(args, hip, acc2info, acc_index, params):
     return index, lengths
 
 
+def _last_record_start(text, used, fmt):
+    """text[:used] holds whole records of a reads file ('fastq': four lines each; 'fasta_ml': opened by a line that starts with
+    '>') -> the byte at which the last of them begins."""
+    if fmt == 'fastq':
+        at = used
+        for _ in range(5):  # (the record's own four line ends, then the one in front of it)
+            at = text.rfind(b'\n', 0, at)
+            if at < 0:
+                return 0
+        return at + 1
+    return text.rfind(b'\n>', 0, used) + 1
+
+
 def align_file_device(args, path, fmt, acc2info, acc_index, sides):
     """A reads file (fmt 'fastq' / 'fasta', plain or gzip) aligned on the device (--aligner device; align.py is the definition) ->
     (ONE SamBatch of all its reads' records, with the side arrays `sides` asks for; the accessions' lengths).  The text goes up piece
     by piece through the reads ingest (mg_reads_parse_prefix_dev: what a piece leaves of its last record is carried to the next), so
     neither the text nor the candidates of the whole file are resident at once; the library halves a piece whose candidates do not
-    fit."""
+    fit.  Under --align_pairs interleaved every piece handed to the aligner holds whole pairs: where a piece that is not the last
+    parses to an odd number of reads, all but the last are aligned and the text is carried from that read's first byte, found on the
+    host text (_last_record_start).  An odd number of reads in the whole file is an error."""
     hip = _hip.Hip.get()
-    params, gap = align_params(args), align_gap_params(args)
+    params, gap, pairs = align_params(args), align_gap_params(args), align_pair_params(args)
     index, lengths = _align_index_for(args, hip, acc2info, acc_index, params)
     fmt = 'fasta_ml' if fmt == 'fasta' else fmt
     batch, carry = None, b''
     try:
         for piece, final in _reads_pieces(path, ALIGN_PIECE_BYTES):
-            text = np.frombuffer(carry + piece, dtype=np.uint8)
+            whole = carry + piece
+            text = np.frombuffer(whole, dtype=np.uint8)
             d_text = hip.array(text if text.size else np.zeros(1, np.uint8))
             reads = None
             try:
                 reads, used = hip.parse_reads_prefix_dev(d_text.ptr, text.size, fmt, final)
                 d_text.free()
-                carry = text[used:].tobytes()
+                count = reads.count
+                if pairs.interleaved and count % 2:
+                    if final:
+                        sys.exit('Error: --align_pairs interleaved: %s holds an odd number of reads.' % path)
+                    used, count = _last_record_start(whole, used, fmt), count - 1
+                carry = whole[used:]
                 d_bases, d_offsets = reads.device_ptrs()
-                batch, _, _ = hip.align_reads_gapped_dev(index, d_bases, d_offsets, reads.count, params, gap, placed=sides.placed,
-                                                         edited=sides.edited, based=sides.based, batch=batch)
+                batch = hip.align_reads_paired_dev(index, d_bases, d_offsets, count, params, gap, pairs, placed=sides.placed,
+                                                   edited=sides.edited, based=sides.based, batch=batch)[0]
             finally:
                 d_text.free()
                 if reads is not None:

@@ -480,9 +480,18 @@ def align_gap_params(args):
                             getattr(args, 'align_gap_extend', align.GAP_EXTEND))
 
 
+def align_pair_params(args):
+    """--align_pairs, --align_max_insert, --align_rescue -> align.PairParams; ValueError names the first value out of its range."""
+    from . import align
+    return align.pair_params(getattr(args, 'align_pairs', 'none'), getattr(args, 'align_max_insert', align.MAX_INSERT),
+                             getattr(args, 'align_rescue', align.RESCUE))
+
+
 def check_aligner_flags(args):
     """--aligner device: what it cannot be combined with, and the ranges of its parameters.  Alignment files (SAM / BAM / PAF, by
     --input_type or the first file's name, as map_main decides) are not aligned: the flag is a no-op there."""
+    if getattr(args, 'align_pairs', 'none') != 'none' and not aligner_is_device(args):
+        sys.exit('Error: --align_pairs pairs the reads in the aligner on the GPU: it needs --aligner device.')
     if not aligner_is_device(args):
         return
     files = getattr(args, 'infiles', ())
@@ -495,8 +504,14 @@ def check_aligner_flags(args):
     try:
         align_params(args)
         align_gap_params(args)
+        pairs = align_pair_params(args)
     except ValueError as e:
         sys.exit('Error: %s' % e)
+    if pairs.interleaved and hasattr(args, 'reads') and os.path.isfile(args.reads):
+        from . import bam
+        if bam.is_bam(args.reads):
+            sys.exit('Error: --align_pairs interleaved pairs by position, and the mates of a BAM of reads are not next to each other '
+                     'in its FASTQ rendering: give an interleaved FASTQ / FASTA file.')
 
 
 def check_flags(args):
